@@ -12,6 +12,6 @@ rocprofv3 --kernel-trace --pmc SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY S
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o p -- python scripts/prof_gibbs.py 30 > $O/pmc_fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o p -- python scripts/prof_gibbs.py 30 > $O/pmc_write.log 2>&1
 python scripts/summarize_pmc.py $O/${TAG}_pmc.csv $O/pmc_sq $O/pmc_sq2 $O/pmc_fetch $O/pmc_write
-python bench.py --steps 500 --warmup 50 > $O/${TAG}_bench.json 2> $O/bench.err
+python bench.py --full --steps 500 --warmup 50 > $O/${TAG}_bench.json 2> $O/bench.err
 rm -rf $O/trace $O/pmc_sq $O/pmc_sq2 $O/pmc_fetch $O/pmc_write
 ls -la $O

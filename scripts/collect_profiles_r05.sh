@@ -10,17 +10,17 @@ O=gpurun_out/r05; mkdir -p $O
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python bench.py --steps 200 --warmup 20 --no-cpu-baseline --batch 0 --no-pmc > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 cp $O/trace/*/t_kernel_stats.csv $O/r05_kernel_stats.csv 2>/dev/null || cp $O/trace/t_kernel_stats.csv $O/r05_kernel_stats.csv
 rm -rf $O/trace
-timeout 600 python bench.py --steps 500 --warmup 50 > $O/r05_bench.json 2> $O/bench.err
+timeout 600 python bench.py --full --steps 500 --warmup 50 > $O/r05_bench.json 2> $O/bench.err
 for shp in "50000 96 12" "50000 96 4"; do set -- $shp
-  timeout 600 python bench.py --V $1 --S $2 --G $3 --steps 100 --warmup 20 --no-cpu-baseline --batch 0 > $O/r05_bench_V$1_S$2_G$3.json 2>> $O/bench.err
+  timeout 600 python bench.py --full --V $1 --S $2 --G $3 --steps 100 --warmup 20 --no-cpu-baseline --batch 0 > $O/r05_bench_V$1_S$2_G$3.json 2>> $O/bench.err
 done
 cp gpurun_out/pmc_traffic_by_shape.json $O/pmc_traffic_by_shape.json
 python scripts/kernel_regs.py > $O/r05_kernel_regs.txt 2>&1
 [ "$MODE" = quick ] && { ls -la $O; exit 0; }
 ( time timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -8 ) 2>&1 | tee $O/r05_pytest_gpu.txt
-timeout 300 python bench.py --V 1000 --S 16 --G 5 --steps 500 --warmup 50 --no-cpu-baseline > $O/r05_bench_cfg2_V1k_S16_G5.json 2>> $O/bench.err
+timeout 300 python bench.py --full --V 1000 --S 16 --G 5 --steps 500 --warmup 50 --no-cpu-baseline > $O/r05_bench_cfg2_V1k_S16_G5.json 2>> $O/bench.err
 for shp in "10000 192 8" "10000 300 8" "5000 512 8"; do set -- $shp
-  timeout 600 python bench.py --V $1 --S $2 --G $3 --steps 100 --warmup 20 --no-cpu-baseline --batch 0 > $O/r05_bench_V$1_S$2_G$3.json 2>> $O/bench.err
+  timeout 600 python bench.py --full --V $1 --S $2 --G $3 --steps 100 --warmup 20 --no-cpu-baseline --batch 0 > $O/r05_bench_V$1_S$2_G$3.json 2>> $O/bench.err
 done
 for shp in "1000 64 5" "3000 64 5" "10000 64 8" "30000 64 6" "50000 96 8" "50000 96 12"; do python scripts/dbg/prof_nmft_tau.py $shp 2>&1 | tail -1; done > $O/r05_nmft_factorize_tau.txt
 python scripts/chain_phases.py --out $O/r05_chain_phases.json 2>&1 | grep "G=" > $O/r05_chain_phases.txt

@@ -1,4 +1,4 @@
-"""one line of a bench.py JSON line read from stdin: the roofline's durations (event bracket, dispatch latency, the kernel's own)"""
+"""one line of a `bench.py --full` JSON line read from stdin: the roofline's durations (event bracket, dispatch latency, the kernel's own)"""
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d["roofline"]
 print("ms/step %.4f" % d["ms_per_step"], "frac %.4f" % r["frac"], "avg %.1f" % r["avg_kernel_us"], "bracket %.1f" % r["avg_event_bracket_us"],

@@ -18,7 +18,7 @@ ap.add_argument("--out", default="gpurun_out/r04/chain_cost_components.json")
 a = ap.parse_args()
 rows = {}
 for G in range(a.gmin, a.gmax + 1):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--V", str(a.V), "--S", str(a.S), "--G", str(G), "--steps", "60",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--V", str(a.V), "--S", str(a.S), "--G", str(G), "--full", "--steps", "60",
                         "--warmup", "10", "--repeats", "3", "--no-pmc", "--no-cpu-baseline", "--batch", "0"], capture_output=True, text=True)
     try:
         d = json.loads(r.stdout.strip().splitlines()[-1])

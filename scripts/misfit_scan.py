@@ -22,7 +22,7 @@ a = ap.parse_args()
 rows = {}
 for G in [int(x) for x in a.gs.split(",")]:
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--V", str(a.V), "--S", str(a.S), "--G", str(G), "--true-G", str(a.true_G),
-                        "--stats-spec", str(a.stats_spec), "--steps", "60", "--warmup", str(a.warmup), "--repeats", "3", "--no-pmc", "--no-cpu-baseline", "--batch", "0"],
+                        "--stats-spec", str(a.stats_spec), "--full", "--steps", "60", "--warmup", str(a.warmup), "--repeats", "3", "--no-pmc", "--no-cpu-baseline", "--batch", "0"],
                        capture_output=True, text=True)
     try:
         d = json.loads(r.stdout.strip().splitlines()[-1])

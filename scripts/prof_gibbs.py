@@ -1,4 +1,4 @@
-"""The workload of the PMC passes (scripts/collect_profiles.sh, bench.py --pmc): the benchmark's chain (NMFT-initialised) stepping n
+"""The workload of the PMC passes (scripts/collect_profiles.sh, bench.py --full --pmc): the benchmark's chain (NMFT-initialised) stepping n
 Gibbs iterations -- the same state the timed region of bench.py runs in.  usage: prof_gibbs.py [n] [V S G [depth_scale]]"""
 import os
 import sys

@@ -30,7 +30,7 @@ def _torchrun(args, port, timeout=600):
 
 def test_bench_walks_the_rccl_path_with_a_world_of_one():
     argv = ["bench.py", "--gpus", "1", "--steps", "6", "--warmup", "2", "--V", "2000", "--S", "16", "--G", "4", "--no-cpu-baseline",
-            "--no-nmft", "--no-pmc", "--repeats", "3"]
+            "--no-nmft", "--no-pmc", "--repeats", "3", "--full"]
     out = _torchrun(argv, 29731)
     line = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["steps"] == 6 and line["scaling"] == "weak"
