@@ -164,7 +164,6 @@ extern "C" int dsm_ctx_create(dsm_ctx **out, int device)
     dsm_ctx *c = new dsm_ctx();
     c->device = device;
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    if (DSM_AB_ENV("DESMAN_HIP_NMFT_NO_FUSED_REDUCE")) c->nmft_fused = 0;    // A/B switch, see dsm_ctx_set_nmft_fused
     if (getenv("DESMAN_HIP_ONE_STREAM")) c->stream_rng = c->stream;      // several chains per GPU: one hardware queue each
     else {   // the single-workgroup MT19937 refill must not queue behind a full grid of the main stream
         int lo = 0, hi = 0;
@@ -661,7 +660,7 @@ extern "C" int dsm_ctx_sample_stats(dsm_ctx *c, uint32_t iter, uint64_t *sum_mu,
     BIND(c);
     const size_t sg = (size_t)c->S * c->G;
     HIP_TRY(hipMemsetAsync(c->sum_mu, 0, sg * sizeof(unsigned long long), c->stream));
-    TRY(stats_place_ntab(c));
+    TRY(stats_ensure_ntab(c));
     HIP_TRY(hipMemsetAsync(c->esum, 0, 16 * sizeof(unsigned long long), c->stream));
     TRY(k_stats(c, iter));
     TRY(k_esum_fold(c));
@@ -707,7 +706,7 @@ extern "C" int dsm_ctx_debug_stage1(dsm_ctx *c, uint32_t iter, uint32_t *ntab, u
         for (size_t h = 0; h < NH; ++h)
             for (size_t s = 0; s < S; ++s) {                                       // device [rep][H][S] -> [S][H], copies summed
                 uint32_t v = 0;
-                for (int r = 0; r < c->ntab_rep; ++r) v += t[((size_t)r * NH + ((h * stats_ntab_hmul() + (s >> 4) * stats_ntab_swz()) & (NH - 1))) * ld + s];
+                for (int r = 0; r < c->ntab_rep; ++r) v += t[((size_t)r * NH + ((h * DSM_NTAB_HMUL + (s >> 4) * DSM_NTAB_SWZ) & (NH - 1))) * ld + s];
                 ntab[s * NH + h] = v;
             }
     return DSM_OK;
@@ -801,7 +800,7 @@ extern "C" int dsm_ctx_gibbs_update(dsm_ctx *c, int n_iter)
     HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
     // entry state: ll, lp, storeStarState(0)  (HaploSNP_Sampler.py:336-338)
     TRY(eval_state(c, c->gamma, c->eta, c->tau_trace, 1));
-    TRY(stats_place_ntab(c));                            // first call with this table: where its atomics cost least (kernels_stats.hip)
+    TRY(stats_ensure_ntab(c));
     TRY(k_tau_neartie_hint(c));                          // which instantiation of the sweep this call runs (same draws either way)
     double *const P[2] = {c->prior, c->prior + (DSM_MAX_S + 4)};
     int nb_prev = 0;
@@ -894,7 +893,7 @@ static int gibbs_update_sharded(dsm_ctx *c, int n_iter, int v_offset, int v_tota
         TRY(k_finalize(c, nb, -1, 1, c->prior, c->gamma, c->eta));
         HIP_TRY(hipMemsetAsync(c->esum, 0, 16 * sizeof(unsigned long long), c->stream));
     }
-    TRY(stats_place_ntab(c));
+    TRY(stats_ensure_ntab(c));
     double *const P[2] = {c->prior, c->prior + (DSM_MAX_S + 4)};
     int nb_prev = 0;
     for (int it = 0; it < n_iter; ++it) {
@@ -1007,7 +1006,7 @@ extern "C" int dsm_batch_gibbs_update(dsm_ctx *const *ctxs, int K, int n_iter)
         BTRY(alloc_traces(c, n_iter));
         BHIP(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
         BTRY(eval_state(c, c->gamma, c->eta, c->tau_trace, 1));
-        BTRY(stats_place_ntab(c));
+        BTRY(stats_ensure_ntab(c));
         words.emplace_back(c, n_iter);
     }
     g_batch.K = K;
@@ -1194,9 +1193,8 @@ extern "C" int dsm_batch_update_tau(dsm_ctx *const *ctxs, int K, int n_iter, con
 extern "C" int dsm_release_device_caches(void)
 {
     // what the library keeps per process and device beyond the life of a context: the MT19937 jump tables (2 x 50 MB per device, built by the
-    // first long fill) and up to 32 placed subset tables (<= 512 KB each).  No context may be running a fill / a mu/E pass while this is called.
+    // first long fill).  No context may be running a fill while this is called.
     mt_jump_release();
-    stats_ntab_pool_release();
     return DSM_OK;
 }
 
@@ -1344,7 +1342,7 @@ extern "C" int dsm_nmft_set(dsm_ctx *c, const double *tau, const double *gamma, 
     TRY(dev_alloc(&c->ngam_raw, (size_t)G * S));
     TRY(dev_alloc(&c->ngam2, (size_t)G * S));            // the other parity's buffers of the update kernel's own gamma step
     TRY(dev_alloc(&c->ngam_raw2, (size_t)G * S));
-    TRY(dev_alloc(&c->npart, (size_t)std::max(std::max(c->nmft_blocks, nmft_wave_grid(c)), std::max(nmft_wide_grid(c), nmft_use_mfma(c) ? std::max(nmft_mfma_grid(c, false), nmft_mfma_grid(c, true)) : 0)) * ((size_t)G * S + G + 1)));
+    TRY(dev_alloc(&c->npart, (size_t)std::max(c->nmft_blocks, std::max(nmft_wide_grid(c), nmft_use_mfma(c) ? std::max(nmft_mfma_grid(c, false), nmft_mfma_grid(c, true)) : 0)) * ((size_t)G * S + G + 1)));
     TRY(dev_alloc(&c->nstat, (size_t)G * S + 2 * G + 16));
     // reference layout tau[v + a*V][g] -> device layout [v][a][g]
     std::vector<double> t((size_t)V * 4 * G);

@@ -20,13 +20,16 @@
 
 void dsm_set_error(const char *fmt, ...);
 
-// A/B switches of the timing experiments (scripts/dbg/): environment variables that move work around, replace a kernel by an
-// older form or -- DESMAN_HIP_STATS_DBG -- switch parts of a kernel OFF for ablation timing (results are garbage then).  They exist only
-// in the experiment build `make -C desman_amd/csrc ab` (-DDSM_AB_SWITCHES -> lib/libdesman_hip_ab.so, loaded with DESMAN_HIP_LIB=...); in
-// the product library every one of them compiles to its default and no environment variable can change what a kernel computes.  What
-// the product library does read: DESMAN_HIP_DEVICE, DESMAN_HIP_STATS_SPEC (which mu/E specification unforced contexts follow),
-// DESMAN_HIP_ONE_STREAM / DESMAN_HIP_NMFT_GRAPH (set by desman-sweep for concurrent chains), DESMAN_HIP_NTAB_TUNE / DESMAN_HIP_TAU_ORDER
-// (= 0: the measured table place / the fp64-blocks-first order off: same results, tests/test_gpu_fuzz.py), DESMAN_HIP_RCCL.
+// Environment switches of the experiment build `make -C desman_amd/csrc ab` (-DDSM_AB_SWITCHES -> lib/libdesman_hip_ab.so, loaded with
+// DESMAN_HIP_LIB=...); in the product library each compiles to its default and no environment variable can change what a kernel computes.
+//   instruments of open work:  DESMAN_HIP_STATS_DBG (stage-1 ablations: results are garbage then), DESMAN_HIP_NMFT_STAMPS (NMF phase
+//                              stamps; the stage-1 / stage-2 clocks are #ifdef blocks), DESMAN_HIP_TAU_GRID (workgroups of the sweep),
+//                              DESMAN_HIP_LEAN_CAP (stage 1's deferral threshold), DESMAN_HIP_NT_SKIP_TOTALS (near-tie sweep)
+//   test hooks:                DESMAN_HIP_NMFT_FORCE_TIMEOUT (a persistent NMF launch that times out), DESMAN_HIP_NTAB_OFF (where the
+//                              subset table starts)
+// What the product library reads: DESMAN_HIP_DEVICE, DESMAN_HIP_STATS_SPEC (which mu/E specification unforced contexts follow),
+// DESMAN_HIP_ONE_STREAM / DESMAN_HIP_NMFT_GRAPH (set by desman-sweep for concurrent chains), DESMAN_HIP_TAU_ORDER (= 0: the
+// fp64-blocks-first order off, same results: tests/test_gpu_fuzz.py), DESMAN_HIP_RCCL; DESMAN_HIP_LIB is read by desman_amd/_lib.py.
 #ifdef DSM_AB_SWITCHES
 #define DSM_AB_ENV(name) getenv(name)
 #else
@@ -88,19 +91,14 @@ struct dsm_ctx {
     size_t pat_rep_len = 0, pat_x_len = 0;
     uint32_t pat_gen = 0;
     uint32_t *s2_scratch = nullptr; // stage 2 as its own launch with a sample's root level shared by several workgroups (kernels_stats.hip: k_stats_stage2)
-    uint32_t *ntab_raw = nullptr;   // the allocation `ntab` points into (kernels_stats.hip: ensure_ntab places the table inside it)
-    uint32_t *ntab_base = nullptr;  // first place the table can start at (4 KB aligned)
-    size_t ntab_off = 0;            // where past ntab_base the table starts (stats_place_ntab)
-    bool ntab_placed = false;       // the place has been measured (or given)
-    bool ntab_measured = false;     // ... measured: the table goes to the process's pool when the chain ends (kernels_stats.hip: stats_release_ntab)
-    int ntab_ld = 0;                // row stride of the table in words (kernels_stats.hip: stats_ntab_ld)
-    int ntab_xcd = 0;               // 1: the table has a copy per XCD (experiment switch; part of the pool key of a placed table)
+    uint32_t *ntab_raw = nullptr;   // the allocation `ntab` points into (kernels_stats.hip: ensure_ntab, a 4 KB-aligned start)
+    int ntab_ld = 0;                // row stride of the table in words (= S)
     int ntab_rep = 1;               // copies of the table (few subsets x many positions: kernels_stats.hip, stats_ntab_rep)
     unsigned long long *big_list = nullptr;   // stage-1 items deferred to the compacted (BTRS) kernel: cell * 4 + base
     uint32_t *big_count = nullptr;            // DSM_BIG_NL counters, DSM_BIG_STRIDE words apart
     size_t big_cap = 0;
     int stats_grid = 0;             // resident workgroups of stats_agg_kernel
-    int stats_grid_key = -1;        // ... of which instantiation (specification x register-gamma form)
+    int stats_grid_key = -1;        // ... of which specification
     int item_stride = 1;            // items per sample row of `items`
     bool chunked = false;           // items carry reads | chunk << 12 (small problems, see dsm_ctx_set_counts)
     int32_t *blk_tab = nullptr;     // [blk_n][3] workgroup -> {sample, j, n_j} of the mu/E pass
@@ -117,7 +115,6 @@ struct dsm_ctx {
     double alpha = 0.1, delta = 0.1, epsilon = 1e-6;
     // sufficient statistics of the auxiliary counts
     unsigned long long *sum_mu = nullptr;   // [S][G]
-    bool stats_probe = false;               // stats_place_ntab is timing stage 1: k_stats_stage1 leaves the compacted launch out
     unsigned long long *esum = nullptr;     // [4][4] [observed][true], followed by DSM_ESUM_PARTS x [4][4] partial sums of stage 1 (kernels_stats.hip: zero between passes)
     // RNG
     uint32_t *mt_state = nullptr;   // 624 words + position
@@ -213,14 +210,11 @@ int k_log2f_test(dsm_ctx *c, const float *d_in, float *d_out, size_t n);
 int build_stats_items(dsm_ctx *c);          // api.hip: work list of the per-read pass from the resident tensor
 
 // ---- launchers (kernels_stats.hip)
-uint32_t stats_ntab_hmul();                  // odd multiplier of the subset -> table row map
-int stats_place_ntab(dsm_ctx *c);         // measures where the subset table should start (once per table; kernels_stats.hip)
-void stats_release_ntab(dsm_ctx *c);     // the table leaves the context: to the process's pool of placed tables, or freed
-#define DSM_NTAB_PAD 0               // words added to a row of the subset table when S is a multiple of 64 (stats_ntab_ld)
-int stats_ntab_ld(int S);
-uint32_t stats_ntab_swz();                 // the sample's part of the subset table's row map
-#define DSM_NTAB_SWZ 17u                // (any odd number: see stats_ntab_swz)
-void stats_ntab_pool_release();            // kernels_stats.hip: frees the pooled subset tables
+// the subset table's row map: row of (subset H, sample s) = (H DSM_NTAB_HMUL + (s >> 4) DSM_NTAB_SWZ) mod 2^G (kernels_stats.hip: ensure_ntab)
+#define DSM_NTAB_HMUL 0x9E3779B1u       // odd multiplier of the subset
+#define DSM_NTAB_SWZ 17u                // the sample's part (any odd number)
+int stats_ensure_ntab(dsm_ctx *c);         // the subset table of the aggregated pass, allocated and zeroed (kernels_stats.hip)
+void stats_release_ntab(dsm_ctx *c);     // ... freed
 void mt_jump_release();                    // kernels_gibbs.hip: frees the MT19937 jump tables
 int stats_ntab_rep(const dsm_ctx *c);       // copies of the subset table the stage-1 atomics are spread over
 int stats_spec(const dsm_ctx *c);           // 2 / 3 = aggregated sampler (oracle/stats_agg.c), 4 = the same over tau patterns, 1 = per-read (orc_stats_counter)
@@ -263,7 +257,6 @@ bool nmft_use_wave(const dsm_ctx *c);
 bool nmft_use_mfma(const dsm_ctx *c);
 bool nmft_use_wide(const dsm_ctx *c);                      // 128 < S <= 512: nmft_split_kernel
 int nmft_wide_grid(const dsm_ctx *c);
-int nmft_wave_grid(const dsm_ctx *c);
 int nmft_mfma_grid(const dsm_ctx *c, bool fix = false);     // up to four workgroups per CU (five for the fused pass of factorize_tau)
 int k_nmft_wave(dsm_ctx *c, int adjust, int do_update);
 int k_nmft_persist(dsm_ctx *c, int max_iter, double min_change, int fix_gamma, int adjust, int *used);

@@ -30,7 +30,7 @@ struct Stage2Params {
     const double *log_tab;
     int S, G;
     uint32_t k0, k1, iter;
-    uint32_t hmul, swz;             // row of (subset H, sample s) in ntab: (H * hmul + (s >> 4) * swz) mod 2^G (kernels_stats.hip: stats_ntab_hmul / _swz)
+    uint32_t hmul, swz;             // row of (subset H, sample s) in ntab: (H * hmul + (s >> 4) * swz) mod 2^G (dsm_host.h: DSM_NTAB_HMUL / _SWZ)
     uint32_t *big_count;            // work-list counter of stage 1: consumed by now, reset here for the next pass (or null)
     int nsplit;                     // workgroups that share a sample's root level (stand-alone kernel, G >= 11), else 1
     uint32_t *scratch, *ticket;     // [S][S2_TAB_ENTRIES] level-1 tables handed over, [S] arrival counters; zero between passes

@@ -5,7 +5,7 @@
 //   tau_kernel        A1  tau sweep             (sampletau/c_sample_tau.c:95-204)
 //                     A5  log-likelihood        (HaploSNP_Sampler.py:431-442), fused epilogue
 //   finalize_kernel   A5/A6 log-posterior, MAP tracking, traces (HaploSNP_Sampler.py:349-358)
-//   mt_fill_kernel    GSL-compatible MT19937 stream for the tau draws (c_sample_tau.c:174)
+//   mt_fill_wide_kernel  GSL-compatible MT19937 stream for the tau draws (c_sample_tau.c:174)
 //
 // HBM layout: counts int32 in two layouts ([V][S][4] lane=sample for the tau
 // sweep, [S][V][4] lane=variant for the per-read pass), tau packed 2 bits per
@@ -121,56 +121,8 @@ __device__ __forceinline__ uint32_t mt_temper(uint32_t y)
     return y;
 }
 
-// The state is double-buffered in LDS (old block / new block), so a phase has no read-after-write
-// hazard inside itself and needs ONE barrier (3 per 624 words instead of 6); the tempered output of
-// a word is stored by the lane that just produced it (no separate output pass).
-__global__ __launch_bounds__(256) void mt_fill_kernel(uint32_t *__restrict__ state, uint32_t *__restrict__ out,
-                                                      size_t n)
-{
-    __shared__ uint32_t buf[2][624];
-    const int tid = threadIdx.x;
-    int cur = 0;
-    for (int i = tid; i < 624; i += 256) buf[0][i] = state[i];
-    int pos = (int)state[624];
-    __syncthreads();
-    size_t done = 0;
-    // words still unread in the resident block
-    if (pos < 624) {
-        const size_t take = (n < (size_t)(624 - pos)) ? n : (size_t)(624 - pos);
-        for (int i = tid; i < (int)take; i += 256) out[i] = mt_temper(buf[0][pos + i]);
-        pos += (int)take;
-        done = take;
-    }
-    while (done < n) {
-        const uint32_t *o = buf[cur];
-        uint32_t *w = buf[cur ^ 1];
-        const size_t left = n - done;
-        const int lo[3] = {0, 227, 454}, hi[3] = {227, 454, 624};
-#pragma unroll
-        for (int ph = 0; ph < 3; ++ph) {
-            const int i = lo[ph] + tid;
-            if (i < hi[ph]) {
-                // word i+1 = 624 is the new block's word 0; words i+397 >= 624 are new words i-227
-                const uint32_t nxt = (i + 1 < 624) ? o[i + 1] : w[0];
-                const uint32_t far = (i + 397 < 624) ? o[i + 397] : w[i - 227];
-                const uint32_t y = (o[i] & 0x80000000u) | (nxt & 0x7fffffffu);
-                const uint32_t val = far ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-                w[i] = val;
-                if ((size_t)i < left) out[done + i] = mt_temper(val);
-            }
-            __syncthreads();
-        }
-        cur ^= 1;
-        const size_t take = (left < 624) ? left : 624;
-        pos = (int)take;
-        done += take;
-    }
-    for (int i = tid; i < 624; i += 256) state[i] = buf[cur][i];
-    if (tid == 0) state[624] = (uint32_t)pos;
-}
-
 // ---------------------------------------------------------------------
-// The same stream, 4x wider per step.  MT19937's recurrence is  P x = 0  with  P = t^624 + t^397 + Q,  where t shifts
+// The generator: up to 4 x 227 words per barrier.  MT19937's recurrence is  P x = 0  with  P = t^624 + t^397 + Q,  where t shifts
 // the word sequence by one and  (Q x)[n] = A (U x[n] | L x[n+1])  is the "twist" (upper bit of one word, lower 31 of
 // the next, times the companion matrix A).  All three terms are GF(2)-linear and t commutes with Q, so the
 // cross terms of P^2 cancel:  P^(2^k) = t^(624 K) + t^(397 K) + Q^K  with K = 2^k, i.e.
@@ -867,7 +819,7 @@ struct TauParams {
     int *nchange;
     uint32_t *step_cnt;                // [gridDim.x][2] this launch's wavefront-steps: run / left to the fp64 code (~0: not screened)
     const uint32_t *screen_ctl;        // [0] != 0: the screening pass is suspended (finalize_body)
-    int screen;                        // fp32 screening pass allowed (DESMAN_HIP_TAU_NO_SCREEN switches it off for A/B runs)
+    int screen;                        // fp32 screening pass allowed (dsm_ctx_set_tau_screen(0) switches it off)
     int nt_skip;                       // experiment (DESMAN_HIP_NT_SKIP_TOTALS): a rare haplotype's step the difference screen left open goes to fp64 without the totals screen
     int V, S, G;
     int v_off;                // first position of this shard in the whole table (counter-based uniforms are keyed by global indices)
@@ -1323,35 +1275,31 @@ int k_mt_fill(dsm_ctx *c, uint32_t *out, size_t n, hipStream_t stream)
 {
     if (n == 0) return DSM_OK;
     KTimer tm(c, DSM_K_MT, stream);
-    static const bool plain = DSM_AB_ENV("DESMAN_HIP_MT_PLAIN") != nullptr;        // A/B switch: the 227-words-per-step kernel
-    if (plain) hipLaunchKernelGGL(mt_fill_kernel, dim3(1), dim3(256), 0, stream, c->mt_state, out, n);
-    else {
-        // The generator is one workgroup that runs next to the main stream's kernels.  It asks for (nearly) all of a CU's
-        // LDS, which it does not use, so that no other workgroup is placed on its CU: a workgroup sharing a CU with these
-        // 16 high-priority wavefronts runs 2-3x longer and becomes the tail of its launch (stage 1 of the mu/E pass, whose
-        // wavefronts all get the same number of tasks: 73 -> 57 us; DESMAN_HIP_MT_HOG=0 switches the reservation off).
-        static const int hog = DSM_AB_ENV("DESMAN_HIP_MT_HOG") ? atoi(DSM_AB_ENV("DESMAN_HIP_MT_HOG")) : 140;   // KB
-        if (hog && !c->mt_attr_set) {                                  // per device, hence per context
-            HIP_TRY(hipFuncSetAttribute((const void *)mt_fill_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, hog * 1024));
-            c->mt_attr_set = true;
-        }
-        // long fills (chunks of sweeps of a large table): from several CUs (mt_fill_parallel above); what is left, if anything, serially
-        static const bool no_par = DSM_AB_ENV("DESMAN_HIP_MT_SERIAL") != nullptr;        // A/B switch
-        static const size_t par_min = DSM_AB_ENV("DESMAN_HIP_MT_PAR_MIN") ? (size_t)atoi(DSM_AB_ENV("DESMAN_HIP_MT_PAR_MIN")) : 6;   // A/B switch, in chunks of D words (config 3, 80 000 words per sweep, never gets there: its generator hides behind the iteration, and five CUs taken at once cost it 0.103 -> 0.106-0.112 ms per iteration)
-        if (!g_batch.K && !no_par && n >= par_min * MTJ_D) {
-            size_t made = 0;
-            { const int r = mt_fill_parallel(c, out, n, stream, &made); if (r != DSM_OK) return r; }
-            out += made; n -= made;
-            if (n == 0) return DSM_OK;
-        }
-        if (g_batch.K) {
-            static thread_local BatchArgs<MtArgs> acc;
-            acc.p[g_batch.k] = MtArgs{c->mt_state, out, n};
-            if (g_batch.k == g_batch.K - 1)          // no CU reservation here: small tables, K generators
-                hipLaunchKernelGGL(mt_fill_wide_kernel_b, dim3(g_batch.K), dim3(1024), 0, stream, acc);
-        } else
-            hipLaunchKernelGGL(mt_fill_wide_kernel, dim3(1), dim3(1024), (size_t)hog * 1024, stream, c->mt_state, out, n);
+    // The generator is one workgroup that runs next to the main stream's kernels.  It asks for (nearly) all of a CU's LDS (140 KB),
+    // which it does not use, so that no other workgroup is placed on its CU: a workgroup sharing a CU with these 16 high-priority
+    // wavefronts runs 2-3x longer and becomes the tail of its launch (stage 1 of the mu/E pass, whose wavefronts all get the same
+    // number of tasks: 73 -> 57 us).
+    const size_t hog = (size_t)140 * 1024;
+    if (!c->mt_attr_set) {                                  // per device, hence per context
+        HIP_TRY(hipFuncSetAttribute((const void *)mt_fill_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hog));
+        c->mt_attr_set = true;
     }
+    // long fills (chunks of sweeps of a large table, from 6 D words on): from several CUs (mt_fill_parallel above); what is left, if
+    // anything, serially.  (Config 3, 80 000 words per sweep, never gets there: its generator hides behind the iteration, and five CUs
+    // taken at once cost it 0.103 -> 0.106-0.112 ms per iteration.)
+    if (!g_batch.K && n >= 6 * MTJ_D) {
+        size_t made = 0;
+        { const int r = mt_fill_parallel(c, out, n, stream, &made); if (r != DSM_OK) return r; }
+        out += made; n -= made;
+        if (n == 0) return DSM_OK;
+    }
+    if (g_batch.K) {
+        static thread_local BatchArgs<MtArgs> acc;
+        acc.p[g_batch.k] = MtArgs{c->mt_state, out, n};
+        if (g_batch.k == g_batch.K - 1)          // no CU reservation here: small tables, K generators
+            hipLaunchKernelGGL(mt_fill_wide_kernel_b, dim3(g_batch.K), dim3(1024), 0, stream, acc);
+    } else
+        hipLaunchKernelGGL(mt_fill_wide_kernel, dim3(1), dim3(1024), hog, stream, c->mt_state, out, n);
     HIP_TRY(hipGetLastError());
     return DSM_OK;
 }
@@ -1479,7 +1427,7 @@ int k_dirichlet(dsm_ctx *c, uint32_t iter, double *gamma_out, double *gamma_trac
         // stage 2 splits the subset counts with the gamma the mu/E pass used = the resident one; gamma_out may be the same
         // buffer: workgroup s stages row s in LDS before it writes the new row s, and no other workgroup reads that row
         s2.ntab = c->ntab; s2.rep = c->ntab_rep; s2.ld = c->ntab_ld; s2.gamma = c->gamma; s2.sum_mu = c->sum_mu; s2.log_tab = c->log_tab;
-        s2.S = c->S; s2.G = c->G; s2.k0 = k0; s2.k1 = k1; s2.iter = iter; s2.hmul = stats_ntab_hmul(); s2.swz = stats_ntab_swz();
+        s2.S = c->S; s2.G = c->G; s2.k0 = k0; s2.k1 = k1; s2.iter = iter; s2.hmul = DSM_NTAB_HMUL; s2.swz = DSM_NTAB_SWZ;
         s2.big_count = c->big_count;
     }
     DirParams q;
@@ -1658,8 +1606,7 @@ int k_tau_sweep(dsm_ctx *c, int mode, const double *gamma, const double *eta_swe
     p.gamma = gamma; p.eta_sweep = eta_sweep; p.eta_ll = eta_ll;
     p.u_raw = (c->tau_rng == DSM_RNG_MT19937 && (mode & 1)) ? u_raw : nullptr;
     p.logp = d_logp; p.ll_partial = c->ll_partial + (size_t)slot * DSM_MAX_GRID; p.nchange = c->nchange + slot; p.log_tab = c->log_tab;
-    static const bool no_screen = DSM_AB_ENV("DESMAN_HIP_TAU_NO_SCREEN") != nullptr;
-    p.screen = (no_screen || !c->tau_screen) ? 0 : 1;
+    p.screen = c->tau_screen ? 1 : 0;
     { static const bool nts = DSM_AB_ENV("DESMAN_HIP_NT_SKIP_TOTALS") != nullptr; p.nt_skip = nts ? 1 : 0; }
     p.step_cnt = c->step_cnt + (size_t)slot * 2 * DSM_MAX_GRID; p.screen_ctl = c->screen_ctl + slot;
     p.order = (c->blk_order && c->blk_order_n[slot] == grid) ? c->blk_order + (size_t)slot * DSM_MAX_GRID : nullptr;

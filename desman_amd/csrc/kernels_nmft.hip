@@ -437,201 +437,6 @@ __global__ __launch_bounds__(256) void nmft_pass_b_kernel(const double *__restri
     }
 }
 
-// ---------------------------------------------------------------------------
-// nmft_wave_kernel: one update in ONE pass over F, without workgroup barriers in the loop.
-// A wavefront owns a variant (its 4 rows of F and tau); lanes = samples (NSL per lane).
-//   1  R = tau.gamma_raw per lane (tau rows read as LDS broadcasts), Q' = F (/) R
-//   2  num[r][g] = sum_s Q'[r][s] gamma_raw[g][s]: 4 x 8 per-lane products per g-chunk, summed over
-//      the wavefront by a transposing butterfly that leaves ONE (r,g) total per lane
-//   3  that lane updates tau[r][g] (:171-172); the four bases of a (v,g) sit in one quad, so the
-//      renormalisation (:174-181) is two DPP exchanges; _adjustment (:88-91); tau -> HBM and LDS
-//   4  R2 = tau_new.gamma, objective terms (:152-156), Q = F (/) R2
-//   5  gamma numerators of the NEXT iteration accumulate in per-lane registers: num[g] += tau_new[r][g] Q[r]
-// do_update = 0 runs 4-5 only (statistics of the current state: the first iteration, div_objective).
-// gamma_raw / gamma: the running update's normalised gamma before / after _adjustment.
-// Partials are written transposed, [G*S numerators][G H1][1 objective] x workgroups.
-// ---------------------------------------------------------------------------
-template <int NSL, int GMAX>
-__global__ __launch_bounds__(256) void nmft_wave_kernel(const double *__restrict__ F, double *__restrict__ tau,
-                                                        const double *__restrict__ gam_raw,
-                                                        const double *__restrict__ gam, int V, int S, int G,
-                                                        int adjust, int do_update, const double *__restrict__ ctl,
-                                                        const double *__restrict__ log_tab, double *__restrict__ partial)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem_w[];
-    if (ctl[2] != 0.0) return;
-    constexpr int SPAD = 64 * NSL;
-    constexpr int GCH = GMAX < 8 ? GMAX : 8;             // haplotypes per reduction chunk
-    constexpr int NV = 4 * GCH;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int nblk = gridDim.x;
-    double2 *ltab = reinterpret_cast<double2 *>(smem_w);                       // [256]
-    double *gr = reinterpret_cast<double *>(smem_w) + 2 * DSM_LOG_TAB_N;        // [GMAX][SPAD] gamma_raw
-    double *gs = gr + GMAX * SPAD;                                              // [GMAX][SPAD] gamma
-    double *t1 = gs + GMAX * SPAD;                                              // [GMAX] rowsum(gamma_raw)
-    double *told = t1 + GMAX + wv * (8 * GMAX);                                 // per wavefront [4][GMAX]
-    double *tnew = told + 4 * GMAX;                                             // per wavefront [4][GMAX]
-    double *red = t1 + GMAX + 4 * (8 * GMAX);                                   // [4][GMAX + 2][SPAD]
-    if (tid < DSM_LOG_TAB_N) ltab[tid] = reinterpret_cast<const double2 *>(log_tab)[tid];
-    for (int i = tid; i < GMAX * SPAD; i += 256) {
-        const int g = i / SPAD, s = i % SPAD;
-        const bool in = g < G && s < S;
-        gr[i] = in ? gam_raw[(size_t)g * S + s] : 0.0;
-        gs[i] = in ? gam[(size_t)g * S + s] : 0.0;
-    }
-    __syncthreads();
-    if (tid < GMAX) {
-        double a = 0.0;
-        for (int s = 0; s < S; ++s) a += gr[tid * SPAD + s];     // gamma.sum(1)  (:170)
-        t1[tid] = a;
-    }
-    __syncthreads();
-
-    double num[NSL][GMAX];
-#pragma unroll
-    for (int j = 0; j < NSL; ++j)
-#pragma unroll
-        for (int g = 0; g < GMAX; ++g) num[j][g] = 0.0;
-    double obj = 0.0, h1 = 0.0;
-    const int myidx = transpose_index<NV>(lane);         // (r, gg) this lane owns after the reduction
-    const int my_r = myidx / GCH, my_gg = myidx % GCH;
-
-    // software prefetch: the F rows and the tau rows of the wavefront's NEXT variant are requested
-    // while the current one is processed (a wavefront handles only a handful of variants, so the
-    // load latency would otherwise be exposed once per variant)
-    double f_nx[NSL][4];
-    double t_nx[(4 * GMAX + 63) / 64];
-    auto prefetch = [&](int v) {
-#pragma unroll
-        for (int j = 0; j < NSL; ++j) {
-            const int s = lane + 64 * j;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) f_nx[j][r] = (v < V && s < S) ? F[((size_t)v * 4 + r) * S + s] : 1.0;
-        }
-#pragma unroll
-        for (int k = 0; k < (4 * GMAX + 63) / 64; ++k) {
-            const int i = lane + 64 * k, r = i / GMAX, g = i % GMAX;
-            t_nx[k] = (v < V && i < 4 * GMAX && g < G) ? tau[((size_t)v * 4 + r) * G + g] : 0.0;
-        }
-    };
-    prefetch(blockIdx.x * 4 + wv);
-    for (int v = blockIdx.x * 4 + wv; v < V; v += nblk * 4) {
-        // tau rows of the variant -> this wavefront's LDS scratch (uniform reads afterwards)
-#pragma unroll
-        for (int k = 0; k < (4 * GMAX + 63) / 64; ++k) {
-            const int i = lane + 64 * k;
-            if (i < 4 * GMAX) { told[i] = t_nx[k]; if (!do_update) tnew[i] = t_nx[k]; }
-        }
-        double f[NSL][4];
-        bool live[NSL];
-#pragma unroll
-        for (int j = 0; j < NSL; ++j) {
-            live[j] = lane + 64 * j < S;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) f[j][r] = f_nx[j][r];
-        }
-        prefetch(v + nblk * 4);
-        if (do_update) {
-            double q[NSL][4];
-#pragma unroll
-            for (int j = 0; j < NSL; ++j) {
-                double R[4] = {0.0, 0.0, 0.0, 0.0};
-                for (int g = 0; g < G; ++g) {
-                    const double gm = gr[g * SPAD + lane + 64 * j];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) R[r] = fma(told[r * GMAX + g], gm, R[r]);
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) q[j][r] = live[j] ? nzd(f[j][r]) / nzd(R[r]) : 0.0;
-            }
-            for (int g0 = 0; g0 < G; g0 += GCH) {
-                double val[NV];
-#pragma unroll
-                for (int gg = 0; gg < GCH; ++gg) {
-                    double a[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                    for (int j = 0; j < NSL; ++j) {
-                        const double gm = gr[(g0 + gg) * SPAD + lane + 64 * j];   // rows >= G are zero
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) a[r] = fma(q[j][r], gm, a[r]);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) val[r * GCH + gg] = a[r];
-                }
-                const double tot_rg = wave_transpose_reduce<NV>(val);             // num[my_r][g0 + my_gg]
-                const int g = g0 + my_gg;
-                const bool ok = g < G;
-                double tn = 0.0;
-                if (ok) tn = told[my_r * GMAX + g] * (nzd(tot_rg) / nzd(t1[g]));  // :171-172
-                // the four bases of (v,g) live in one quad: sum over a in the reference's order
-                const double t_a0 = dpp_mov<0x00>(tn), t_a1 = dpp_mov<0xAA>(tn);  // lanes with (b0,b1) = (0,0) / (0,1) -> r = 0 / 1
-                const double t_a2 = dpp_mov<0x55>(tn), t_a3 = dpp_mov<0xFF>(tn);  //                    (1,0) / (1,1) -> r = 2 / 3
-                const double tot = ((t_a0 + t_a1) + t_a2) + t_a3;                 // :176-178
-                if (ok) {
-                    double x = tn / tot;                                          // :180-181
-                    if (adjust && x < DSM_EPS) x = DSM_EPS;                       // :88-91
-                    if (lane < 32) tau[((size_t)v * 4 + my_r) * G + g] = x;
-                    tnew[my_r * GMAX + g] = x;
-                }
-            }
-        }
-        // statistics of the (new) state for the next iteration
-        h1 += (lane < 4 * GMAX) ? tnew[lane] : 0.0;          // GMAX <= 16: one (r,g) column per lane
-#pragma unroll
-        for (int j = 0; j < NSL; ++j) {
-            double R[4] = {0.0, 0.0, 0.0, 0.0};
-            for (int g = 0; g < G; ++g) {
-                const double gm = gs[g * SPAD + lane + 64 * j];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) R[r] = fma(tnew[r * GMAX + g], gm, R[r]);
-            }
-            double q2[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const double pa = R[r] < DSM_EPS ? DSM_EPS : R[r];
-                const double ratio = nzd(f[j][r]) / pa;
-                q2[r] = live[j] ? ((R[r] < DSM_EPS) ? nzd(f[j][r]) / nzd(R[r]) : ratio) : 0.0;
-                if (live[j]) obj += f[j][r] * dsm_log(ratio, ltab) - f[j][r] + pa;
-            }
-#pragma unroll
-            for (int g = 0; g < GMAX; ++g) {
-                if (g < G) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) num[j][g] = fma(tnew[r * GMAX + g], q2[r], num[j][g]);
-                }
-            }
-        }
-    }
-    // workgroup reduction over the 4 wavefronts (fixed order) -> transposed partials
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NSL; ++j)
-#pragma unroll
-        for (int g = 0; g < GMAX; ++g) red[((size_t)wv * (GMAX + 2) + g) * SPAD + lane + 64 * j] = num[j][g];
-    red[((size_t)wv * (GMAX + 2) + GMAX) * SPAD + lane] = obj;
-    // H1: lane i holds the (r = i / GMAX, g = i % GMAX) column sums
-    red[((size_t)wv * (GMAX + 2) + GMAX + 1) * SPAD + lane] = (lane < 4 * GMAX) ? h1 : 0.0;
-    __syncthreads();
-    for (int i = tid; i < G * S; i += 256) {
-        const int g = i / S, s = i % S;
-        double a = 0.0;
-        for (int k = 0; k < 4; ++k) a += red[((size_t)k * (GMAX + 2) + g) * SPAD + s];
-        partial[(size_t)i * nblk + blockIdx.x] = a;
-    }
-    if (tid < G) {
-        double a = 0.0;
-        for (int k = 0; k < 4; ++k)
-            for (int r = 0; r < 4; ++r) a += red[((size_t)k * (GMAX + 2) + GMAX + 1) * SPAD + r * GMAX + tid];
-        partial[((size_t)G * S + tid) * nblk + blockIdx.x] = a;
-    }
-    if (tid == 64) {
-        double a = 0.0;
-        for (int k = 0; k < 4; ++k)
-            for (int l = 0; l < 64; ++l) a += red[((size_t)k * (GMAX + 2) + GMAX) * SPAD + l];
-        partial[((size_t)G * S + G) * nblk + blockIdx.x] = a;
-    }
-}
-
 // get_tau (Init_NMFT.py:230-245): strict '>' against a running max from 0.0
 __global__ void nmft_get_tau_kernel(const double *__restrict__ tau, int V, int G, uint64_t *__restrict__ packed)
 {
@@ -767,8 +572,6 @@ int k_nmft_reduce(dsm_ctx *c)
 bool nmft_gstep_applies(const dsm_ctx *c, int fix_gamma)
 {
     if (fix_gamma || !nmft_use_mfma(c) || !c->ngam2 || !c->ngam_raw2) return false;
-    static const bool off = DSM_AB_ENV("DESMAN_HIP_NMFT_NO_GSTEP") != nullptr;     // A/B switch
-    if (off) return false;
     return c->nmft_fused < 0 ? nmft_mfma_grid(c, false) > 128 : c->nmft_fused == 3;
 }
 
@@ -789,55 +592,19 @@ int k_nmft_pass_b(dsm_ctx *c, int adjust)
     return DSM_OK;
 }
 
-// which (NSL, GMAX) the one-pass wavefront kernel is compiled for (per-lane accumulators NSL*GMAX <= 32)
-static bool wave_shape(const dsm_ctx *c, int *nsl, int *gmax)
-{
-    const int need = (c->S + 63) / 64;
-    *nsl = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 8;
-    *gmax = c->nG <= 4 ? 4 : c->nG <= 8 ? 8 : c->nG <= 16 ? 16 : 32;
-    return need <= 8 && (*nsl) * (*gmax) <= 32 && (*gmax) <= 16;
-}
-
 bool nmft_use_mfma(const dsm_ctx *c);
 bool nmft_use_wide(const dsm_ctx *c);
-bool nmft_use_wave(const dsm_ctx *c) { int a, b; return wave_shape(c, &a, &b) || nmft_use_mfma(c) || nmft_use_wide(c); }      // the one-pass kernels
-
-int nmft_wave_grid(const dsm_ctx *c)
-{
-    int g = (c->V + 3) / 4;
-    if (g > 768) g = 768;                     // ~3 wavefronts per SIMD (the kernel's register occupancy)
-    return g < 1 ? 1 : g;
-}
-
-template <int NSL, int GMAX>
-static void launch_wave(dsm_ctx *c, int adjust, int do_update, int grid)
-{
-    const size_t sh = (2 * DSM_LOG_TAB_N + 2 * (size_t)GMAX * 64 * NSL + GMAX + 4 * 8 * GMAX +
-                       4 * (size_t)(GMAX + 2) * 64 * NSL) * sizeof(double);
-    hipLaunchKernelGGL((nmft_wave_kernel<NSL, GMAX>), dim3(grid), dim3(256), sh, c->stream, c->F, c->ntau, c->ngam_raw,
-                       c->ngam, c->V, c->S, c->nG, adjust, do_update, NMFT_CTL(c), c->log_tab, c->npart);
-}
+bool nmft_use_wave(const dsm_ctx *c) { return nmft_use_mfma(c) || nmft_use_wide(c); }      // the one-pass kernels
 
 // do_update = 1: tau half of the running update + statistics of the next; 0: statistics only
 int k_nmft_mfma(dsm_ctx *c, int adjust, int do_update);
-bool nmft_use_mfma(const dsm_ctx *c);
-
 int k_nmft_wide(dsm_ctx *c, int adjust, int do_update);
 int k_nmft_wave(dsm_ctx *c, int adjust, int do_update)
 {
     if (nmft_use_mfma(c)) return k_nmft_mfma(c, adjust, do_update);
     if (nmft_use_wide(c)) return k_nmft_wide(c, adjust, do_update);
-    KTimer tm(c, do_update ? DSM_K_NMFT_B : DSM_K_NMFT_A);
-    int nsl, gmax;
-    if (!wave_shape(c, &nsl, &gmax)) { dsm_set_error("nmft_wave: unsupported shape"); return DSM_ERR_UNSUPPORTED; }
-    const int grid = nmft_wave_grid(c);
-#define WCASE(N, GM) if (nsl == N && gmax == GM) launch_wave<N, GM>(c, adjust, do_update, grid)
-    WCASE(1, 4); WCASE(1, 8); WCASE(1, 16); WCASE(2, 4); WCASE(2, 8); WCASE(2, 16); WCASE(4, 4); WCASE(4, 8);
-    WCASE(8, 4);
-#undef WCASE
-    HIP_TRY(hipGetLastError());
-    c->npart_cols = grid;
-    return DSM_OK;
+    dsm_set_error("nmft: no one-pass kernel for this shape");
+    return DSM_ERR_UNSUPPORTED;
 }
 
 int k_nmft_get_tau(dsm_ctx *c, uint64_t *d_packed)
@@ -849,7 +616,7 @@ int k_nmft_get_tau(dsm_ctx *c, uint64_t *d_packed)
 }
 
 // ===========================================================================
-// nmft_mfma_kernel: the one-pass update of nmft_wave_kernel with its three dense contractions on the matrix cores
+// nmft_mfma_kernel: one update in ONE pass over F, with its three dense contractions on the matrix cores
 // (v_mfma_f64_16x16x4_f64; measured 2x the VALU form of the same contraction on gfx950: the VALU form is bound by
 // operand delivery -- one LDS broadcast per FMA -- not by the FMA rate; profiles/r02_mfma_f64_ab.txt).
 //
@@ -876,7 +643,7 @@ int k_nmft_get_tau(dsm_ctx *c, uint64_t *d_packed)
 // of scratch at 3 wavefronts per SIMD: 38 -> 35 us per update at V = 10k); five and six tiles run at 2 wavefronts per SIMD, where
 // 256 registers hold the F tiles again (236-254 VGPRs, no spills: 202 -> 184 us per update at 50k x 96 x 12, and 119 us once the
 // end-of-kernel reduction shared the loop's LDS -- see `red` below); seven and eight tiles re-read F (224-249 VGPRs).  Other
-// shapes run nmft_wave_kernel / the two-pass kernels.
+// shapes run nmft_split_kernel (128 < S <= 512) / the two-pass kernels.
 // ===========================================================================
 typedef double double4_t __attribute__((ext_vector_type(4)));
 #ifdef DSM_AB_SWITCHES           // phase clocks of the update kernel's quad loop (experiment build only; DESMAN_HIP_NMFT_STAMPS=1 prints them per launch)
@@ -1624,10 +1391,9 @@ static bool mfma_shape(const dsm_ctx *c, int *nt, int *kb)
 {
     *nt = (c->S + 15) / 16;
     *kb = (c->nG + 3) / 4;
-    static const bool off = DSM_AB_ENV("DESMAN_HIP_NMFT_NO_MFMA") != nullptr;      // A/B switch: the VALU one-pass kernel
-    // measured against the VALU one-pass kernel: 1.0-1.3x at (NT, KB) = (4, 2), 1.96x at (6, 3) [V = 50k, S = 96, G = 12:
-    // 211 vs 413 us per update]; at (8, 4) the 140 KB of LDS leave one workgroup per CU and the VALU kernel wins (449 vs 491 us)
-    return !off && *nt >= 1 && *nt <= 8 && *kb >= 1 && *kb <= 4;          // S <= 128, G <= 16
+    // measured against the VALU one-pass kernel it replaced (since removed): 1.0-1.3x at (NT, KB) = (4, 2), 1.96x at (6, 3) [V = 50k,
+    // S = 96, G = 12: 211 vs 413 us per update]
+    return *nt >= 1 && *nt <= 8 && *kb >= 1 && *kb <= 4;          // S <= 128, G <= 16
 }
 
 bool nmft_use_mfma(const dsm_ctx *c) { int a, b; return mfma_shape(c, &a, &b); }
@@ -1642,8 +1408,6 @@ int nmft_mfma_grid(const dsm_ctx *c, bool fix)
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus < 1) cus = 256;
     // (a context's partial table is laid out for the larger of the two grids: dsm_nmft_set asks with fix = true)
     int cap = (fix ? nmft_mfma_fix_wgs(nt, kb) : nmft_mfma_wgs(nt, kb)) * cus;
-    static const int wgs_env = DSM_AB_ENV("DESMAN_HIP_NMFT_WGS") ? atoi(DSM_AB_ENV("DESMAN_HIP_NMFT_WGS")) : 0;       // A/B switch: fewer resident workgroups per CU
-    if (wgs_env > 0 && wgs_env * cus < cap) cap = wgs_env * cus;
     if (g > cap) g = cap;
     return g < 1 ? 1 : g;
 }
@@ -1997,10 +1761,9 @@ __global__ __launch_bounds__(512, split_wgs(NT, KB, NCB)) void nmft_split_kernel
 // 30k x 80 x 10 with its padded tile -- one wavefront per quad stays the form there, profiles/r05_nmft_split_ab.txt.)
 static bool wide_shape(const dsm_ctx *c, int *nt, int *kb, int *ncb)
 {
-    static const bool off = DSM_AB_ENV("DESMAN_HIP_NMFT_NO_MFMA") != nullptr || DSM_AB_ENV("DESMAN_HIP_NMFT_NO_WIDE") != nullptr;
     const int tiles = (c->S + 15) / 16;
     *kb = (c->nG + 3) / 4;
-    if (off || tiles <= 8 || tiles > 32 || *kb < 1 || *kb > 4) return false;
+    if (tiles <= 8 || tiles > 32 || *kb < 1 || *kb > 4) return false;
     static const int shapes[5][2] = {{3, 4}, {4, 4}, {5, 4}, {6, 4}, {8, 4}};       // by capacity: 12, 16, 20, 24, 32 tiles
     for (int i = 0; i < 5; ++i)
         if (shapes[i][0] * shapes[i][1] >= tiles) {
@@ -2483,9 +2246,8 @@ static int launch_persist(dsm_ctx *c, const NmftPersistParams &q, int grid, size
 // tiles / K-blocks, dynamic LDS.
 static int nmft_persist_shape(const dsm_ctx *c, int fix_gamma, int *nt_out, int *kb_out, int *nwv_out, size_t *sh_out, int *cus_out)
 {
-    static const bool off = DSM_AB_ENV("DESMAN_HIP_NMFT_NO_PERSIST") != nullptr;
     int nt, kb;
-    if (off || c->nmft_persist == 0 || !mfma_shape(c, &nt, &kb) || nt > 6 || kb > 3 || c->timing) return 0;
+    if (c->nmft_persist == 0 || !mfma_shape(c, &nt, &kb) || nt > 6 || kb > 3 || c->timing) return 0;
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) return 0;
     const int G = c->nG, S = c->S, nquad = (c->V + 3) / 4, nblk = (nquad + 3) / 4;

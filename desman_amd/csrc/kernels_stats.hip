@@ -25,8 +25,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <atomic>
-#include <mutex>
 #include <vector>
 
 // ablation switches of DESMAN_HIP_STATS_DBG: only in the experiment build (dsm_host.h: DSM_AB_SWITCHES); the product kernel has none of the tests
@@ -67,11 +65,11 @@ struct StatsAggParams {
                                     // whole pass on deep data)
     size_t big_seg;
     double lean_cap;                // stage 1 hands an item whose rarer outcome has a mean above this to the compacted kernel
-    uint32_t swz;                   // ... + (s >> 4) * swz: the four 64 B lines of a subset's 64 samples sit in four different rows (stats_ntab_swz)
+    uint32_t swz;                   // ... + (s >> 4) * swz: the four 64 B lines of a subset's 64 samples sit in four different rows (dsm_host.h: DSM_NTAB_SWZ)
     uint32_t hmul;                  // the row of subset H is (H * hmul) mod 2^G (dsm_stage2.h: s2_row): an odd multiplier scatters the hot
                                     // subsets over the memory channels whatever the table's address
     int xcd;                        // 1: the table has a copy per XCD (rep = 8 k); a workgroup adds to a copy of ITS XCD (HW_REG_XCC_ID) with
-                                    // workgroup-scope atomics, which execute in that XCD's L2 instead of at the memory side
+                                    // workgroup-scope atomics, which execute in that XCD's L2 instead of at the memory side (the host passes 0)
     // spec 4 (pattern-aggregated stage 1): non-null -> only the REPRESENTATIVE positions (lowest position of each packed tau word:
     // pat_rep[word] & 0xFFFFFFFF) carry cells, with the counts of all positions of their word summed in pat_x [V][4][S]
     const unsigned long long *pat_rep;
@@ -88,10 +86,8 @@ __device__ __forceinline__ uint64_t wave_uniform_u64(uint64_t x)
 
 // LPV = lanes per variant: a wavefront works on 64 / LPV (variant, LPV-sample chunk) tasks at a time, so that tables of 16,
 // 32, 48 or 96 samples fill its lanes (lane = sample alone leaves 3/4 of a wavefront idle at S = 16 and 1/4 at S = 96).
-// SPEC: 2 or 3 (dsm_binom.h).  REGG: S <= LPV and G <= 8 -- a lane keeps its sample for the whole launch, so its G abundances
-// live in registers (no LDS tile of gamma: the 4 KB it took at config 3 now hold the log / exp tables of spec 3 at the same six
-// workgroups per CU) and the haplotype loop of a cell is scalar compares + one add per haplotype, no LDS read.
-template <int LPV, int SPEC, bool REGG, bool PAT = false>
+// SPEC: 2 or 3 (dsm_binom.h).  (gamma in registers instead of the LDS tile: measured slower, 54-57 vs 48-49 us at config 3, and removed)
+template <int LPV, int SPEC, bool PAT = false>
 __device__ __forceinline__ void stats_agg_body(const StatsAggParams &p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem_s[];
@@ -106,8 +102,8 @@ __device__ __forceinline__ void stats_agg_body(const StatsAggParams &p)
     const int S = p.S, G = p.G, V = p.V;
     const int NCH = (S + LPV - 1) / LPV, SP = NCH * LPV;
     double *tabs = reinterpret_cast<double *>(smem_s);                // [NTAB]
-    double *gT = tabs + NTAB;                                         // [G][SP] gamma transposed (not with REGG)
-    double *rcp = gT + (REGG ? 0 : (size_t)G * SP);                   // [256]  1/k
+    double *gT = tabs + NTAB;                                         // [G][SP] gamma transposed
+    double *rcp = gT + (size_t)G * SP;                                // [256]  1/k
     double *es = rcp + DSM_RCP_TAB_N;                                 // [16]   eta
     uint32_t *eacc = reinterpret_cast<uint32_t *>(es + 16);           // [16][256] lane-private Esum columns
     const double2 *ltab = reinterpret_cast<const double2 *>(tabs);
@@ -120,22 +116,15 @@ __device__ __forceinline__ void stats_agg_body(const StatsAggParams &p)
     const int nunit = PAT ? (int)__builtin_amdgcn_readfirstlane((int)*p.pat_n) : V;
     const int ntask = nunit * NCH;                                    // (variant, chunk of LPV samples)
     const int nslot = (ntask + NG - 1) / NG;                          // NG tasks per wavefront pass
-    if constexpr (!REGG) {
-        for (int i = tid; i < G * SP; i += 256) {
-            const int g = i / SP, s = i - g * SP;
-            gT[i] = (s < S) ? p.gamma[(size_t)s * G + g] : 0.0;
-        }
+    for (int i = tid; i < G * SP; i += 256) {
+        const int g = i / SP, s = i - g * SP;
+        gT[i] = (s < S) ? p.gamma[(size_t)s * G + g] : 0.0;
     }
     if constexpr (SPEC >= 3) { for (int i = tid; i < NTAB; i += 256) tabs[i] = p.log_tab[i]; }
     for (int k = tid; k < DSM_RCP_TAB_N; k += blockDim.x) rcp[k] = k ? 1.0 / (double)k : 0.0;
     if (tid < 16) es[tid] = p.eta[tid];
 #pragma unroll
     for (int i = 0; i < 16; ++i) eacc[i * 256 + tid] = 0u;
-    double gr[REGG ? 8 : 1];
-    if constexpr (REGG) {
-#pragma unroll
-        for (int g = 0; g < 8; ++g) gr[g] = (g < G && lig < S) ? p.gamma[(size_t)lig * G + g] : 0.0;
-    }
     __syncthreads();
 
     S1_CLK(1);
@@ -180,28 +169,14 @@ __device__ __forceinline__ void stats_agg_body(const StatsAggParams &p)
             const uint32_t tlo = __builtin_amdgcn_readlane((uint32_t)t, gi * LPV), thi = __builtin_amdgcn_readlane((uint32_t)(t >> 32), gi * LPV);
             const uint64_t tg = ((uint64_t)thi << 32) | tlo;
             if (NG == 1 || grp == gi) {
-                if constexpr (REGG) {
-#pragma unroll
-                    for (int g = 0; g < 8; ++g) {
-                        if (g < G) {
-                            const int a = (int)((tlo >> (2 * g)) & 3);
-                            const uint32_t bit = 1u << g;
-                            if (a == 0) { H0 |= bit; G0 = G0 + gr[g]; }
-                            else if (a == 1) { H1 |= bit; G1 = G1 + gr[g]; }
-                            else if (a == 2) { H2 |= bit; G2 = G2 + gr[g]; }
-                            else { H3 |= bit; G3 = G3 + gr[g]; }
-                        }
-                    }
-                } else {
-                    for (int g = 0; g < G; ++g) {
-                        const int a = (int)((tg >> (2 * g)) & 3);
-                        const double x = gcol[g * SP];
-                        const uint32_t bit = 1u << g;
-                        if (a == 0) { H0 |= bit; G0 = G0 + x; }
-                        else if (a == 1) { H1 |= bit; G1 = G1 + x; }
-                        else if (a == 2) { H2 |= bit; G2 = G2 + x; }
-                        else { H3 |= bit; G3 = G3 + x; }
-                    }
+                for (int g = 0; g < G; ++g) {
+                    const int a = (int)((tg >> (2 * g)) & 3);
+                    const double x = gcol[g * SP];
+                    const uint32_t bit = 1u << g;
+                    if (a == 0) { H0 |= bit; G0 = G0 + x; }
+                    else if (a == 1) { H1 |= bit; G1 = G1 + x; }
+                    else if (a == 2) { H2 |= bit; G2 = G2 + x; }
+                    else { H3 |= bit; G3 = G3 + x; }
                 }
             }
         }
@@ -266,10 +241,9 @@ __device__ __forceinline__ void stats_agg_body(const StatsAggParams &p)
                 } else hand |= (1u << b) | ((uint32_t)kind << (4 + 2 * b));
             }
         };
-        if constexpr (SPEC == 2 && !REGG) { item(0, xs[0]); item(1, xs[1]); item(2, xs[2]); item(3, xs[3]); }
+        if constexpr (SPEC == 2) { item(0, xs[0]); item(1, xs[1]); item(2, xs[2]); item(3, xs[3]); }
         else {
-            // (the table-exp variant and the gamma-in-registers experiment keep the rolled loop: four copies of their item do not fit
-            // the 80 registers of six wavefronts per SIMD)
+            // (the table-exp variant keeps the rolled loop: four copies of its item do not fit the 80 registers of six wavefronts per SIMD)
 #pragma unroll 1
             for (int b = 0; b < 4; ++b) item(b, (b == 0) ? xs[0] : (b == 1) ? xs[1] : (b == 2) ? xs[2] : xs[3]);
         }
@@ -346,10 +320,10 @@ __device__ __forceinline__ void stats_agg_body(const StatsAggParams &p)
 }
 
 // six wavefronts per SIMD (the persistent grid's six workgroups per CU): the register allocation must leave room for them
-template <int LPV, int SPEC, bool REGG>
-__global__ __launch_bounds__(256, 6) void stats_agg_kernel(StatsAggParams p) { stats_agg_body<LPV, SPEC, REGG>(p); }
+template <int LPV, int SPEC>
+__global__ __launch_bounds__(256, 6) void stats_agg_kernel(StatsAggParams p) { stats_agg_body<LPV, SPEC>(p); }
 template <int LPV>      // (five workgroups per CU: at six the 16- and 32-lane forms spill)
-__global__ __launch_bounds__(256, 5) void stats_pat_kernel(StatsAggParams p) { stats_agg_body<LPV, 2, false, true>(p); }
+__global__ __launch_bounds__(256, 5) void stats_pat_kernel(StatsAggParams p) { stats_agg_body<LPV, 2, true>(p); }
 
 // ---- spec 4: the two small passes ahead of stage 1 ------------------------------------------------------------------------
 // Cells (v, s) and (v', s) of positions with the same packed tau word have the same weights W_a = eta[a,b] Gamma_a for every
@@ -448,10 +422,10 @@ __global__ __launch_bounds__(256) void pat_agg_kernel(const int32_t *__restrict_
         if (c.w) atomicAdd(xr + 3 * (size_t)S, (uint32_t)c.w);
     }
 }
-template <int LPV, int SPEC, bool REGG>
-__global__ __launch_bounds__(256, 6) void stats_agg_kernel_b(BatchArgs<StatsAggParams> b) { stats_agg_body<LPV, SPEC, REGG>(b.p[blockIdx.y]); }
+template <int LPV, int SPEC>
+__global__ __launch_bounds__(256, 6) void stats_agg_kernel_b(BatchArgs<StatsAggParams> b) { stats_agg_body<LPV, SPEC>(b.p[blockIdx.y]); }
 template <int LPV>
-__global__ __launch_bounds__(256, 5) void stats_pat_kernel_b(BatchArgs<StatsAggParams> b) { stats_agg_body<LPV, 2, false, true>(b.p[blockIdx.y]); }
+__global__ __launch_bounds__(256, 5) void stats_pat_kernel_b(BatchArgs<StatsAggParams> b) { stats_agg_body<LPV, 2, true>(b.p[blockIdx.y]); }
 
 // ---------------------------------------------------------------------------------------------------
 // the deferred items (rarer outcome with a mean above 64: burn-in states, very deep data), one lane per item:
@@ -530,7 +504,7 @@ __device__ __forceinline__ void stats_big_body(const StatsAggParams &p)
 
 // the copies of Esum stage 1 adds to (stats_agg_body's last lines) -> Esum, copies zero again.  The Gibbs loop never launches this: the
 // eta rows of dirichlet_kernel do the same sum on their way in.  For the paths that read Esum otherwise (dsm_ctx_sample_stats,
-// dsm_ctx_debug_stage1, the exchange of a chain sharded by positions, the table-place probe).
+// dsm_ctx_debug_stage1, the exchange of a chain sharded by positions).
 __global__ __launch_bounds__(256) void esum_fold_kernel(unsigned long long *__restrict__ esum)
 {
     static_assert(DSM_ESUM_PARTS * 4 == 256, "one thread per (copy, group of four counters)");
@@ -674,12 +648,9 @@ int stats_spec(const dsm_ctx *c)
 // 472 us with one table, 300 with two; V = 20k, S = 32, G = 5 (64 lines) 0.127 ms per iteration with two copies, 0.094 with
 // sixteen.  So: one table while a counter takes <= 128 atomics (config 3: 117, config 5: 37); otherwise at least two copies
 // (V = 20k, S = 64, G = 8: 145 -> 88 us) and as many as bring lines x rep to 384 -- every copy is one more read per subset at
-// stage 2's root (64 copies: +20 us on the Dirichlet launch).  DESMAN_HIP_NTAB_LINES overrides the 384.
+// stage 2's root (64 copies: +20 us on the Dirichlet launch).
 int stats_ntab_rep(const dsm_ctx *c)
 {
-    static const double want = DSM_AB_ENV("DESMAN_HIP_NTAB_LINES") ? atof(DSM_AB_ENV("DESMAN_HIP_NTAB_LINES")) : 384.0;
-    static const int force = DSM_AB_ENV("DESMAN_HIP_NTAB_REP") ? atoi(DSM_AB_ENV("DESMAN_HIP_NTAB_REP")) : 0;      // A/B switch
-    if (force > 0) return force;
     // a chain sharded by positions: every rank must lay its table out alike (the tables are all-reduced element by element), so
     // the rule reads the WHOLE table's position count, never the shard's own (shards differ by one position: V = 21 845, G = 8 on
     // two ranks gave 10 922 -> one copy and 10 923 -> two).  More copies than a shard needs cost one read each at stage 2's root.
@@ -687,212 +658,43 @@ int stats_ntab_rep(const dsm_ctx *c)
     if (per <= 128.0) return 1;
     const double lines = (double)((((size_t)1 << c->G) * (size_t)c->S * 4 + 63) / 64);
     int rep = 2;
-    while (lines * rep < want && rep < 64 && (size_t)(2 * rep) * ((size_t)1 << c->G) * (size_t)c->S * 4 <= ((size_t)64 << 20)) rep *= 2;
+    while (lines * rep < 384.0 && rep < 64 && (size_t)(2 * rep) * ((size_t)1 << c->G) * (size_t)c->S * 4 <= ((size_t)64 << 20)) rep *= 2;
     return rep;
 }
 
-// a copy of the table per XCD (stats_agg_body: the atomics of stage 1 then execute in the XCD's L2) while 8 copies stay below 64 MB
-static bool stats_ntab_xcd(const dsm_ctx *c)
-{
-    // measured at config 3 (rocprofv3 kernel trace of the Gibbs loop): stage 1 47.9 -> 46.1 us, but the root of stage 2 then reads
-    // eight copies: Dirichlet launch 19.2 -> 22.7 us.  Off by default.
-    static const int env = DSM_AB_ENV("DESMAN_HIP_NTAB_XCD") ? atoi(DSM_AB_ENV("DESMAN_HIP_NTAB_XCD")) : 0;      // A/B switch
-    return env != 0 && (size_t)8 * ((size_t)1 << c->G) * (size_t)c->S * 4 <= ((size_t)64 << 20);
-}
-
-// Odd multiplier of the subset -> table row map.  Why: the subsets that take most of stage 1's atomics are the low-popcount ones, and
-// with the identity map their rows sit at addresses base + 256 H whose bits line up with the memory-channel hash: depending on where
-// hipMalloc put the 64 KB table, the memory-side atomics of stage 1 cost 2 us or 26 us at config 3 (stage 1 46 vs 72 us; found when
-// two more allocations ahead of it -- the persistent NMFT kernel's -- moved the table; base offsets scanned: fast at 256 B and
-// 32-60 KB into a 2 MB block, slow at 0, 4 KB, 64 KB ...).  Scattering the rows takes the pathology away (46-54 us at every offset
-// scanned).  DESMAN_HIP_NTAB_HMUL=1 is the identity (A/B switch).
-// Round 6: the sample's part of the row map.  A subset's 64 samples are one 256 B row = four 64 B lines, and a wavefront's add to it is one
-// instruction = four line-atomics that arrive at the memory side together.  With (s >> 4) * swz added to the row index the four lines of a
-// LOGICAL row sit in four different physical rows, i.e. 256 B blocks: the adds a hot subset takes are spread over four places of the table
-// instead of queueing at one.  Measured at config 3 (scripts/dbg/r06_swz_scan.py, profiles/r06_swz_scan.txt): stage 1 40.5 us at EVERY one
-// of eight table places and every odd swz tried (1, 3, 17, 85; also 64), against 45-47 us at the good places and 55-59 us at the bad ones
-// without it -- the place lottery of rounds 2-5 (44 vs 54-61 us for the same launch, hipMalloc's answer deciding; stats_place_ntab's eight
-// timed passes per table; a probe that kept a slow place in 2 of 6 processes) is gone, and the launch is 11 % faster than its best place
-// was.  Stage 2 reads the same map (dsm_stage2.h); integer sums: nothing but the time changes.  0 = off (the map of rounds 2-5: the
-// place is then measured as before).  DESMAN_HIP_NTAB_SWZ in the experiment build.
-uint32_t stats_ntab_swz()
-{
-    static const uint32_t k = DSM_AB_ENV("DESMAN_HIP_NTAB_SWZ") ? (uint32_t)strtoul(DSM_AB_ENV("DESMAN_HIP_NTAB_SWZ"), nullptr, 0) : DSM_NTAB_SWZ;
-    return k;
-}
-uint32_t stats_ntab_hmul()
-{
-    static const uint32_t k = DSM_AB_ENV("DESMAN_HIP_NTAB_HMUL") ? ((uint32_t)strtoul(DSM_AB_ENV("DESMAN_HIP_NTAB_HMUL"), nullptr, 0) | 1u) : 0x9E3779B1u;
-    return k;
-}
-
-// Row stride of the subset table.  With S a multiple of 64 the rows are whole 256 B blocks and where the hot rows fall relative to the
-// memory-channel interleave decides what stage 1's memory-side atomics cost: at config 3 (S = 64) 44 us or 54 us (69 at the worst) for the
-// same launch, switching with every 256 B the table's base moves and with the multiplier of the row map (scripts/dbg/ntab_off_scan.py);
-// S = 48 or 96 (rows of 192 / 384 B, which cut the interleave at a different place every row) show none of it.  Longer rows (320 / 384 B)
-// narrowed the spread without closing it, so DSM_NTAB_PAD is 0 and the table's START is measured instead (stats_place_ntab below);
-// DESMAN_HIP_NTAB_PAD adds words to such rows in the experiment build (A/B switch).
-int stats_ntab_ld(int S)
-{
-    static const int pad = DSM_AB_ENV("DESMAN_HIP_NTAB_PAD") ? atoi(DSM_AB_ENV("DESMAN_HIP_NTAB_PAD")) : DSM_NTAB_PAD;
-    return (S % 64 == 0) ? S + pad : S;
-}
-
-// Where the table starts.  What the memory-side atomics of stage 1 cost depends on how the rows that take most adds fall on the
-// memory channels, i.e. on the table's PHYSICAL address: at config 3 the same launch takes 44 us at one 256 B offset and 54-61 us at
-// the next (scripts/dbg/ntab_scan_inproc.py: stable to 0.3 us for a given place, the median place costs 53 us) -- and hipMalloc's
-// answer moves with every allocation made before it and with the box (round 2's 0.105 ms was a lucky place, the same build measured
-// 0.131 once two allocations preceded the table).  Neither an odd row multiplier, nor longer rows, nor two or four copies take the
-// spread away, so the place is MEASURED: the table is allocated with DSM_NTAB_PLACES x 256 B to spare and
-// stats_place_ntab() times stage 1 on the chain's own state at each place, once per table, and keeps the fastest.
-// DESMAN_HIP_NTAB_OFF=<bytes> fixes the place instead (experiments); DESMAN_HIP_NTAB_TUNE=0 keeps place 0.
-#define DSM_NTAB_PLACES 8
-// Round 5 (VERDICT r4 "weak" 12: 55 chains of a sweep each probed again, next to whatever else ran on the GPU): a table whose place has been
-// measured outlives its chain.  dsm_ctx_destroy hands it to this pool (stats_release_ntab) and the next chain of the same device and
-// table size takes it, place and all, without a probe -- a table's cost is a property of its PHYSICAL address, which it keeps.  Probes
-// themselves are serialised (g_ntab_probe_mu): never two of this process at a time.  The pool holds at most 32 tables (each <= 512 KB:
-// larger ones are never probed and never pooled); dsm_debug_ntab_probes() counts the probes of the process.
-struct NtabSlot { int device; size_t need; int ld, rep, xcd; uint32_t *raw, *base; size_t off; };
-static std::mutex g_ntab_mu, g_ntab_probe_mu;
-static std::vector<NtabSlot> g_ntab_pool;
-static std::atomic<int> g_ntab_probes{0};
-extern "C" int dsm_debug_ntab_probes(void) { return g_ntab_probes.load(); }
-// frees the pooled subset tables (dsm_release_device_caches)
-void stats_ntab_pool_release()
-{
-    std::lock_guard<std::mutex> lk(g_ntab_mu);
-    for (const NtabSlot &sl : g_ntab_pool) {
-        int cur = 0;
-        (void)hipGetDevice(&cur);
-        (void)hipSetDevice(sl.device);
-        (void)hipFree(sl.raw);
-        (void)hipSetDevice(cur);
-    }
-    g_ntab_pool.clear();
-}
+// The subset table's row map: row of (subset H, sample s) = (H DSM_NTAB_HMUL + (s >> 4) DSM_NTAB_SWZ) mod 2^G (dsm_host.h).  The odd
+// multiplier scatters the low-popcount subsets that take most of stage 1's atomics; the sample's part puts the four 64 B lines of a
+// subset's 64 samples into four different rows.  Together they make every place of the table cost the same: stage 1 40.5 us at config 3
+// at each of eight places, where the identity map had 45-47 us at the good ones and 55-59 at the bad (profiles/r06_swz_scan.txt).  So the
+// table is allocated and zeroed once per layout and freed with its chain; rows are S words.  A copy per XCD, padded rows, other row maps
+// and a place measured per table were tried and removed.
 void stats_release_ntab(dsm_ctx *c)
 {
-    if (!c->ntab_raw) return;
-    bool kept = false;
-    if (c->ntab_measured) {
-        // (whoever takes the table next clears it on ITS stream: nothing of this context's may still be queued on the table)
-        (void)hipStreamSynchronize(c->stream);
-        std::lock_guard<std::mutex> lk(g_ntab_mu);
-        if (g_ntab_pool.size() < 32) { g_ntab_pool.push_back(NtabSlot{c->device, c->ntab_len, c->ntab_ld, c->ntab_rep, c->ntab_xcd, c->ntab_raw, c->ntab_base, c->ntab_off}); kept = true; }
-    }
-    if (!kept) (void)hipFree(c->ntab_raw);
-    c->ntab_raw = nullptr; c->ntab = nullptr; c->ntab_base = nullptr; c->ntab_len = 0; c->ntab_placed = c->ntab_measured = false;
+    if (c->ntab_raw) (void)hipFree(c->ntab_raw);
+    c->ntab_raw = nullptr; c->ntab = nullptr; c->ntab_len = 0;
 }
 static int ensure_ntab(dsm_ctx *c)
 {
-    // (the layout the pass wants now; the context's fields keep the layout its CURRENT table was made for until that table is released)
-    int rep = stats_ntab_rep(c);
-    const int xcd = stats_ntab_xcd(c) ? 1 : 0;
-    if (xcd) rep = std::max(8, (rep + 7) / 8 * 8);
-    const int ld = stats_ntab_ld(c->S);
+    const int rep = stats_ntab_rep(c), ld = c->S;
     const size_t need = (size_t)rep * ((size_t)1 << c->G) * (size_t)ld;
-    if (c->ntab_raw && (c->ntab_len != need || c->ntab_ld != ld || c->ntab_rep != rep || c->ntab_xcd != xcd)) stats_release_ntab(c);
-    c->ntab_rep = rep; c->ntab_ld = ld; c->ntab_xcd = xcd;
-    static const bool scan = DSM_AB_ENV("DESMAN_HIP_NTAB_SCAN") != nullptr;          // experiments: the offset is re-read at every call
+    if (c->ntab && c->ntab_len == need && c->ntab_ld == ld && c->ntab_rep == rep) return DSM_OK;
+    stats_release_ntab(c);
+    c->ntab_rep = rep; c->ntab_ld = ld;
+    // test hook of the experiment build: DESMAN_HIP_NTAB_OFF=<bytes> starts the table that far (in 256 B steps) past its 4 KB-aligned base
     const char *eo = DSM_AB_ENV("DESMAN_HIP_NTAB_OFF");
-    const size_t off_env = eo ? ((size_t)strtoull(eo, nullptr, 0) & ~(size_t)255) : (size_t)-1;
-    if (c->ntab && c->ntab_len == need && (!scan || off_env == (size_t)-1 || off_env == c->ntab_off)) return DSM_OK;
-    if (c->ntab_raw) stats_release_ntab(c);
-    if (off_env == (size_t)-1) {                           // a table of this size whose place was measured by an earlier chain
-        std::lock_guard<std::mutex> lk(g_ntab_mu);
-        for (size_t i = 0; i < g_ntab_pool.size(); ++i)
-            // (the measured place belongs to the access pattern -- row stride, copies, per-XCD mode -- not to the word count alone)
-            if (g_ntab_pool[i].device == c->device && g_ntab_pool[i].need == need && g_ntab_pool[i].ld == c->ntab_ld &&
-                g_ntab_pool[i].rep == c->ntab_rep && g_ntab_pool[i].xcd == c->ntab_xcd) {
-                const NtabSlot sl = g_ntab_pool[i];
-                g_ntab_pool.erase(g_ntab_pool.begin() + (long)i);
-                c->ntab_raw = sl.raw; c->ntab_base = sl.base; c->ntab_off = sl.off; c->ntab = sl.base + sl.off / 4; c->ntab_len = need;
-                c->ntab_placed = c->ntab_measured = true;
-                break;
-            }
-    }
-    if (c->ntab_raw) {
-        HIP_TRY(hipMemsetAsync(c->ntab, 0, need * sizeof(uint32_t), c->stream));
-        return DSM_OK;
-    }
-    const size_t off = off_env != (size_t)-1 ? off_env : 0;
-    const size_t spare = std::max<size_t>(off, (size_t)DSM_NTAB_PLACES * 256) + 4096;
+    const size_t off = eo ? ((size_t)strtoull(eo, nullptr, 0) & ~(size_t)255) : 0;
+    const size_t spare = off + 4096;
     hipError_t e = hipMalloc((void **)&c->ntab_raw, need * sizeof(uint32_t) + spare);
     if (e != hipSuccess) { dsm_set_error("hipMalloc(%zu B) failed: %s", need * 4 + spare, hipGetErrorString(e)); return DSM_ERR_NOMEM; }
-    c->ntab_base = reinterpret_cast<uint32_t *>(((uintptr_t)c->ntab_raw + 4095) & ~(uintptr_t)4095);
-    c->ntab = c->ntab_base + off / 4;
-    c->ntab_off = off;
+    c->ntab = reinterpret_cast<uint32_t *>(((uintptr_t)c->ntab_raw + 4095) & ~(uintptr_t)4095) + off / 4;
     c->ntab_len = need;
-    c->ntab_placed = off_env != (size_t)-1;               // a place given from outside is not measured again
-    c->ntab_measured = false;
     HIP_TRY(hipMemsetAsync(c->ntab, 0, need * sizeof(uint32_t), c->stream));
     return DSM_OK;
 }
 
-int stats_place_ntab(dsm_ctx *c)
+int stats_ensure_ntab(dsm_ctx *c)
 {
-    static const bool on = !(getenv("DESMAN_HIP_NTAB_TUNE") && atoi(getenv("DESMAN_HIP_NTAB_TUNE")) == 0);
-    static const bool verbose = getenv("DESMAN_HIP_NTAB_TUNE") && atoi(getenv("DESMAN_HIP_NTAB_TUNE")) == 2;
-    if (stats_spec(c) < 2) return DSM_OK;
-    int r = ensure_ntab(c);
-    if (r != DSM_OK) return r;
-    if (c->ntab_placed) return DSM_OK;
-    c->ntab_placed = true;
-    if (stats_ntab_swz() != 0u) return DSM_OK;          // round 6: with the sample-swizzled row map every place costs the same (stats_ntab_swz): nothing to measure
-    // tables of a few hundred KB: larger ones spread over the channels whatever their place (config 5, 1.5 MB: 302 us everywhere)
-    if (!on || g_batch.K || c->ntab_len * sizeof(uint32_t) > ((size_t)512 << 10)) return DSM_OK;
-    std::lock_guard<std::mutex> probe_lk(g_ntab_probe_mu);
-    g_ntab_probes.fetch_add(1);
-    const bool timing = c->timing;
-    c->timing = false;
-    hipEvent_t ev[2];
-    HIP_TRY(hipEventCreate(&ev[0]));
-    HIP_TRY(hipEventCreate(&ev[1]));
-    auto clear = [&]() -> int {
-        HIP_TRY(hipMemsetAsync(c->ntab, 0, c->ntab_len * sizeof(uint32_t), c->stream));
-        HIP_TRY(hipMemsetAsync(c->esum, 0, (16 + 16 * DSM_ESUM_PARTS) * sizeof(unsigned long long), c->stream));
-        if (c->big_count) HIP_TRY(hipMemsetAsync(c->big_count, 0, DSM_BIG_NT * DSM_BIG_NL * DSM_BIG_STRIDE * sizeof(uint32_t), c->stream));
-        return DSM_OK;
-    };
-    float best = 0.f;
-    int best_k = 0;
-    for (int k = 0; k < DSM_NTAB_PLACES && r == DSM_OK; ++k) {
-        c->ntab = c->ntab_base + (size_t)k * 64;
-        // the draws are counter-based (the iteration index is an argument): running the pass here moves no stream.  Sums are cleared after.
-        r = clear();
-        if (r == DSM_OK) r = k_stats_stage1(c, 0xFFFFFF00u + (uint32_t)k);
-        if (r == DSM_OK) r = clear();
-        if (r != DSM_OK) break;
-        // Round 6: the stage-1 launch alone (the compacted kernel and the clears between the events added 10-90 us of work that does not
-        // depend on the place -- most on the burn-in state a chain is probed in -- to a difference of 9 us), the FASTEST of three launches
-        // per place (a launch is only ever slowed by what else runs): 2 of 6 processes had kept a slow place at config 3 (stage 1 52-55 us
-        // instead of 45-47, profiles/r06_stats_ab.txt)
-        float ms = 0.f;
-        for (int j = 0; j < 3 && r == DSM_OK; ++j) {
-            c->stats_probe = true;                                    // k_stats_stage1: no compacted launch behind the pass
-            (void)hipEventRecord(ev[0], c->stream);
-            r = k_stats_stage1(c, 0xFFFFFF80u + (uint32_t)k);
-            (void)hipEventRecord(ev[1], c->stream);
-            c->stats_probe = false;
-            if (r == DSM_OK) r = clear();
-            if (r != DSM_OK) break;
-            if (hipEventSynchronize(ev[1]) != hipSuccess) { r = DSM_ERR_HIP; dsm_set_error("stats_place_ntab: hipEventSynchronize failed"); break; }
-            float m1 = 0.f;
-            (void)hipEventElapsedTime(&m1, ev[0], ev[1]);
-            if (j == 0 || m1 < ms) ms = m1;
-        }
-        if (r != DSM_OK) break;
-        if (k == 0 || ms < best) { best = ms; best_k = k; }
-        if (verbose) fprintf(stderr, "desman_hip: subset table at +%d B: %.1f us per stage-1 launch\n", k * 256, 1000.0 * ms);
-    }
-    (void)hipEventDestroy(ev[0]);
-    (void)hipEventDestroy(ev[1]);
-    c->timing = timing;
-    c->ntab = c->ntab_base + (size_t)best_k * 64;
-    c->ntab_off = (size_t)best_k * 256;
-    if (r != DSM_OK) return r;
-    c->ntab_measured = true;
-    return clear();
+    return stats_spec(c) < 2 ? DSM_OK : ensure_ntab(c);
 }
 
 static int ensure_big_list(dsm_ctx *c, size_t seg)
@@ -950,44 +752,37 @@ int k_stats_stage1(dsm_ctx *c, uint32_t iter)
     const int spec_full = stats_spec(c);                  // 2, 3 or 4 (the caller checked that the aggregated pass applies)
     const bool pat = spec_full == 4;
     const int spec = stats_draw_version(spec_full);
-    static const int regg_env = DSM_AB_ENV("DESMAN_HIP_STATS_REGG") ? atoi(DSM_AB_ENV("DESMAN_HIP_STATS_REGG")) : -1;   // A/B switch
-    // (gamma in registers where a lane keeps its sample, instead of the LDS tile: measured slower -- 87-91 VGPRs, i.e. five
-    // wavefronts per SIMD, or spills at six: 54-57 us against 48-49; kept as an A/B switch)
-    const bool regg = NCH == 1 && G <= 8 && regg_env == 1 && !pat;
-    const size_t sh = ((regg ? 0 : (size_t)G * SP) + (spec >= 3 ? 2 * DSM_LOG_TAB_N + DSM_EXP_TAB_N : 0) + DSM_RCP_TAB_N + 16) * sizeof(double) +
+    const size_t sh = ((size_t)G * SP + (spec >= 3 ? 2 * DSM_LOG_TAB_N + DSM_EXP_TAB_N : 0) + DSM_RCP_TAB_N + 16) * sizeof(double) +
                       16 * 256 * sizeof(uint32_t);
     if (sh > 160 * 1024) { dsm_set_error("stats_agg: gamma tile (%zu B) exceeds LDS", sh); return DSM_ERR_UNSUPPORTED; }
     // the instantiation of this shape and specification: {single, batched}
     const void *fn = nullptr, *fn_b = nullptr;
-#define AGG_CASE(L, SP_, R)                                                                                               \
-    if (LPV == L && spec == SP_ && regg == R) { fn = (const void *)stats_agg_kernel<L, SP_, R>; fn_b = (const void *)stats_agg_kernel_b<L, SP_, R>; }
-    AGG_CASE(16, 2, false) AGG_CASE(16, 2, true) AGG_CASE(32, 2, false) AGG_CASE(32, 2, true) AGG_CASE(64, 2, false) AGG_CASE(64, 2, true)
-    AGG_CASE(16, 3, false) AGG_CASE(16, 3, true) AGG_CASE(32, 3, false) AGG_CASE(32, 3, true) AGG_CASE(64, 3, false) AGG_CASE(64, 3, true)
+#define AGG_CASE(L, SP_) if (LPV == L && spec == SP_) { fn = (const void *)stats_agg_kernel<L, SP_>; fn_b = (const void *)stats_agg_kernel_b<L, SP_>; }
+    AGG_CASE(16, 2) AGG_CASE(32, 2) AGG_CASE(64, 2) AGG_CASE(16, 3) AGG_CASE(32, 3) AGG_CASE(64, 3)
 #undef AGG_CASE
     if (pat) {
         fn = LPV == 16 ? (const void *)stats_pat_kernel<16> : LPV == 32 ? (const void *)stats_pat_kernel<32> : (const void *)stats_pat_kernel<64>;
         fn_b = LPV == 16 ? (const void *)stats_pat_kernel_b<16> : LPV == 32 ? (const void *)stats_pat_kernel_b<32> : (const void *)stats_pat_kernel_b<64>;
     }
     if (!fn) { dsm_set_error("stats_agg: no kernel for spec %d", spec); return DSM_ERR_UNSUPPORTED; }
-    if (c->stats_grid == 0 || c->stats_grid_key != (spec_full * 2 + (regg ? 1 : 0))) {
+    if (c->stats_grid == 0 || c->stats_grid_key != spec_full) {
         int occ = 0;
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 256, sh));
         hipDeviceProp_t prop;
         HIP_TRY(hipGetDeviceProperties(&prop, c->device));
-        static const int wgs_env = DSM_AB_ENV("DESMAN_HIP_STATS_WGS") ? atoi(DSM_AB_ENV("DESMAN_HIP_STATS_WGS")) : 6;   // A/B switch
+        const int wgs = std::min(6, std::max(1, occ));      // six workgroups per CU: measured optimum (below)
         // ... on all CUs but one per XCD when the sweep's uniforms are MT19937 words: the generator's workgroup keeps a CU to itself
         // (kernels_gibbs.hip: k_mt_fill) and workgroups go to the XCDs in turn whatever room they have, so a persistent grid sized for
         // every CU leaves six workgroups of that XCD waiting for others to finish -- a launch that starts while the generator runs took
         // 51 us instead of 46 (scripts/dbg/trace_stats_vs_mt.sh).  Leaving 8 CUs: 106.7 vs 107.5 us per iteration at config 3 (1 CU: no
         // change; 16 and more: slower).
-        static const int leave_env = DSM_AB_ENV("DESMAN_HIP_STATS_LEAVE_CUS") ? atoi(DSM_AB_ENV("DESMAN_HIP_STATS_LEAVE_CUS")) : -1;   // A/B switch
         const int n_xcd = prop.multiProcessorCount % 8 == 0 && prop.multiProcessorCount >= 64 ? 8 : 1;
         // (only while a wavefront makes a pass or two: over many passes the smaller grid is simply 3 % less machine -- config 5, twelve
         // passes: 384 vs 368 us)
-        const long passes4 = (((long)V * NCH + NG - 1) / NG) / std::max(1L, (long)std::min(wgs_env, std::max(1, occ)) * prop.multiProcessorCount);   // workgroup = 4 wavefronts: passes x 4
-        const int leave = leave_env >= 0 ? leave_env : ((c->tau_rng == DSM_RNG_MT19937 && passes4 <= 12) ? n_xcd : 0);
-        c->stats_grid = std::min(wgs_env, std::max(1, occ)) * std::max(1, prop.multiProcessorCount - leave);   // six workgroups per CU: measured optimum (below)
-        c->stats_grid_key = spec_full * 2 + (regg ? 1 : 0);
+        const long passes4 = (((long)V * NCH + NG - 1) / NG) / std::max(1L, (long)wgs * prop.multiProcessorCount);   // workgroup = 4 wavefronts: passes x 4
+        const int leave = (c->tau_rng == DSM_RNG_MT19937 && passes4 <= 12) ? n_xcd : 0;
+        c->stats_grid = wgs * std::max(1, prop.multiProcessorCount - leave);
+        c->stats_grid_key = spec_full;
     }
     const long ntask = ((long)V * NCH + NG - 1) / NG;            // wavefront passes (NG lane groups = NG tasks each)
     // a persistent grid of six workgroups (24 wavefronts) per CU, passes dealt round-robin: the kernel is issue-bound, and a SIMD
@@ -1008,8 +803,8 @@ int k_stats_stage1(dsm_ctx *c, uint32_t iter)
     p.v_off = c->shard_on ? c->shard_voff : 0; p.V_tot = c->shard_on ? c->shard_vtot : V;
     p.k0 = (uint32_t)c->ctr_seed; p.k1 = (uint32_t)(c->ctr_seed >> 32); p.iter = iter;
     p.ntab = c->ntab; p.rep = c->ntab_rep; p.ld = c->ntab_ld; p.esum = c->esum; p.log_tab = c->log_tab;
-    p.xcd = stats_ntab_xcd(c) ? 1 : 0;
-    p.hmul = stats_ntab_hmul(); p.swz = stats_ntab_swz();
+    p.xcd = 0;                                                   // (a copy of the table per XCD: measured slower, removed)
+    p.hmul = DSM_NTAB_HMUL; p.swz = DSM_NTAB_SWZ;
     p.big_list = c->big_list; p.big_count = c->big_count;
     p.pat_rep = nullptr; p.pat_x = nullptr; p.pat_list = nullptr; p.pat_n = nullptr;
     if (pat) {
@@ -1054,9 +849,9 @@ int k_stats_stage1(dsm_ctx *c, uint32_t iter)
         p.dbg = dbg;
         if (!(p.lean_cap > 0.0 && p.lean_cap <= DSM_BINV_MEAN_CAP)) p.lean_cap = DSM_LEAN_CAP;
     }
-    // (a batch: fewer workgroups per list, the launch holds K times as many lists)
-    static const int big_wgs_env = DSM_AB_ENV("DESMAN_HIP_BIG_WGS") ? atoi(DSM_AB_ENV("DESMAN_HIP_BIG_WGS")) : 0;     // A/B switch: workgroups per list
-    const int big_wgs = big_wgs_env > 0 ? big_wgs_env : 16;
+    // (a batch: fewer workgroups per list, the launch holds K times as many lists; fewer for a single chain measured no faster at config 3
+    // and slower at ten times the depth, profiles/r06_big_wgs.txt)
+    const int big_wgs = 16;
     const int big_grid = DSM_BIG_NT * DSM_BIG_NL *
         (int)std::max<long>(1, std::min<long>((ntask * 64 * 4 / DSM_BIG_NL + 255) / 256, g_batch.K ? std::max(2, big_wgs / g_batch.K) : big_wgs));
     if (g_batch.K) {
@@ -1078,8 +873,6 @@ int k_stats_stage1(dsm_ctx *c, uint32_t iter)
         void *args[] = {(void *)&p};
         HIP_TRY(hipLaunchKernel(fn, dim3(grid), dim3(256), args, sh, c->stream));
     }
-    if (c->stats_probe && !pat) return DSM_OK;           // (stats_place_ntab times the pass alone and clears the lists itself; over tau words the
-                                                         // compacted kernel is also what leaves a handed-over item's pooled count zero: it runs)
     KTimer tm(c, DSM_K_STATSBIG);
     // the deferred items (none once the chain has converged on data of ordinary depth: the launch then returns at once);
     // up to 16 workgroups per list = 4096 items of a list per round (a list one item longer than a round doubles the launch:
@@ -1122,7 +915,7 @@ int k_stats_stage2(dsm_ctx *c, uint32_t iter)
     KTimer tm(c, DSM_K_STATS2);
     Stage2Params p;
     p.ntab = c->ntab; p.rep = c->ntab_rep; p.ld = c->ntab_ld; p.gamma = c->gamma; p.sum_mu = c->sum_mu; p.log_tab = c->log_tab;
-    p.S = c->S; p.G = c->G; p.hmul = stats_ntab_hmul(); p.swz = stats_ntab_swz();
+    p.S = c->S; p.G = c->G; p.hmul = DSM_NTAB_HMUL; p.swz = DSM_NTAB_SWZ;
     p.k0 = (uint32_t)c->ctr_seed; p.k1 = (uint32_t)(c->ctr_seed >> 32); p.iter = iter;
     p.big_count = c->big_count;
     // 2^G subsets per sample at the root: 256 threads up to G = 9, 1024 above

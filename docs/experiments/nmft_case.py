@@ -3,7 +3,6 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 from desman_amd import _lib
-if os.environ.get('NM_OLD_LIB'): _lib.SIGNATURES.pop('dsm_debug_ntab_probes', None)      # (a library of an earlier round)
 from desman_amd.synth import synth_counts
 from oracle import cbind, ref_numpy as rn
 V, S, G, fix = [int(x) for x in sys.argv[1:5]]

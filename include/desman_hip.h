@@ -138,10 +138,6 @@ int dsm_ctx_sample_stats(dsm_ctx *ctx, uint32_t iter, uint64_t *sum_mu, uint64_t
  * unsharded chain under dsm_ctx_force_stats_spec(ctx, 2).  */
 int dsm_ctx_stats_spec(dsm_ctx *ctx);
 int dsm_ctx_force_stats_spec(dsm_ctx *ctx, int spec);
-/* how often this process has measured where a subset table should start.  Always 0 since round 6: the table's row map puts the four cache lines of
- * a subset's row into four rows, and every place costs the same; the measurement of rounds 3-5 (eight timed stage-1 passes per
- * new table, measured tables pooled per process) only runs in the experiment build with DESMAN_HIP_NTAB_SWZ=0.   */
-int dsm_debug_ntab_probes(void);
 /* test hooks of the aggregated sampler: stage 1 only (subset counts ntab [S][2^G] u32 and esum), and nsamp variates of one
  * sampler (kind 0 binom_small, 1 binom_big: out [nsamp]; 2 mult4 with weights w[0..3]: out [nsamp][4]) of version
  * spec (2 / 3) exactly as oracle/stats_agg.c: orc_binom_test / orc_mult4_test draw them.                          */
@@ -301,8 +297,7 @@ int dsm_ctx_sweep_stats(dsm_ctx *ctx, uint64_t *steps, uint64_t *exact_steps, in
 /* test hook: out[i] = the hardware log2 (v_log_f32) of in[i], the logarithm of the screening pass */
 int dsm_ctx_debug_log2f(dsm_ctx *ctx, const float *in, float *out, size_t n);
 /* Frees what the library keeps per process and device beyond the life of a context: the MT19937 jump tables of the parallel generator
-   (2 x 50 MB per device, built by the first fill of >= 6 x 131 040 words: 2 x 2.2 ms) and the pool of placed subset tables (at most 32 of
-   <= 512 KB).  For long-lived processes and for several rank processes sharing one GPU; nothing may be in flight.  Returns 0. */
+   (2 x 50 MB per device, built by the first fill of >= 6 x 131 040 words: 2 x 2.2 ms).  For long-lived processes and for several rank processes sharing one GPU; nothing may be in flight.  Returns 0. */
 int dsm_release_device_caches(void);
 /* test hook: out[i] = a[i] / b[i] as the NMFT update divides (kernels_nmft.hip): kind 0 = fdiv_ext (any a, b >= 0: operands brought to
    within 2^+-512 of one by exact powers of two), 1 = fdiv_lo (a in (0, 1]), 2 = fdiv (operands far from the ends of the exponent range).

@@ -12,7 +12,7 @@ timeout 400 python bench.py --full --V 50000 --S 96 --G 12 --steps 100 --warmup 
 cp gpurun_out/pmc_traffic_by_shape.json $O/pmc_traffic_by_shape.json
 # NMFT: wall time per update + MFMA / VALU counters of the persistent kernel and of the three-launch kernels
 python scripts/prof_nmft.py 10000 64 8 1000 > $O/r03_nmft.txt 2>&1
-DESMAN_HIP_NMFT_NO_PERSIST=1 python scripts/prof_nmft.py 10000 64 8 1000 >> $O/r03_nmft.txt 2>&1
+NMFT_PERSIST=0 python scripts/prof_nmft.py 10000 64 8 1000 >> $O/r03_nmft.txt 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_nmft -o p -- python scripts/prof_nmft.py 10000 64 8 200 > $O/pmc_nmft.log 2>&1
 python scripts/summarize_pmc.py $O/r03_nmft_pmc_V10k.csv $O/pmc_nmft
 python scripts/dbg/nmft_ab.py > $O/r03_nmft_ab.txt 2>&1

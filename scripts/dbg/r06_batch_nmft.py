@@ -1,5 +1,5 @@
 """round 6: the NMF start of a batch of small tables -- every chain its own persistent launch, as many at once as fit -- against the
-batched three-launch loop (DESMAN_HIP_NMFT_NO_PERSIST=1, experiment build) and against the chains one by one.  us per chain-update.  usage: r06_batch_nmft.py"""
+batched three-launch loop (dsm_batch_nmft_factorize: a batch never takes the persistent path) and against the chains one by one.  us per chain-update.  usage: r06_batch_nmft.py"""
 import os, sys, subprocess, time
 root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 lib = os.path.join(root, "desman_amd", "lib", "libdesman_hip_ab.so")

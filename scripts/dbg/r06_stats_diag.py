@@ -1,4 +1,4 @@
-"""round 6 diagnostics of stage 1 (experiment builds): ablations, workgroups per CU, table place fixed.  usage: r06_stats_diag.py lib.so [V S G]"""
+"""round 6 diagnostics of stage 1 (experiment builds): ablations, table place fixed.  usage: r06_stats_diag.py lib.so [V S G]"""
 import os, sys, subprocess
 root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 lib = os.path.abspath(sys.argv[1])
@@ -30,9 +30,7 @@ def run(**env):
 print("lib", os.path.basename(lib), (V, S, G), flush=True)
 for off in (0, 256, 512, 768, 1024, 1280):
     print("place +%d:" % off, run(DESMAN_HIP_NTAB_OFF=off), flush=True)
-print("default (measured place):", run(), flush=True)
+print("default (the allocator's place):", run(), flush=True)
 OFF = 256
 for dbg in (1, 2, 3, 8, 11, 20, 36, 52, 63):
     print("dbg %2d:" % dbg, run(DESMAN_HIP_STATS_DBG=dbg, DESMAN_HIP_NTAB_OFF=OFF), flush=True)
-for w in (3, 4, 5, 6, 7, 8):
-    print("wgs %d:" % w, run(DESMAN_HIP_STATS_WGS=w, DESMAN_HIP_NTAB_OFF=OFF), "leave0", run(DESMAN_HIP_STATS_WGS=w, DESMAN_HIP_NTAB_OFF=OFF, DESMAN_HIP_STATS_LEAVE_CUS=0), flush=True)

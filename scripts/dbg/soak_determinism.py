@@ -27,7 +27,7 @@ for n in (7, 500, 1, 993, 20, 1479):
 print(h.hexdigest(), tr["ll"][-1])
 ''' % root
 outs = []
-for env in ({}, {"DESMAN_HIP_NTAB_TUNE": "0", "DESMAN_HIP_TAU_ORDER": "0"}, {}):
+for env in ({}, {"DESMAN_HIP_TAU_ORDER": "0"}, {}):
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True)
     print(r.stdout.strip() or r.stderr[-500:]); outs.append(r.stdout.split()[0] if r.stdout else None)
 print("identical" if len(set(outs)) == 1 and outs[0] else "DIFFERENT")

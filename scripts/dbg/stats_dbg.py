@@ -19,8 +19,8 @@ for it in range(200): ctx.sample_stats(100 + it)
 tm = ctx.get_timing()
 print({k: round(1e3 * ms / max(n, 1), 1) for k, (ms, n) in tm.items() if n})
 ''' % root
-for spec, xcd in ((2, 1), (3, 1)):
+for spec in (2, 3):
     for dbg in (0, 1, 2, 8, 10, 16, 32, 48, 59):
-        env = dict(os.environ, DESMAN_HIP_STATS_DBG=str(dbg), DESMAN_HIP_STATS_REGG="0", DESMAN_HIP_NTAB_XCD=str(xcd))
+        env = dict(os.environ, DESMAN_HIP_STATS_DBG=str(dbg))
         r = subprocess.run([sys.executable, "-c", code, str(spec)], env=env, capture_output=True, text=True)
-        print("spec", spec, "xcd", xcd, "dbg", dbg, r.stdout.strip().splitlines()[-1] if r.stdout.strip() else r.stderr[-300:], flush=True)
+        print("spec", spec, "dbg", dbg, r.stdout.strip().splitlines()[-1] if r.stdout.strip() else r.stderr[-300:], flush=True)

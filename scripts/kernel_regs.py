@@ -12,7 +12,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
-pats = sys.argv[1:] or [r"^(void )?tau_kernel<(32|64), (2|3|4|6|8), true, true>", r"^(void )?stats_agg_kernel<(32|64), 2, false>",
+pats = sys.argv[1:] or [r"^(void )?tau_kernel<(32|64), (2|3|4|6|8), true, true>", r"^(void )?stats_agg_kernel<(32|64), 2>",
                         r"^(void )?nmft_persist_kernel<", r"^(void )?nmft_mfma_kernel<", r"^(void )?dirichlet_kernel\(", r"^(void )?stats_big_kernel<2>",
                         r"^(void )?stats_stage2_kernel<2>"]
 rows = []

@@ -105,10 +105,10 @@ print(h.hexdigest(), tr["ll"][-1])
 @pytest.mark.parametrize("V,S,G", [(10000, 64, 8), (6000, 96, 5)])
 def test_three_processes_end_on_the_same_bits(V, S, G):
     """1000 iterations in calls of uneven length after a 300-update NMF start (the benchmark's chain; the second shape takes the
-    register-lean sweep and a table whose rows are not whole 256 B blocks).  DESMAN_HIP_NTAB_TUNE=0 / DESMAN_HIP_TAU_ORDER=0 switch the
-    measured table place and the fp64-blocks-first order off: the bits may not depend on either."""
+    register-lean sweep and a table whose rows are not whole 256 B blocks).  DESMAN_HIP_TAU_ORDER=0 switches the fp64-blocks-first order
+    off: the bits may not depend on it."""
     outs = []
-    for env in ({}, {"DESMAN_HIP_NTAB_TUNE": "0", "DESMAN_HIP_TAU_ORDER": "0"}, {}):
+    for env in ({}, {"DESMAN_HIP_TAU_ORDER": "0"}, {}):
         r = subprocess.run([sys.executable, "-c", _SOAK, str(V), str(S), str(G)], env=dict(os.environ, **env), capture_output=True,
                            text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
