@@ -39,8 +39,6 @@ static_assert(sizeof(k_names) / sizeof(k_names[0]) == DSM_K_COUNT, "one name per
 extern "C" const char *dsm_kernel_name(int k) { return (k >= 0 && k < DSM_K_COUNT) ? k_names[k] : "?"; }
 
 // ---------------------------------------------------------------- timing
-thread_local BatchCtl g_batch;
-
 KTimer::KTimer(dsm_ctx *ctx, int kid, hipStream_t stream) : c(ctx), k(kid), st(stream ? stream : ctx->stream)
 {
     c->k_launches[k]++;
@@ -134,6 +132,13 @@ static int need(dsm_ctx *c, bool counts, bool state)
     return DSM_OK;
 }
 
+// Esum and the DSM_ESUM_PARTS copies stage 1 adds to, all zero: what a failed pass left in the copies is not added to the next one
+static int esum_reset(dsm_ctx *c)
+{
+    HIP_TRY(hipMemsetAsync(c->esum, 0, (16 + 16 * DSM_ESUM_PARTS) * sizeof(unsigned long long), c->stream));
+    return DSM_OK;
+}
+
 // Both slots of the sweep's block order start as the identity and no slot is marked usable: whatever a failed or skipped finalize launch
 // leaves behind is then the identity or an order written for the CURRENT grid (the grid changes only with the table: dsm_ctx_set_counts
 // calls this again) -- a sweep can never index its blocks through stale or uninitialised words.
@@ -196,7 +201,7 @@ extern "C" int dsm_ctx_create(dsm_ctx **out, int device)
     HIP_TRY(hipMemcpyAsync(c->log_tab, dsm_log_table_host, sizeof dsm_log_table_host, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->log_tab + 2 * DSM_LOG_TAB_N, dsm_exp_table_host, sizeof dsm_exp_table_host, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->nchange, 0, 2 * sizeof(int), c->stream));
-    HIP_TRY(hipMemsetAsync(c->esum, 0, (16 + 16 * DSM_ESUM_PARTS) * sizeof(unsigned long long), c->stream));
+    TRY(esum_reset(c));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *out = c;
     return DSM_OK;
@@ -661,13 +666,13 @@ extern "C" int dsm_ctx_sample_stats(dsm_ctx *c, uint32_t iter, uint64_t *sum_mu,
     const size_t sg = (size_t)c->S * c->G;
     HIP_TRY(hipMemsetAsync(c->sum_mu, 0, sg * sizeof(unsigned long long), c->stream));
     TRY(stats_ensure_ntab(c));
-    HIP_TRY(hipMemsetAsync(c->esum, 0, 16 * sizeof(unsigned long long), c->stream));
+    TRY(esum_reset(c));
     TRY(k_stats(c, iter));
     TRY(k_esum_fold(c));
     if (sum_mu) HIP_TRY(hipMemcpyAsync(sum_mu, c->sum_mu, sg * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (esum) HIP_TRY(hipMemcpyAsync(esum, c->esum, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemsetAsync(c->sum_mu, 0, sg * sizeof(unsigned long long), c->stream));
-    HIP_TRY(hipMemsetAsync(c->esum, 0, 16 * sizeof(unsigned long long), c->stream));
+    TRY(esum_reset(c));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;
 }
@@ -690,7 +695,7 @@ extern "C" int dsm_ctx_debug_stage1(dsm_ctx *c, uint32_t iter, uint32_t *ntab, u
     TRY(need(c, true, true));
     if (stats_spec(c) < 2) { dsm_set_error("debug_stage1: the aggregated specification does not apply to this shape (force it with dsm_ctx_force_stats_spec)"); return DSM_ERR_UNSUPPORTED; }
     BIND(c);
-    HIP_TRY(hipMemsetAsync(c->esum, 0, 16 * sizeof(unsigned long long), c->stream));
+    TRY(esum_reset(c));
     TRY(k_stats_stage1(c, iter));
     TRY(k_esum_fold(c));
     const size_t NH = (size_t)1 << c->G, S = (size_t)c->S;
@@ -699,7 +704,7 @@ extern "C" int dsm_ctx_debug_stage1(dsm_ctx *c, uint32_t iter, uint32_t *ntab, u
     HIP_TRY(hipMemcpyAsync(t.data(), c->ntab, t.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     if (esum) HIP_TRY(hipMemcpyAsync(esum, c->esum, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemsetAsync(c->ntab, 0, t.size() * sizeof(uint32_t), c->stream));
-    HIP_TRY(hipMemsetAsync(c->esum, 0, 16 * sizeof(unsigned long long), c->stream));
+    TRY(esum_reset(c));
     HIP_TRY(hipMemsetAsync(c->big_count, 0, DSM_BIG_NT * DSM_BIG_NL * DSM_BIG_STRIDE * sizeof(uint32_t), c->stream));     // no stage 2 follows to reset it
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (ntab)
@@ -790,56 +795,161 @@ static int alloc_traces(dsm_ctx *c, int n)
     return DSM_OK;
 }
 
-extern "C" int dsm_ctx_gibbs_update(dsm_ctx *c, int n_iter)
+// ---------------------------------------------------------------- chains of one call
+// What the launchers read to batch (dsm_host.h: LAUNCH_OR_COLLECT); written only by Chains::launch.
+thread_local BatchCtl g_batch;
+
+// The chains of one update call: one context on its own (the dsm_ctx_* entry points: plain launches), or K contexts of one shape
+// (dsm_batch_*: one launch per kernel for all of them, chain = blockIdx.y), each moved onto the leader's streams with timing off for
+// the duration of the call.  The destructor drains the leader's streams and puts every moved context back, on every return path.
+struct Chains {
+    dsm_ctx *const *c;
+    int K;
+    bool batched;
+    struct Home { hipStream_t stream, stream_rng; bool timing; int nmft_fused; };
+    std::vector<Home> home;                 // the moved chains' own settings
+    dsm_ctx *lead() const { return c[0]; }
+    ~Chains()
+    {
+        if (home.empty()) return;
+        (void)hipStreamSynchronize(lead()->stream);
+        (void)hipStreamSynchronize(lead()->stream_rng);
+        for (size_t k = 0; k < home.size(); ++k) {
+            c[k]->stream = home[k].stream; c[k]->stream_rng = home[k].stream_rng; c[k]->timing = home[k].timing; c[k]->nmft_fused = home[k].nmft_fused;
+        }
+    }
+    // Checks the chains (state: a chain state is needed; fits(lead, c, k): the caller's own checks of chain k) and, batched, moves them
+    // onto the leader's streams; nmft: with the leader's launch form of the NMF update.
+    template <class Fits> int open(bool state, bool nmft, Fits fits)
+    {
+        if (!c || K < 1 || K > DSM_MAX_BATCH) { dsm_set_error("batch of %d chains (1..%d)", K, DSM_MAX_BATCH); return DSM_ERR_ARG; }
+        for (int k = 0; k < K; ++k) {
+            TRY(need(c[k], true, state));
+            const dsm_ctx *a = c[0], *b = c[k];
+            if (b->device != a->device || b->V != a->V || b->S != a->S) { dsm_set_error("batch: chain %d differs from chain 0 in device or shape", k); return DSM_ERR_ARG; }
+            TRY(fits(a, b, k));
+            for (int j = 0; j < k; ++j) if (c[j] == b) { dsm_set_error("batch: chain %d listed twice", k); return DSM_ERR_ARG; }
+        }
+        BIND(lead());
+        for (int k = 0; batched && k < K; ++k) {
+            HIP_TRY(hipStreamSynchronize(c[k]->stream));
+            HIP_TRY(hipStreamSynchronize(c[k]->stream_rng));
+            home.push_back(Home{c[k]->stream, c[k]->stream_rng, c[k]->timing, c[k]->nmft_fused});
+            c[k]->stream = lead()->stream; c[k]->stream_rng = lead()->stream_rng; c[k]->timing = false;
+            if (nmft) c[k]->nmft_fused = home[0].nmft_fused;
+        }
+        return DSM_OK;
+    }
+    // f(chain, k) chain by chain, each launch its own
+    template <class F> int each(F f) const
+    {
+        for (int k = 0; k < K; ++k) TRY(f(c[k], k));
+        return DSM_OK;
+    }
+    // f(chain, k) for every chain; batched, what each launcher f calls collects from the chains goes out as one launch
+    template <class F> int launch(F f) const
+    {
+        int r = DSM_OK;
+        for (int k = 0; k < K && r == DSM_OK; ++k) {
+            if (batched) g_batch = BatchCtl{K, k};
+            r = f(c[k], k);
+        }
+        g_batch = BatchCtl{};
+        return r;
+    }
+};
+
+// the chains of a Gibbs or update_tau batch also share G and the tau RNG
+static int same_G_and_rng(const dsm_ctx *a, const dsm_ctx *b, int k)
 {
-    TRY(need(c, true, true));
+    if (b->G != a->G || b->tau_rng != a->tau_rng) { dsm_set_error("batch: chain %d differs from chain 0 in shape or tau RNG", k); return DSM_ERR_ARG; }
+    return DSM_OK;
+}
+
+// the Dirichlet log-prior terms of iteration it (two slots, by parity)
+static double *prior_slot(dsm_ctx *c, int it) { return c->prior + (it & 1) * (DSM_MAX_S + 4); }
+
+// The Gibbs loop of one chain (unbatched) or of K chains of one shape sharing every launch of the iteration.  A chain ends in the same
+// state either way: the mu/E specification is the chain's own (round 5; the per-read pass of small or shallow tables and of G > 16 is
+// launched chain by chain, everything else is shared).
+static int gibbs_update(dsm_ctx *const *ctxs, int K, bool batched, int n_iter)
+{
     if (n_iter < 0) { dsm_set_error("n_iter < 0"); return DSM_ERR_ARG; }
-    BIND(c);
-    TRY(alloc_traces(c, n_iter));
-    const size_t sg = (size_t)c->S * c->G;
-    HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
-    // entry state: ll, lp, storeStarState(0)  (HaploSNP_Sampler.py:336-338)
-    TRY(eval_state(c, c->gamma, c->eta, c->tau_trace, 1));
-    TRY(stats_ensure_ntab(c));
-    TRY(k_tau_neartie_hint(c));                          // which instantiation of the sweep this call runs (same draws either way)
-    double *const P[2] = {c->prior, c->prior + (DSM_MAX_S + 4)};
-    int nb_prev = 0;
+    Chains ch{ctxs, K, batched};
+    TRY(ch.open(true, false, [](const dsm_ctx *a, const dsm_ctx *b, int k) -> int {
+        TRY(same_G_and_rng(a, b, k));
+        // one specification per batch (the launches are shared): chains of one shape on one table have the same by rule
+        if (stats_spec(b) == stats_spec(a)) return DSM_OK;
+        dsm_set_error("batch: chain %d runs mu/E specification %d, chain 0 specification %d (different tables or different dsm_ctx_force_stats_spec)", k, stats_spec(b), stats_spec(a));
+        return DSM_ERR_ARG;
+    }));
+    dsm_ctx *const lead = ch.lead();
+    const int spec = stats_spec(lead);
+    // sampleMu (:341): spec v2 = stage 1, then stage 2 inside the Dirichlet launch; spec v1 = the per-read pass
+    const bool agg = spec >= 2;
+    const bool fuse_s2 = agg && lead->G < 10;           // many subsets per sample: stage 2 as its own 1024-thread launch
+    const size_t sg = (size_t)lead->S * lead->G;
     // the MT19937 words of the sweeps are generated on the side stream, chunks of sweeps ahead (never beyond the last sweep
     // of the call: the stream position must equal the reference's)
-    SweepWords words(c, n_iter);
-    TRY(words.prefetch());
+    std::vector<SweepWords> words;
+    words.reserve(K);
+    std::vector<int> nb_prev(K, 0);
+    std::vector<uint32_t> ic(K);
+    std::vector<const uint32_t *> u(K, nullptr);
+    TRY(ch.each([&](dsm_ctx *c, int) -> int {
+        TRY(alloc_traces(c, n_iter));
+        HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
+        // entry state: ll, lp, storeStarState(0)  (HaploSNP_Sampler.py:336-338)
+        TRY(eval_state(c, c->gamma, c->eta, c->tau_trace, 1));
+        TRY(stats_ensure_ntab(c));
+        if (!batched) TRY(k_tau_neartie_hint(c));       // which instantiation of the sweep this call runs (same draws either way)
+        words.emplace_back(c, n_iter);
+        return DSM_OK;
+    }));
+    TRY(ch.launch([&](dsm_ctx *, int k) { return words[k].prefetch(); }));
     for (int it = 0; it < n_iter; ++it) {
         // (the abundances move during a burn-in: the choice of the sweep's instantiation is looked at again now and then -- a stream
         // synchronisation and a 4-byte read-back every 64 iterations; the draws do not depend on it)
-        if (it && (it & 63) == 0 && c->tau_neartie_mode == -1) { TRY(k_tau_rare_count(c, true)); TRY(k_tau_neartie_hint(c)); }
-        const uint32_t ic = c->iter_ctr++;
-        // sampleMu (:341): spec v2 = stage 1 here, stage 2 inside the Dirichlet launch; spec v1 = the per-read pass
-        const bool agg = stats_spec(c) >= 2;
-        const bool fuse_s2 = agg && c->G < 10;           // many subsets per sample: stage 2 as its own 1024-thread launch
-        TRY(agg ? k_stats_stage1(c, ic) : k_stats_v1(c, ic));
-        if (agg && !fuse_s2) TRY(k_stats_stage2(c, ic));
+        if (!batched && it && (it & 63) == 0 && lead->tau_neartie_mode == -1) { TRY(k_tau_rare_count(lead, true)); TRY(k_tau_neartie_hint(lead)); }
+        TRY(ch.launch([&](dsm_ctx *c, int k) { ic[k] = c->iter_ctr++; return agg ? k_stats_stage1(c, ic[k]) : k_stats_v1(c, ic[k]); }));
+        if (agg && !fuse_s2) TRY(ch.launch([&](dsm_ctx *c, int k) { return k_stats_stage2(c, ic[k]); }));
         // sampleGamma (:342) + the eta draw (:347: eta depends only on the E sums) + traces; the same
         // launch finalizes iteration it-1 (ll, lp, MAP test :349-353) in one extra workgroup
-        TRY(k_dirichlet(c, ic, c->gamma, c->gamma_trace + (size_t)it * sg, c->eta_new, c->eta_trace + (size_t)it * 16,
-                        P[it & 1], it - 1, nb_prev, P[(it - 1) & 1], fuse_s2 ? 1 : 0));
+        TRY(ch.launch([&](dsm_ctx *c, int k) {
+            return k_dirichlet(c, ic[k], c->gamma, c->gamma_trace + (size_t)it * sg, c->eta_new, c->eta_trace + (size_t)it * 16,
+                               prior_slot(c, it), it - 1, nb_prev[k], prior_slot(c, it - 1), fuse_s2 ? 1 : 0);
+        }));
         // tau sweep with (gamma_new, eta_old) (:345) + log-likelihood of the new state with eta_new (:349)
-        const uint32_t *u = nullptr;
-        TRY(words.acquire(it, &u));
-        TRY(k_tau_sweep(c, 3, c->gamma, c->eta, c->eta_new, c->tau_trace + (size_t)(it + 1) * c->V, nullptr, ic, &nb_prev, u));
-        TRY(words.release(it));
-        std::swap(c->eta, c->eta_new);                                   // eta_new becomes the chain's eta
+        TRY(ch.launch([&](dsm_ctx *, int k) { return words[k].acquire(it, &u[k]); }));
+        TRY(ch.launch([&](dsm_ctx *c, int k) {
+            return k_tau_sweep(c, 3, c->gamma, c->eta, c->eta_new, c->tau_trace + (size_t)(it + 1) * c->V, nullptr, ic[k], &nb_prev[k], u[k]);
+        }));
+        TRY(ch.each([&](dsm_ctx *c, int k) -> int {
+            TRY(words[k].release(it));
+            std::swap(c->eta, c->eta_new);                               // eta_new becomes the chain's eta
+            return DSM_OK;
+        }));
     }
-    // the last iteration's finalize launch also counts the haplotypes that are rare in every sample -- what the next call's choice of
-    // sweep instantiation goes by -- straight into the host's pinned word: it rides on this call's own launch and synchronisation
-    const bool want_rare = n_iter > 0 && c->tau_neartie_mode == -1;
-    if (want_rare && !c->h_rare) HIP_TRY(hipHostMalloc((void **)&c->h_rare, sizeof(int), hipHostMallocDefault));
+    // the last iteration's finalize launch of a chain run alone also counts the haplotypes that are rare in every sample -- what the next
+    // call's choice of sweep instantiation goes by -- straight into the host's pinned word: it rides on this call's own launch and synchronisation
+    const bool want_rare = !batched && n_iter > 0 && lead->tau_neartie_mode == -1;
+    if (want_rare && !lead->h_rare) HIP_TRY(hipHostMalloc((void **)&lead->h_rare, sizeof(int), hipHostMallocDefault));
     if (n_iter > 0)
-        TRY(k_finalize(c, nb_prev, n_iter - 1, 0, P[(n_iter - 1) & 1], c->gamma_trace + (size_t)(n_iter - 1) * sg,
-                       c->eta_trace + (size_t)(n_iter - 1) * 16, 0, want_rare ? c->h_rare : nullptr));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (want_rare) c->tau_rare_n = *c->h_rare;
+        TRY(ch.each([&](dsm_ctx *c, int k) {
+            return k_finalize(c, nb_prev[k], n_iter - 1, 0, prior_slot(c, n_iter - 1), c->gamma_trace + (size_t)(n_iter - 1) * sg,
+                              c->eta_trace + (size_t)(n_iter - 1) * 16, 0, want_rare ? c->h_rare : nullptr);
+        }));
+    HIP_TRY(hipStreamSynchronize(lead->stream));
+    if (want_rare) lead->tau_rare_n = *lead->h_rare;
     return DSM_OK;
 }
+
+extern "C" int dsm_ctx_gibbs_update(dsm_ctx *c, int n_iter) { return gibbs_update(&c, 1, false, n_iter); }
+
+// K chains of one shape (same device, V, S, G, tau RNG), one launch per kernel of the iteration for all of them: on tables that leave
+// most of the GPU idle -- a few hundred to a few thousand positions, the usual DESMAN input -- the replicate chains of a G value
+// (scripts/runDesman.sh:15-21) then cost little more than one.  Every chain ends in the state dsm_ctx_gibbs_update leaves it in.
+extern "C" int dsm_batch_gibbs_update(dsm_ctx *const *ctxs, int K, int n_iter) { return gibbs_update(ctxs, K, true, n_iter); }
 
 // ONE chain sharded over several GPUs by positions (last row: for chains < GPUs).  This context holds positions
 // v_offset .. v_offset + V of a table of v_total; gamma / eta are replicated.  Per iteration the shards exchange, through
@@ -876,7 +986,7 @@ static int gibbs_update_sharded(dsm_ctx *c, int n_iter, int v_offset, int v_tota
     TRY(alloc_traces(c, n_iter));
     const size_t sg = (size_t)c->S * c->G;
     HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
-    HIP_TRY(hipMemsetAsync(c->esum, 0, 16 * sizeof(unsigned long long), c->stream));
+    TRY(esum_reset(c));
     auto swap_vec = [&](uint32_t *tab, size_t n_tab) -> int {
         if (comm) return comm_enqueue_exchange(comm, tab, n_tab, c->shard_vec, (size_t)18, c->stream);
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -891,7 +1001,7 @@ static int gibbs_update_sharded(dsm_ctx *c, int n_iter, int v_offset, int v_tota
         TRY(k_shard_pack(c, nb));
         TRY(swap_vec(nullptr, 0));
         TRY(k_finalize(c, nb, -1, 1, c->prior, c->gamma, c->eta));
-        HIP_TRY(hipMemsetAsync(c->esum, 0, 16 * sizeof(unsigned long long), c->stream));
+        TRY(esum_reset(c));
     }
     TRY(stats_ensure_ntab(c));
     double *const P[2] = {c->prior, c->prior + (DSM_MAX_S + 4)};
@@ -914,7 +1024,7 @@ static int gibbs_update_sharded(dsm_ctx *c, int n_iter, int v_offset, int v_tota
         TRY(swap_vec(nullptr, 0));
         TRY(k_finalize(c, nb_prev, n_iter - 1, 0, P[(n_iter - 1) & 1], c->gamma_trace + (size_t)(n_iter - 1) * sg,
                        c->eta_trace + (size_t)(n_iter - 1) * 16));
-        HIP_TRY(hipMemsetAsync(c->esum, 0, 16 * sizeof(unsigned long long), c->stream));
+        TRY(esum_reset(c));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;
@@ -947,115 +1057,9 @@ extern "C" int dsm_device_write(int device, void *dev, const void *host, size_t 
     return DSM_OK;
 }
 
-// K chains of one shape (same device, V, S, G, tau RNG), one launch per kernel of the iteration for all of them (chain =
-// blockIdx.y): on tables that leave most of the GPU idle -- a few hundred to a few thousand positions, the usual DESMAN
-// input -- the replicate chains of a G value (scripts/runDesman.sh:15-21) then cost little more than one.  Every chain ends
-// in the state dsm_ctx_gibbs_update leaves it in: the mu/E specification is the chain's own (round 5; the per-read pass of small or
-// shallow tables and of G > 16 is launched chain by chain, everything else is shared).
-extern "C" int dsm_batch_gibbs_update(dsm_ctx *const *ctxs, int K, int n_iter)
+// one chain's inputs of an update_tau call: the stored (gamma, eta) pairs in, the entry state and the log-priors of every pair
+static int tau_inputs(dsm_ctx *c, int n_iter, const double *gamma_store, const double *eta_store)
 {
-    if (!ctxs || K < 1 || K > DSM_MAX_BATCH) { dsm_set_error("batch of %d chains (1..%d)", K, DSM_MAX_BATCH); return DSM_ERR_ARG; }
-    if (n_iter < 0) { dsm_set_error("n_iter < 0"); return DSM_ERR_ARG; }
-    for (int k = 0; k < K; ++k) {
-        TRY(need(ctxs[k], true, true));
-        const dsm_ctx *a = ctxs[0], *b = ctxs[k];
-        if (b->device != a->device || b->V != a->V || b->S != a->S || b->G != a->G || b->tau_rng != a->tau_rng) {
-            dsm_set_error("batch: chain %d differs from chain 0 in device, shape or tau RNG", k);
-            return DSM_ERR_ARG;
-        }
-        for (int j = 0; j < k; ++j) if (ctxs[j] == ctxs[k]) { dsm_set_error("batch: chain %d listed twice", k); return DSM_ERR_ARG; }
-    }
-    dsm_ctx *const lead = ctxs[0];
-    BIND(lead);
-    // every chain on the leader's streams for the duration of the call; spec v2 of the mu/E pass
-    struct Saved { hipStream_t st, rng; int force; bool timing; };
-    std::vector<Saved> saved(K);
-    for (int k = 0; k < K; ++k) {
-        dsm_ctx *c = ctxs[k];
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream_rng));
-        saved[k] = Saved{c->stream, c->stream_rng, c->force_stats_spec, c->timing};
-        // (round 5: a chain's mu/E specification is its own -- what it would run alone, by the shape rule or by its own choice -- so that
-        // its draws do not depend on whether it runs in a batch; rounds 2-4 made every batch spec 2)
-        c->stream = lead->stream; c->stream_rng = lead->stream_rng; c->timing = false;
-    }
-    auto restore = [&]() {
-        g_batch = BatchCtl{};
-        for (int k = 0; k < K; ++k) {
-            dsm_ctx *c = ctxs[k];
-            c->stream = saved[k].st; c->stream_rng = saved[k].rng; c->force_stats_spec = saved[k].force; c->timing = saved[k].timing;
-        }
-    };
-#define BTRY(expr) do { int _r = (expr); if (_r != DSM_OK) { (void)hipStreamSynchronize(lead->stream); (void)hipStreamSynchronize(lead->stream_rng); restore(); return _r; } } while (0)
-#define BHIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { dsm_set_error("%s failed: %s", #expr, hipGetErrorString(_e)); (void)hipStreamSynchronize(lead->stream); restore(); return DSM_ERR_HIP; } } while (0)
-    // one specification per batch (the launches are shared): chains of one shape on one table have the same by rule
-    const int spec = stats_spec(lead);
-    for (int k = 1; k < K; ++k)
-        if (stats_spec(ctxs[k]) != spec) {
-            dsm_set_error("batch: chain %d runs mu/E specification %d, chain 0 specification %d (different tables or different dsm_ctx_force_stats_spec)", k, stats_spec(ctxs[k]), spec);
-            restore();
-            return DSM_ERR_ARG;
-        }
-    const bool agg = spec >= 2;                         // spec 1 (small or shallow tables, G > 16): the per-read pass has no shared launch -- chain by chain
-    const size_t sg = (size_t)lead->S * lead->G;
-    std::vector<SweepWords> words;
-    words.reserve(K);
-    std::vector<int> nb_prev(K, 0);
-    for (int k = 0; k < K; ++k) {                                  // entry states, chain by chain (once per call)
-        dsm_ctx *c = ctxs[k];
-        BTRY(alloc_traces(c, n_iter));
-        BHIP(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
-        BTRY(eval_state(c, c->gamma, c->eta, c->tau_trace, 1));
-        BTRY(stats_ensure_ntab(c));
-        words.emplace_back(c, n_iter);
-    }
-    g_batch.K = K;
-    for (int k = 0; k < K; ++k) { g_batch.k = k; BTRY(words[k].prefetch()); }
-    const bool fuse_s2 = agg && lead->G < 10;
-    std::vector<uint32_t> ic(K);
-    std::vector<const uint32_t *> u(K, nullptr);
-    for (int it = 0; it < n_iter; ++it) {
-        for (int k = 0; k < K; ++k) { g_batch.k = k; ic[k] = ctxs[k]->iter_ctr++; BTRY(agg ? k_stats_stage1(ctxs[k], ic[k]) : k_stats_v1(ctxs[k], ic[k])); }
-        if (agg && !fuse_s2) for (int k = 0; k < K; ++k) { g_batch.k = k; BTRY(k_stats_stage2(ctxs[k], ic[k])); }
-        for (int k = 0; k < K; ++k) {
-            dsm_ctx *c = ctxs[k];
-            double *const P[2] = {c->prior, c->prior + (DSM_MAX_S + 4)};
-            g_batch.k = k;
-            BTRY(k_dirichlet(c, ic[k], c->gamma, c->gamma_trace + (size_t)it * sg, c->eta_new, c->eta_trace + (size_t)it * 16,
-                             P[it & 1], it - 1, nb_prev[k], P[(it - 1) & 1], fuse_s2 ? 1 : 0));
-        }
-        for (int k = 0; k < K; ++k) { g_batch.k = k; BTRY(words[k].acquire(it, &u[k])); }
-        for (int k = 0; k < K; ++k) {
-            dsm_ctx *c = ctxs[k];
-            g_batch.k = k;
-            BTRY(k_tau_sweep(c, 3, c->gamma, c->eta, c->eta_new, c->tau_trace + (size_t)(it + 1) * c->V, nullptr, ic[k], &nb_prev[k], u[k]));
-        }
-        for (int k = 0; k < K; ++k) { g_batch.k = k; BTRY(words[k].release(it)); std::swap(ctxs[k]->eta, ctxs[k]->eta_new); }
-    }
-    g_batch = BatchCtl{};
-    if (n_iter > 0)
-        for (int k = 0; k < K; ++k) {
-            dsm_ctx *c = ctxs[k];
-            double *const P[2] = {c->prior, c->prior + (DSM_MAX_S + 4)};
-            BTRY(k_finalize(c, nb_prev[k], n_iter - 1, 0, P[(n_iter - 1) & 1], c->gamma_trace + (size_t)(n_iter - 1) * sg,
-                            c->eta_trace + (size_t)(n_iter - 1) * 16));
-        }
-    BHIP(hipStreamSynchronize(lead->stream));
-    BHIP(hipStreamSynchronize(lead->stream_rng));
-#undef BTRY
-#undef BHIP
-    restore();
-    return DSM_OK;
-}
-
-extern "C" int dsm_ctx_update_tau(dsm_ctx *c, int n_iter, const double *gamma_store, const double *eta_store)
-{
-    TRY(need(c, true, true));
-    if (n_iter < 1 || !gamma_store || !eta_store) { dsm_set_error("update_tau: bad arguments"); return DSM_ERR_ARG; }
-    BIND(c);
-    TRY(alloc_traces(c, n_iter));
-    SweepWords words(c, n_iter);
-    TRY(words.prefetch());
     const size_t sg = (size_t)c->S * c->G;
     if (n_iter > c->in_cap || !c->gamma_in) {            // grow-only, like the traces
         TRY(dev_alloc(&c->gamma_in, (size_t)n_iter * sg));
@@ -1075,119 +1079,55 @@ extern "C" int dsm_ctx_update_tau(dsm_ctx *c, int n_iter, const double *gamma_st
     // sweep it writes parity it & 1 of (ll_partial, nchange); its finalize (ll / lp / MAP test / traces) rides as one
     // extra workgroup in the launch of sweep it + 1, which writes the other parity: one launch per sweep
     HIP_TRY(hipMemsetAsync(c->nchange, 0, 2 * sizeof(int), c->stream));
-    int nb_prev = 0;
-    for (int it = 0; it < n_iter; ++it) {
-        const uint32_t ic = c->iter_ctr++;
-        const double *g = c->gamma_in + (size_t)it * sg, *e = c->eta_in + (size_t)it * 16;
-        const uint32_t *u = nullptr;
-        TRY(words.acquire(it, &u));
-        int nb = 0;
-        TauFinalRider rider;
-        if (it > 0) {
-            rider.nblocks = nb_prev; rider.it = it - 1; rider.prior = c->prior_all + (size_t)(it - 1) * (c->S + 4);
-            rider.gamma_src = c->gamma_in + (size_t)(it - 1) * sg; rider.eta_src = c->eta_in + (size_t)(it - 1) * 16;
-        }
-        TRY(k_tau_sweep(c, 3, g, e, e, c->tau_trace + (size_t)(it + 1) * c->V, nullptr, ic, &nb, u, it & 1,
-                        it > 0 ? &rider : nullptr));                                                    // :392-393
-        TRY(words.release(it));
-        nb_prev = nb;
-    }
-    TRY(k_finalize(c, nb_prev, n_iter - 1, 0, c->prior_all + (size_t)(n_iter - 1) * (c->S + 4),
-                   c->gamma_in + (size_t)(n_iter - 1) * sg, c->eta_in + (size_t)(n_iter - 1) * 16, (n_iter - 1) & 1));
-    HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;
 }
 
-// updateTau of K chains of one shape at once (the -r path of replicate chains): one tau_kernel launch per sweep for all of
-// them.  gamma_stores[k] [n][S][G], eta_stores[k] [n][4][4]: chain k's traces.
-extern "C" int dsm_batch_update_tau(dsm_ctx *const *ctxs, int K, int n_iter, const double *const *gamma_stores,
-                                    const double *const *eta_stores)
+// updateTau (the -r path) of one chain or of K chains of one shape sharing the launch of every sweep.  gamma_stores[k] [n][S][G],
+// eta_stores[k] [n][4][4]: chain k's traces.
+static int update_tau(dsm_ctx *const *ctxs, int K, bool batched, int n_iter, const double *const *gamma_stores, const double *const *eta_stores)
 {
-    if (!ctxs || K < 1 || K > DSM_MAX_BATCH) { dsm_set_error("batch of %d chains (1..%d)", K, DSM_MAX_BATCH); return DSM_ERR_ARG; }
     if (n_iter < 1 || !gamma_stores || !eta_stores) { dsm_set_error("update_tau: bad arguments"); return DSM_ERR_ARG; }
-    for (int k = 0; k < K; ++k) {
-        TRY(need(ctxs[k], true, true));
-        const dsm_ctx *a = ctxs[0], *b = ctxs[k];
+    Chains ch{ctxs, K, batched};
+    TRY(ch.open(true, false, [&](const dsm_ctx *a, const dsm_ctx *b, int k) {
         if (!gamma_stores[k] || !eta_stores[k]) { dsm_set_error("update_tau: bad arguments"); return DSM_ERR_ARG; }
-        if (b->device != a->device || b->V != a->V || b->S != a->S || b->G != a->G || b->tau_rng != a->tau_rng) {
-            dsm_set_error("batch: chain %d differs from chain 0 in device, shape or tau RNG", k);
-            return DSM_ERR_ARG;
-        }
-        for (int j = 0; j < k; ++j) if (ctxs[j] == ctxs[k]) { dsm_set_error("batch: chain %d listed twice", k); return DSM_ERR_ARG; }
-    }
-    dsm_ctx *const lead = ctxs[0];
-    BIND(lead);
-    struct Saved { hipStream_t st, rng; bool timing; };
-    std::vector<Saved> saved(K);
-    for (int k = 0; k < K; ++k) {
-        dsm_ctx *c = ctxs[k];
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream_rng));
-        saved[k] = Saved{c->stream, c->stream_rng, c->timing};
-        c->stream = lead->stream; c->stream_rng = lead->stream_rng; c->timing = false;
-    }
-    auto restore = [&]() {
-        g_batch = BatchCtl{};
-        for (int k = 0; k < K; ++k) { ctxs[k]->stream = saved[k].st; ctxs[k]->stream_rng = saved[k].rng; ctxs[k]->timing = saved[k].timing; }
-    };
-#define BTRY(expr) do { int _r = (expr); if (_r != DSM_OK) { (void)hipStreamSynchronize(lead->stream); (void)hipStreamSynchronize(lead->stream_rng); restore(); return _r; } } while (0)
-#define BHIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { dsm_set_error("%s failed: %s", #expr, hipGetErrorString(_e)); (void)hipStreamSynchronize(lead->stream); restore(); return DSM_ERR_HIP; } } while (0)
-    const size_t sg = (size_t)lead->S * lead->G;
+        return same_G_and_rng(a, b, k);
+    }));
+    const size_t sg = (size_t)ch.lead()->S * ch.lead()->G;
     std::vector<SweepWords> words;
     words.reserve(K);
-    for (int k = 0; k < K; ++k) {                                  // per chain, once: traces in, entry state, all log-priors
-        dsm_ctx *c = ctxs[k];
-        BTRY(alloc_traces(c, n_iter));
-        if (n_iter > c->in_cap || !c->gamma_in) {
-            BTRY(dev_alloc(&c->gamma_in, (size_t)n_iter * sg));
-            BTRY(dev_alloc(&c->eta_in, (size_t)n_iter * 16));
-            BTRY(dev_alloc(&c->prior_all, (size_t)n_iter * (c->S + 4)));
-            c->in_cap = n_iter;
-        }
-        BHIP(hipMemcpyAsync(c->gamma_in, gamma_stores[k], (size_t)n_iter * sg * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        BHIP(hipMemcpyAsync(c->eta_in, eta_stores[k], (size_t)n_iter * 16 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        BHIP(hipMemcpyAsync(c->gamma_trace, c->gamma_in, (size_t)n_iter * sg * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        BHIP(hipMemcpyAsync(c->eta_trace, c->eta_in, (size_t)n_iter * 16 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        BHIP(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
-        BTRY(eval_state(c, c->gamma_in, c->eta_in, c->tau_trace, 1));
-        BTRY(k_prior_batch(c, c->gamma_in, c->eta_in, n_iter, c->prior_all));
-        BHIP(hipMemsetAsync(c->nchange, 0, 2 * sizeof(int), c->stream));
-        words.emplace_back(c, n_iter);
-    }
-    g_batch.K = K;
-    for (int k = 0; k < K; ++k) { g_batch.k = k; BTRY(words[k].prefetch()); }
+    TRY(ch.each([&](dsm_ctx *c, int) -> int { TRY(alloc_traces(c, n_iter)); words.emplace_back(c, n_iter); return DSM_OK; }));
+    TRY(ch.launch([&](dsm_ctx *, int k) { return words[k].prefetch(); }));          // (generating while the inputs go in)
+    TRY(ch.each([&](dsm_ctx *c, int k) { return tau_inputs(c, n_iter, gamma_stores[k], eta_stores[k]); }));
     std::vector<int> nb_prev(K, 0);
     std::vector<const uint32_t *> u(K, nullptr);
     for (int it = 0; it < n_iter; ++it) {
-        for (int k = 0; k < K; ++k) { g_batch.k = k; BTRY(words[k].acquire(it, &u[k])); }
-        for (int k = 0; k < K; ++k) {
-            dsm_ctx *c = ctxs[k];
+        TRY(ch.launch([&](dsm_ctx *, int k) { return words[k].acquire(it, &u[k]); }));
+        TRY(ch.launch([&](dsm_ctx *c, int k) -> int {
             const uint32_t ic = c->iter_ctr++;
             const double *g = c->gamma_in + (size_t)it * sg, *e = c->eta_in + (size_t)it * 16;
-            int nb = 0;
             TauFinalRider rider;
             if (it > 0) {
                 rider.nblocks = nb_prev[k]; rider.it = it - 1; rider.prior = c->prior_all + (size_t)(it - 1) * (c->S + 4);
                 rider.gamma_src = c->gamma_in + (size_t)(it - 1) * sg; rider.eta_src = c->eta_in + (size_t)(it - 1) * 16;
             }
-            g_batch.k = k;
-            BTRY(k_tau_sweep(c, 3, g, e, e, c->tau_trace + (size_t)(it + 1) * c->V, nullptr, ic, &nb, u[k], it & 1, it > 0 ? &rider : nullptr));
-            nb_prev[k] = nb;
-        }
-        for (int k = 0; k < K; ++k) { g_batch.k = k; BTRY(words[k].release(it)); }
+            return k_tau_sweep(c, 3, g, e, e, c->tau_trace + (size_t)(it + 1) * c->V, nullptr, ic, &nb_prev[k], u[k], it & 1,
+                               it > 0 ? &rider : nullptr);                                              // :392-393
+        }));
+        TRY(ch.each([&](dsm_ctx *, int k) { return words[k].release(it); }));
     }
-    g_batch = BatchCtl{};
-    for (int k = 0; k < K; ++k) {
-        dsm_ctx *c = ctxs[k];
-        BTRY(k_finalize(c, nb_prev[k], n_iter - 1, 0, c->prior_all + (size_t)(n_iter - 1) * (c->S + 4),
-                        c->gamma_in + (size_t)(n_iter - 1) * sg, c->eta_in + (size_t)(n_iter - 1) * 16, (n_iter - 1) & 1));
-    }
-    BHIP(hipStreamSynchronize(lead->stream));
-    BHIP(hipStreamSynchronize(lead->stream_rng));
-#undef BTRY
-#undef BHIP
-    restore();
+    TRY(ch.each([&](dsm_ctx *c, int k) {
+        return k_finalize(c, nb_prev[k], n_iter - 1, 0, c->prior_all + (size_t)(n_iter - 1) * (c->S + 4),
+                          c->gamma_in + (size_t)(n_iter - 1) * sg, c->eta_in + (size_t)(n_iter - 1) * 16, (n_iter - 1) & 1);
+    }));
+    HIP_TRY(hipStreamSynchronize(ch.lead()->stream));
     return DSM_OK;
+}
+
+extern "C" int dsm_ctx_update_tau(dsm_ctx *c, int n_iter, const double *gamma_store, const double *eta_store) { return update_tau(&c, 1, false, n_iter, &gamma_store, &eta_store); }
+
+extern "C" int dsm_batch_update_tau(dsm_ctx *const *ctxs, int K, int n_iter, const double *const *gamma_stores, const double *const *eta_stores)
+{
+    return update_tau(ctxs, K, true, n_iter, gamma_stores, eta_stores);
 }
 
 extern "C" int dsm_release_device_caches(void)
@@ -1377,45 +1317,72 @@ extern "C" int dsm_nmft_get(dsm_ctx *c, double *tau, double *gamma)
 
 // nstat control words (after the G*S + 2G reduced statistics):
 //   [0] div of the current state  [1] previous div  [2] done flag  [3] updates run  [4] it at stop
+//   [10] the fused pass of factorize_tau left the current rows in ntau2  [11] the update kernel's own gamma step left gamma in ngam2
+static double *nmft_ctl(dsm_ctx *c) { return c->nstat + (size_t)c->nG * c->S + 2 * c->nG; }
+
+// One chain's part of a factorize call (dsm_nmft_factorize, dsm_batch_nmft_factorize): its start, its control words as last read back,
+// its end.  The destructor takes over which buffer of each pair the update loop left current -- pointer swaps, no copies -- and clears
+// what the update kernels read only during the call, on every return path.
+struct NmftRun {
+    dsm_ctx *c = nullptr;
+    Scratch<double> trace;                  // objective after every update
+    double h[12] = {};
+    bool fusedfix = false;                  // gamma fixed on the matrix-core kernel: ntau / ntau2 alternate
+    bool swap_tau = false, swap_gam = false;    // set by the update loops that alternate a pair (the persistent launch keeps its own)
+    ~NmftRun()
+    {
+        if (!c) return;
+        if (swap_tau && h[10] != 0.0) std::swap(c->ntau, c->ntau2);
+        if (swap_gam && h[11] != 0.0) { std::swap(c->ngam, c->ngam2); std::swap(c->ngam_raw, c->ngam_raw2); }
+        c->ndiv_trace = nullptr; c->nmft_fix_gamma = 0;
+    }
+    int begin(dsm_ctx *ctx, int max_iter, int fix_gamma)
+    {
+        c = ctx;
+        TRY(trace.alloc((size_t)max_iter + 1));
+        HIP_TRY(hipMemsetAsync(nmft_ctl(c), 0, 16 * sizeof(double), c->stream));
+        c->ndiv_trace = trace;
+        // gamma fixed: the update kernels leave out what only a gamma update reads (kernels_nmft.hip), and on the matrix-core kernel an
+        // update is ONE fused pass (objective of the current rows + candidate rows of the next update into the second buffer, accepted or
+        // not by the control step that follows: NmftMfmaParams.fix_gamma == 2)
+        fusedfix = fix_gamma && nmft_use_mfma(c);
+        c->nmft_fix_gamma = fusedfix ? 2 : fix_gamma ? 1 : 0;
+        if (fusedfix && !c->ntau2) TRY(dev_alloc(&c->ntau2, (size_t)c->V * 4 * c->nG));
+        // factorize applies _adjustment once before the first objective (Init_NMFT.py:102)
+        if (!fix_gamma) TRY(k_nmft_clamp(c));
+        return DSM_OK;
+    }
+    int read_ctl() { HIP_TRY(hipMemcpyAsync(h, nmft_ctl(c), sizeof h, hipMemcpyDeviceToHost, c->stream)); return DSM_OK; }
+    // updates run and the objective trace, from the control words read back after the last launch (the copy is enqueued)
+    int finish(int *n_done, double *div_trace)
+    {
+        const int done = (int)h[3];
+        if (n_done) *n_done = done;
+        if (div_trace) HIP_TRY(hipMemcpyAsync(div_trace, trace, ((size_t)done + 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        return DSM_OK;
+    }
+};
+
 extern "C" int dsm_nmft_factorize(dsm_ctx *c, int max_iter, double min_change, int fix_gamma, int *n_done, double *div_trace)
 {
     TRY(need(c, true, false));
     if (!c->ntau) { dsm_set_error("nmft_factorize: call dsm_nmft_set first"); return DSM_ERR_STATE; }
     if (max_iter < 0) { dsm_set_error("max_iter < 0"); return DSM_ERR_ARG; }
     BIND(c);
-    const int G = c->nG, S = c->S;
-    double *ctl = c->nstat + (size_t)G * S + 2 * G;
-    Scratch<double> d_trace;
-    TRY(d_trace.alloc((size_t)max_iter + 1));
-    struct TraceGuard { dsm_ctx *c; ~TraceGuard() { c->ndiv_trace = nullptr; c->nmft_fix_gamma = 0; } } trace_guard{c};
-    HIP_TRY(hipMemsetAsync(ctl, 0, 16 * sizeof(double), c->stream));
+    NmftRun run;
+    TRY(run.begin(c, max_iter, fix_gamma));
     const int adjust = fix_gamma ? 0 : 1;
-    c->ndiv_trace = d_trace;
-    c->nmft_fix_gamma = fix_gamma ? 1 : 0;               // the update kernels leave out what only a gamma update reads (kernels_nmft.hip)
-    // ... and on the matrix-core kernel an update is ONE fused pass (objective of the current rows + candidate rows of the next update
-    // into a second buffer, accepted or not by the control step that follows: NmftMfmaParams.fix_gamma == 2)
-    const bool fusedfix = fix_gamma && nmft_use_mfma(c);
-    if (fusedfix) {
-        if (!c->ntau2) TRY(dev_alloc(&c->ntau2, (size_t)c->V * 4 * G));
-        c->nmft_fix_gamma = 2;
-    }
-    // factorize applies _adjustment once before the first objective (Init_NMFT.py:102)
-    if (adjust) TRY(k_nmft_clamp(c));
+    const bool fusedfix = run.fusedfix;
     const int BATCH = 64;
-    double h[7] = {0, 0, 0, 0, 0, 0, 0};
     {
         // tables whose quads of variants are all resident at once: the whole loop as ONE persistent launch (kernels_nmft.hip)
         int used = 0;
         TRY(k_nmft_persist(c, max_iter, min_change, fix_gamma, adjust, &used));
         if (used) {
-            HIP_TRY(hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, c->stream));
+            TRY(run.read_ctl());
             HIP_TRY(hipStreamSynchronize(c->stream));
-            const int done = (int)h[3];
-            if (n_done) *n_done = done;
-            if (div_trace) {
-                HIP_TRY(hipMemcpyAsync(div_trace, d_trace, ((size_t)done + 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(hipStreamSynchronize(c->stream));
-            }
+            TRY(run.finish(n_done, div_trace));
+            HIP_TRY(hipStreamSynchronize(c->stream));
             return DSM_OK;
         }
     }
@@ -1432,6 +1399,8 @@ extern "C" int dsm_nmft_factorize(dsm_ctx *c, int max_iter, double min_change, i
     // time: 4.2 s eager -> 2.2 s replayed.  desman_amd.chains opts in through DESMAN_HIP_NMFT_GRAPH=1.
     // (Timing mode records events per launch -> eager.)
     const bool gstep = wave && !fusedfix && nmft_gstep_applies(c, fix_gamma);
+    run.swap_tau = fusedfix;                 // an odd number of accepted candidates: the current rows are in ntau2
+    run.swap_gam = gstep;                    // an odd number of gamma steps: the current gamma is in ngam2
     auto enqueue_iteration = [&](int n) -> int {                                     // n = launch number of this call (parity slot)
         if (fusedfix) {                                                              // the pass first: its objective is what the control step tests
             TRY(k_nmft_wave(c, adjust, 1));
@@ -1470,33 +1439,12 @@ extern "C" int dsm_nmft_factorize(dsm_ctx *c, int max_iter, double min_change, i
     for (int launched = 0; launched <= max_iter;) {
         if (use_graph) { HIP_TRY(hipGraphLaunch(gexec, c->stream)); launched += BATCH; }
         else { for (int k = 0; k < BATCH && launched <= max_iter; ++k, ++launched) TRY(enqueue_iteration(launched)); }
-        HIP_TRY(hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, c->stream));
+        TRY(run.read_ctl());
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (h[2] != 0.0) break;
+        if (run.h[2] != 0.0) break;
     }
-    const int done = (int)h[3];
-    if (n_done) *n_done = done;
-    if (gstep) {
-        // the update kernel's own gamma step alternates between two buffers: an odd number of updates leaves the current gamma in the second
-        double cur = 0.0;
-        HIP_TRY(hipMemcpyAsync(&cur, ctl + 11, sizeof cur, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (cur != 0.0) {
-            HIP_TRY(hipMemcpyAsync(c->ngam, c->ngam2, (size_t)G * S * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(c->ngam_raw, c->ngam_raw2, (size_t)G * S * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        }
-    }
-    if (fusedfix) {
-        // an odd number of accepted candidates: the current rows are in the second buffer
-        double par = 0.0;
-        HIP_TRY(hipMemcpyAsync(&par, ctl + 10, sizeof par, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (par != 0.0) HIP_TRY(hipMemcpyAsync(c->ntau, c->ntau2, (size_t)c->V * 4 * G * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    }
-    if (div_trace) {
-        HIP_TRY(hipMemcpyAsync(div_trace, d_trace, ((size_t)done + 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
+    TRY(run.finish(n_done, div_trace));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;
 }
 
@@ -1507,89 +1455,42 @@ extern "C" int dsm_nmft_factorize(dsm_ctx *c, int max_iter, double min_change, i
 extern "C" int dsm_batch_nmft_factorize(dsm_ctx *const *ctxs, int K, int max_iter, double min_change, int fix_gamma,
                                         int *n_done, double *div_traces)
 {
-    if (!ctxs || K < 1 || K > DSM_MAX_BATCH) { dsm_set_error("batch of %d chains (1..%d)", K, DSM_MAX_BATCH); return DSM_ERR_ARG; }
     if (max_iter < 0) { dsm_set_error("max_iter < 0"); return DSM_ERR_ARG; }
-    for (int k = 0; k < K; ++k) {
-        TRY(need(ctxs[k], true, false));
-        const dsm_ctx *a = ctxs[0], *b = ctxs[k];
-        if (!b->ntau) { dsm_set_error("nmft_factorize: call dsm_nmft_set first (chain %d)", k); return DSM_ERR_STATE; }
-        if (b->device != a->device || b->V != a->V || b->S != a->S || b->nG != a->nG) {
-            dsm_set_error("batch: chain %d differs from chain 0 in device or shape", k);
-            return DSM_ERR_ARG;
-        }
-        for (int j = 0; j < k; ++j) if (ctxs[j] == ctxs[k]) { dsm_set_error("batch: chain %d listed twice", k); return DSM_ERR_ARG; }
-        if (!nmft_use_mfma(b) && !nmft_use_wide(b)) { dsm_set_error("batch: the matrix-core NMFT kernels do not apply to this shape (S <= 512, G <= 16)"); return DSM_ERR_UNSUPPORTED; }
-    }
-    dsm_ctx *const lead = ctxs[0];
     // (Round 6, VERDICT r5 item 6 -- measured, not kept: every chain of a batch of small tables running its own persistent launch from a host
     // thread of its own, as many at once as the persistent path's gate admits (four of V = 1000, S = 64).  4.4 us per chain-update at 8 x
     // (1000, 64, 5) and 8 x COG0015 against 2.9-3.0 for the batched three-launch loop below, which shares every launch among the K chains:
     // profiles/r06_batch_nmft.txt.  The batched loop already is what the item asked a batch-persistent kernel for.)
-    BIND(lead);
-    const int G = lead->nG, S = lead->S;
-    struct Saved { hipStream_t st; bool timing; int fused; };
-    std::vector<Saved> saved(K);
-    std::vector<Scratch<double>> traces(K);
-    for (int k = 0; k < K; ++k) {
-        dsm_ctx *c = ctxs[k];
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        saved[k] = Saved{c->stream, c->timing, c->nmft_fused};
-        c->stream = lead->stream; c->timing = false; c->nmft_fused = saved[0].fused;   // one launch form for the whole batch: the leader's
-    }
-    auto restore = [&]() {
-        g_batch = BatchCtl{};
-        for (int k = 0; k < K; ++k) {
-            ctxs[k]->stream = saved[k].st; ctxs[k]->timing = saved[k].timing; ctxs[k]->nmft_fused = saved[k].fused;
-            ctxs[k]->ndiv_trace = nullptr; ctxs[k]->nmft_fix_gamma = 0;
-        }
-    };
-#define BTRY(expr) do { int _r = (expr); if (_r != DSM_OK) { (void)hipStreamSynchronize(lead->stream); restore(); return _r; } } while (0)
-#define BHIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { dsm_set_error("%s failed: %s", #expr, hipGetErrorString(_e)); (void)hipStreamSynchronize(lead->stream); restore(); return DSM_ERR_HIP; } } while (0)
+    NmftRun run[DSM_MAX_BATCH];             // (before the chains: their destructor drains the stream before the traces are freed)
+    Chains ch{ctxs, K, true};
+    TRY(ch.open(false, true, [](const dsm_ctx *a, const dsm_ctx *b, int k) {
+        if (!b->ntau) { dsm_set_error("nmft_factorize: call dsm_nmft_set first (chain %d)", k); return DSM_ERR_STATE; }
+        if (b->nG != a->nG) { dsm_set_error("batch: chain %d differs from chain 0 in device or shape", k); return DSM_ERR_ARG; }
+        if (!nmft_use_mfma(b) && !nmft_use_wide(b)) { dsm_set_error("batch: the matrix-core NMFT kernels do not apply to this shape (S <= 512, G <= 16)"); return DSM_ERR_UNSUPPORTED; }
+        return DSM_OK;
+    }));
     const int adjust = fix_gamma ? 0 : 1;
-    const bool fused = fix_gamma && nmft_use_mfma(lead);                  // (S > 128: nmft_split_kernel has no fused pass)
-    auto ctl_of = [&](dsm_ctx *c) { return c->nstat + (size_t)G * S + 2 * G; };
-    for (int k = 0; k < K; ++k) {                                  // per chain, once: control words, _adjustment, first statistics
-        dsm_ctx *c = ctxs[k];
-        BTRY(traces[k].alloc((size_t)max_iter + 1));
-        c->ndiv_trace = traces[k];
-        c->nmft_fix_gamma = fused ? 2 : (fix_gamma ? 1 : 0);      // gamma fixed: the fused pass where the shape has one (dsm_nmft_factorize), else the two-half form without gamma numerators
-        if (fused && !c->ntau2) BTRY(dev_alloc(&c->ntau2, (size_t)c->V * 4 * G));
-        BHIP(hipMemsetAsync(ctl_of(c), 0, 16 * sizeof(double), c->stream));
-        if (adjust) BTRY(k_nmft_clamp(c));
-    }
-    g_batch.K = K;
-    if (!fused) for (int k = 0; k < K; ++k) { g_batch.k = k; BTRY(k_nmft_wave(ctxs[k], adjust, 0)); }
+    TRY(ch.each([&](dsm_ctx *c, int k) { return run[k].begin(c, max_iter, fix_gamma); }));
+    // gamma fixed: the fused pass where the shape has one (S <= 128), else the two-half form of nmft_split_kernel without gamma numerators
+    const bool fused = run[0].fusedfix;
+    for (int k = 0; k < K; ++k) run[k].swap_tau = fused;
+    if (!fused) TRY(ch.launch([&](dsm_ctx *c, int) { return k_nmft_wave(c, adjust, 0); }));
     const int BATCH = 64;
-    std::vector<double> h((size_t)K * 11, 0.0);
     for (int launched = 0; launched <= max_iter;) {
         for (int i = 0; i < BATCH && launched <= max_iter; ++i, ++launched) {
-            if (fused)                                  // the fused pass first: its objective is what the control step tests
-                for (int k = 0; k < K; ++k) { g_batch.k = k; BTRY(k_nmft_wave(ctxs[k], adjust, 1)); }
-            for (int k = 0; k < K; ++k) { g_batch.k = k; BTRY(k_nmft_gamma(ctxs[k], max_iter, min_change, fix_gamma, adjust, launched & 1)); }
-            if (!fused)
-                for (int k = 0; k < K; ++k) { g_batch.k = k; BTRY(k_nmft_wave(ctxs[k], adjust, 1)); }
+            if (fused) TRY(ch.launch([&](dsm_ctx *c, int) { return k_nmft_wave(c, adjust, 1); }));     // the fused pass first: its objective is what the control step tests
+            TRY(ch.launch([&](dsm_ctx *c, int) { return k_nmft_gamma(c, max_iter, min_change, fix_gamma, adjust, launched & 1); }));
+            if (!fused) TRY(ch.launch([&](dsm_ctx *c, int) { return k_nmft_wave(c, adjust, 1); }));
         }
-        for (int k = 0; k < K; ++k)
-            BHIP(hipMemcpyAsync(h.data() + (size_t)k * 11, ctl_of(ctxs[k]), 11 * sizeof(double), hipMemcpyDeviceToHost, lead->stream));
-        BHIP(hipStreamSynchronize(lead->stream));
+        TRY(ch.each([&](dsm_ctx *, int k) { return run[k].read_ctl(); }));
+        HIP_TRY(hipStreamSynchronize(ch.lead()->stream));
         bool all = true;
-        for (int k = 0; k < K; ++k) all = all && h[(size_t)k * 11 + 2] != 0.0;
+        for (int k = 0; k < K; ++k) all = all && run[k].h[2] != 0.0;
         if (all) break;
     }
-    g_batch = BatchCtl{};
-    for (int k = 0; k < K; ++k) {
-        const int done = (int)h[(size_t)k * 11 + 3];
-        if (n_done) n_done[k] = done;
-        if (fused && h[(size_t)k * 11 + 10] != 0.0)              // an odd number of accepted candidates: the current rows are in the second buffer
-            BHIP(hipMemcpyAsync(ctxs[k]->ntau, ctxs[k]->ntau2, (size_t)ctxs[k]->V * 4 * G * sizeof(double), hipMemcpyDeviceToDevice, lead->stream));
-        if (div_traces)
-            BHIP(hipMemcpyAsync(div_traces + (size_t)k * ((size_t)max_iter + 1), traces[k], ((size_t)done + 1) * sizeof(double),
-                                hipMemcpyDeviceToHost, lead->stream));
-    }
-    BHIP(hipStreamSynchronize(lead->stream));
-#undef BTRY
-#undef BHIP
-    restore();
+    TRY(ch.each([&](dsm_ctx *, int k) {
+        return run[k].finish(n_done ? n_done + k : nullptr, div_traces ? div_traces + (size_t)k * ((size_t)max_iter + 1) : nullptr);
+    }));
+    HIP_TRY(hipStreamSynchronize(ch.lead()->stream));
     return DSM_OK;
 }
 
@@ -1598,12 +1499,10 @@ extern "C" int dsm_nmft_objective(dsm_ctx *c, double *div)
     TRY(need(c, true, false));
     if (!c->ntau || !div) { dsm_set_error("nmft_objective: call dsm_nmft_set first"); return DSM_ERR_STATE; }
     BIND(c);
-    const int G = c->nG, S = c->S;
-    double *ctl = c->nstat + (size_t)G * S + 2 * G;
-    HIP_TRY(hipMemsetAsync(ctl, 0, 16 * sizeof(double), c->stream));
+    HIP_TRY(hipMemsetAsync(nmft_ctl(c), 0, 16 * sizeof(double), c->stream));
     TRY(nmft_use_wave(c) ? k_nmft_wave(c, 0, 0) : k_nmft_pass_a(c));
     TRY(k_nmft_gamma(c, 0, 0.0, 1, 0, 0));     // max_iter = 0: reduce + record div only
-    HIP_TRY(hipMemcpyAsync(div, ctl, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(div, nmft_ctl(c), sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;
 }

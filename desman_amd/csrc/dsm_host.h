@@ -8,7 +8,7 @@
 #include "../../include/desman_hip.h"
 
 #define DSM_MAX_GRID 4096
-#define DSM_ESUM_PARTS 64   // copies of Esum the workgroups of stage 1 add to (workgroup b: copy b mod 64); the compacted kernel folds them into Esum
+#define DSM_ESUM_PARTS 64   // copies of Esum the wavefronts of stage 1 add to (wavefront w: copy w mod 64); the eta rows of dirichlet_kernel, esum_fold_kernel and shard_pack fold them into Esum
 #define DSM_BIG_NL 64        // sub-lists of deferred stage-1 items (kernels_stats.hip), one counter each ...
 #define DSM_BIG_STRIDE 16    // ... 64 B apart
 #define DSM_BIG_NT 3         // ... for each kind of deferred item (BTRS / long search / search + two more binomials)

@@ -75,23 +75,70 @@ def test_batch_equals_chains_run_one_by_one(V, S, G, K, n_iter, spec):
         c.close()
 
 
+def _nmft_start(V, S, G, seed):
+    rs = np.random.RandomState(seed)
+    gam0 = np.ascontiguousarray(rs.dirichlet(np.full(G, 0.3), size=S).T)
+    d = rs.dirichlet(np.full(4, 0.3), size=V * G).reshape(V, G, 4)
+    return np.ascontiguousarray(np.transpose(d, (2, 0, 1)).reshape(4 * V, G)), gam0
+
+
 def test_batch_argument_checks():
-    counts, _, _ = synth_counts(50, 8, 3, seed=1)
-    a = _chain(counts, random_state(50, 8, 3, seed=2), 1, 2)
-    b = _chain(counts[:40], random_state(40, 8, 3, seed=3), 1, 2)
-    with pytest.raises(_lib.DesmanHipError):
-        _lib.Context.batch_gibbs_update([a, b], 2)             # shapes differ
-    a2 = _chain(counts, random_state(50, 8, 3, seed=4), 1, 2)
-    a2.force_stats_spec(_lib.STATS_AGG)
-    with pytest.raises(_lib.DesmanHipError):
-        _lib.Context.batch_gibbs_update([a, a2], 2)            # one chain asks for another mu/E specification than the other runs
-    a2.close()
-    with pytest.raises(_lib.DesmanHipError):
-        _lib.Context.batch_gibbs_update([a, a], 2)             # the same chain twice
-    with pytest.raises(_lib.DesmanHipError):
-        _lib.Context.batch_gibbs_update([a] * 9, 2)            # more than 8
+    """Every batch entry point refuses a bad batch with the same error code, and every context of a refused batch then runs alone
+    bit for bit as an identically built context that was never put in a batch (its own streams, timing and NMF launch form)."""
+    V, S, G = 50, 8, 3
+    counts, _, _ = synth_counts(V, S, G, seed=1)
+
+    def build(k, v=V, g=G, spec=0, nmft_g=G):
+        c = _chain(counts[:v], random_state(v, S, g, seed=2 + k), 1 + k, 2 + k)
+        c.force_stats_spec(spec)
+        if nmft_g:
+            c.nmft_set(*_nmft_start(v, S, nmft_g, seed=20 + k))
+        return c
+
+    recipes = dict(a=dict(k=0), a1=dict(k=1), b=dict(k=2, v=40),                 # b: another shape
+                   spec=dict(k=3, spec=_lib.STATS_AGG),    # asks for another mu/E specification than the others run
+                   g4=dict(k=4, g=4),                      # another G
+                   no_nmft=dict(k=5, nmft_g=0),            # dsm_nmft_set never called
+                   ng4=dict(k=6, nmft_g=4))                # another NMF rank
+    ctx = {name: build(**r) for name, r in recipes.items()}
+    a, a1 = ctx["a"], ctx["a1"]
+    n = 3
+    rs = np.random.RandomState(9)
+
+    def stores(cs):
+        return ([np.ascontiguousarray(rs.dirichlet(np.ones(c.G), size=(n, c.S))) for c in cs],
+                [np.ascontiguousarray(rs.dirichlet(np.ones(4), size=(n, 4)) * 0.08 + 0.92 * np.eye(4)) for c in cs])
+
+    ARG, STATE = "error -2:", "error -3:"
+    refused = [
+        (lambda cs: _lib.Context.batch_gibbs_update(cs, 2), [[a, ctx["b"]], [a, ctx["g4"]], [a, ctx["spec"]], [a, a1, a], [a] * 9], []),
+        (lambda cs: _lib.Context.batch_update_tau(cs, *stores(cs)), [[a, ctx["b"]], [a, ctx["g4"]], [a, a1, a], [a] * 9], []),
+        (lambda cs: _lib.Context.batch_nmft_factorize(cs, 20, 1e-7), [[a, ctx["b"]], [a, ctx["ng4"]], [a, a1, a], [a] * 9],
+         [[a, ctx["no_nmft"]]]),
+    ]
+    for call, arg_cases, state_cases in refused:
+        for cs, code in [(cs, ARG) for cs in arg_cases] + [(cs, STATE) for cs in state_cases]:
+            with pytest.raises(_lib.DesmanHipError, match=code):
+                call(cs)
+
+    # after the refusals: each context alone == a fresh one built the same way
+    def alone(c, nmft):
+        c.gibbs_update(4)
+        out = _snapshot(c)
+        if nmft:
+            out["nmft_n"], out["nmft_trace"] = c.nmft_factorize(30, 1e-7)
+            out["nmft_tau"], out["nmft_gamma"] = c.nmft_get()
+        return out
+
+    for name, r in recipes.items():
+        nmft = r.get("nmft_g", G) != 0
+        fresh = build(**r)
+        want = alone(fresh, nmft)
+        fresh.close()
+        _same(want, alone(ctx[name], nmft))
     _lib.Context.batch_gibbs_update([a], 2)                    # a batch of one is allowed
-    a.close(); b.close()
+    for c in ctx.values():
+        c.close()
 
 
 @pytest.mark.parametrize("V,S,G,K", [(120, 16, 4, 3), (300, 64, 8, 5), (90, 96, 12, 2), (50, 7, 1, 4), (90, 96, 3, 2), (70, 130, 4, 3),

@@ -96,6 +96,22 @@ def _nmft_run(counts, tau0, gam0, fused, fix_gamma, max_iter=20, persist=0):
     return n, tr, tau, gam, onehot, div
 
 
+def _nmft_two_calls(counts, tau0, gam0, fused):
+    """factorize with an odd number of updates, then factorize_tau, on one context of the three-launch loop"""
+    c = _lib.Context(0)
+    c.set_counts(counts)
+    c.set_nmft_persist(0)
+    c.set_nmft_fused(fused)
+    c.nmft_set(tau0, gam0)
+    out = []
+    for fix_gamma in (False, True):
+        n, tr = c.nmft_factorize(max_iter=19, min_change=1e-5, fix_gamma=fix_gamma)
+        tau, gam = c.nmft_get()
+        out.append((n, tr, tau, gam, c.nmft_get_tau()))
+    c.close()
+    return out
+
+
 @pytest.mark.parametrize("V,S,G", [(10000, 64, 8), (50000, 96, 12), (3000, 64, 8), (2000, 32, 5), (13000, 40, 3), (12288, 48, 12), (933, 64, 5),
                                    (97, 20, 2), (5000, 128, 8), (2500, 110, 12), (14001, 100, 3), (3000, 64, 16), (6000, 96, 13), (2000, 128, 15),
                                    (3000, 300, 8), (1001, 130, 3), (801, 512, 16), (2000, 200, 12), (1500, 260, 5), (37, 400, 2),
@@ -135,6 +151,13 @@ def test_full_size_nmft_factorize_matches_oracle(V, S, G):
         assert np.array_equal(onehot_p, onehot) and div_p == div
         if fix_gamma:
             assert np.array_equal(gam_p, gam0)
+        else:
+            # a second call on the context after the update kernel's own gamma step (3: where the shape allows it) ran an odd number
+            # of updates, which leaves the current gamma in its second buffers: the same bits as with a launch of its own (0)
+            gst, own = _nmft_two_calls(counts, tau0, gam0, 3), _nmft_two_calls(counts, tau0, gam0, 0)
+            assert gst[0][0] == 19
+            for x, y in zip(gst, own):
+                assert x[0] == y[0] and all(np.array_equal(u, v) for u, v in zip(x[1:], y[1:]))
 
 
 def test_full_size_nmft_stop_rule_fires_at_the_oracles_update():
