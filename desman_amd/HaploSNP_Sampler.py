@@ -3,8 +3,11 @@
 Same class name, constructor signature, attributes and method names; the Gibbs
 iterations run entirely on the device (dsm_ctx_gibbs_update).  V-sized arrays
 are fetched from HBM only when asked for (tau_store is materialised lazily).
+assignTau (dead in the reference's CLI, bin/desman:213-214) runs on the device as an
+exact enumeration of the 4^G joint states (dsm_assign_tau, G <= 10); the tauStates
+table it walks upstream is never built.
 Not mirrored (never reached by the CLI): the pure-Python
-samplers, Chib marginal likelihood, DIC, assignTau, the 4^G tauStates table.
+samplers, Chib marginal likelihood, DIC.
 """
 import logging
 
@@ -43,6 +46,7 @@ class HaploSNP_Sampler:
         self._alloc_stores()
         self.ll = 0.0
         self.lp = 0.0
+        self._device = device
         self._ctx = ctx if ctx is not None else _lib.Context(device)
         self._ctx.set_counts(self.variants)
         self._ctx.set_priors(alpha_constant, delta_constant, epsilon)
@@ -221,6 +225,32 @@ class HaploSNP_Sampler:
             self.tauIndices = (idx * w[None, :]).sum(axis=1)
         else:
             self.tauIndices = np.array([self.mapTauState(self.tau[v]) for v in range(self.V)], dtype=object)
+
+    # ---- positions that were not in the fit (HaploSNP_Sampler.py:233-261)
+    def _assign(self, assignMatrix, seed):
+        a = np.asarray(assignMatrix)
+        counts = np.ascontiguousarray(np.reshape(a, (a.shape[0], self.S, 4)), dtype=np.int64)
+        return _lib.assign_tau(counts, self.gamma_star, self.eta_star, seed=seed, device=self._device)
+
+    @staticmethod
+    def _onehot(state):
+        out = np.zeros(state.shape + (4,), dtype=np.int64)
+        np.put_along_axis(out, state.astype(np.int64)[..., None], 1, axis=2)
+        return out
+
+    def assignTau(self, assignMatrix):
+        """(assignTau [N,G,4] one-hot, conf [N]) for the rows of assignMatrix [N, S*4] under gamma_star / eta_star: assignTau is one
+        draw from the exact posterior over the 4^G joint states of each position, conf the posterior probability of its most
+        probable state.  The draw is keyed by one randint of the sampler's randomState, so repeated calls differ as upstream."""
+        seed = int(self.randomState.randint(0, 2 ** 31 - 1))
+        res = self._assign(assignMatrix, seed)
+        return self._onehot(res["draw_state"]), res["conf"]
+
+    def assignTauExact(self, assignMatrix):
+        """the deterministic part of the same posterior: dict of tau [N,G,4] (one-hot MAP state, ties to the lowest state index),
+        conf [N], logz [N] (log normaliser) and marg [N,G,4] (P(tau_vg = a), the exact counterpart of tauMean)"""
+        res = self._assign(assignMatrix, None)
+        return dict(tau=self._onehot(res["map_state"]), conf=res["conf"], logz=res["logz"], marg=res["marg"])
 
     def calculateSND(self, tau):
         """pairwise single-nucleotide differences between haplotypes (:712-730)."""

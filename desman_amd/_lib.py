@@ -109,6 +109,9 @@ SIGNATURES = {
     "dsm_nmft_objective": (_i, [_vp, C.POINTER(_d)]),
     "dsm_nmft_get_tau": (_i, [_vp, _i64p]),
     "dsm_lrt_step": (_i, [_i, _f64p, _i32p, _i32p, _f64p, _d, _i, _i, _f64p, _f64p, _f64p]),
+    "dsm_assign_tau": (_i, [_i, _i64p, _i, _i, _i, _f64p, _f64p, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+    "dsm_ctx_assign_tau": (_i, [_vp, _f64p, _f64p, _i, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+    "dsm_assign_debug_set_chunk": (_i, [_i]),
     "dsm_genes_create": (_i, [C.POINTER(_vp), _i]),
     "dsm_genes_destroy": (_i, [_vp]),
     "dsm_genes_set_data": (_i, [_vp, _vp, _i, _i, _i, _i32p, _f64p]),
@@ -208,6 +211,45 @@ def lrt_step(ffreq, maxA, maxB, eta, upperP, optimise, p, device=0):
 
 def device_count():
     return load().dsm_device_count()
+
+
+ASSIGN_MAX_G = 10    # DSM_ASSIGN_MAX_G: dsm_assign_tau evaluates all 4^G joint states of a position
+
+
+def _assign_model(gamma, eta, S):
+    gamma = np.ascontiguousarray(gamma, dtype=np.float64)
+    eta = np.ascontiguousarray(eta, dtype=np.float64)
+    if gamma.ndim != 2 or gamma.shape[0] != S or eta.shape != (4, 4):
+        raise ValueError("assign_tau: gamma must be [S=%d, G] and eta [4, 4]; got %s, %s" % (S, gamma.shape, eta.shape))
+    return gamma, eta
+
+
+def _assign_out(N, G, seed):
+    out = dict(map_state=np.zeros((N, G), dtype=np.uint8), conf=np.zeros(N), logz=np.zeros(N), marg=np.zeros((N, G, 4)))
+    if seed is not None:
+        out["draw_state"] = np.zeros((N, G), dtype=np.uint8)
+    return out
+
+
+def assign_tau(counts, gamma, eta, seed=None, device=0):
+    """Exact joint assignment of the positions ``counts`` [N,S,4] under fitted gamma [S,G], eta [4,4] (dsm_assign_tau): a dict of
+    map_state [N,G] uint8, conf [N], logz [N], marg [N,G,4] and -- with a seed -- draw_state [N,G], one posterior draw per
+    position keyed by (seed, position).  G <= ASSIGN_MAX_G."""
+    x = np.ascontiguousarray(counts, dtype=np.int64)
+    if x.ndim != 3 or x.shape[2] != 4:
+        raise ValueError("assign_tau: counts must be [N,S,4]")
+    N, S = x.shape[0], x.shape[1]
+    gamma, eta = _assign_model(gamma, eta, S)
+    G = gamma.shape[1]
+    out = _assign_out(N, G, seed)
+    check(load().dsm_assign_tau(int(device), x, N, S, G, gamma, eta, int(seed or 0) & 0xFFFFFFFFFFFFFFFF, _ptr(out["map_state"]),
+                                _ptr(out["conf"]), _ptr(out["logz"]), _ptr(out["marg"]), _ptr(out.get("draw_state"))))
+    return out
+
+
+def assign_debug_set_chunk(positions=0):
+    """test hook: positions per launch of assign_tau / Context.assign_tau (0 = the default bound); results do not depend on it"""
+    check(load().dsm_assign_debug_set_chunk(int(positions)))
 
 
 def _ptr(a):
@@ -337,6 +379,15 @@ class Context:
 
     def set_tau_rng(self, mode):
         check(self.lib.dsm_ctx_set_tau_rng(self._h, int(mode)))
+
+    def assign_tau(self, gamma, eta, seed=None):
+        """assign_tau() of the module on the count tensor resident in this context (no second upload); the chain state is not touched"""
+        gamma, eta = _assign_model(gamma, eta, self.S)
+        G = gamma.shape[1]
+        out = _assign_out(self.V, G, seed)
+        check(self.lib.dsm_ctx_assign_tau(self._h, gamma, eta, G, int(seed or 0) & 0xFFFFFFFFFFFFFFFF, _ptr(out["map_state"]),
+                                          _ptr(out["conf"]), _ptr(out["logz"]), _ptr(out["marg"]), _ptr(out.get("draw_state"))))
+        return out
 
     # ---- single steps
     def sample_tau(self, want_logp=False):

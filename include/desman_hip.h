@@ -210,6 +210,31 @@ int dsm_lrt_step(int device, const double *ffreq, const int32_t *maxA, const int
                  const double *eta, double upperP, int optimise, int V, double *p_inout,
                  double *MLL, double *BLL);
 
+/* Exact joint haplotype assignment of positions that were not in the fit (desman/HaploSNP_Sampler.py:233-261, assignTau;
+ * bin/desman:209-240).  For each of the N positions ALL 4^G joint states t = (a_0 .. a_{G-1}) are evaluated in fp64 under the
+ * fitted gamma [S][G] and eta [4][4] with a uniform prior over the states:
+ *     L(t) = sum_{s,b} x[s][b] ln sum_g gamma[s][g] eta[a_g][b]     (cells with x = 0 contribute exactly 0),
+ * state index idx(t) = sum_g a_g 4^(G-1-g), the order of the reference's tauStates.  Host pointers:
+ *     map_state [N][G]    argmax_t L(t), ties to the lowest idx
+ *     conf      [N]       posterior of map_state = 1 / sum_t exp(L(t) - L_max)   (the reference's conf)
+ *     logz      [N]       ln sum_t exp L(t)
+ *     marg      [N][G][4] P(a_g = a | x, gamma, eta)
+ *     draw_state[N][G]    (may be NULL) one draw from the posterior: inverse CDF over idx order with one Philox uniform keyed by
+ *                         (seed, position index within the call); the reference's assignTau in law
+ * A position at which no state has positive probability (exact zeros in eta / gamma that contradict its counts) comes back as
+ * map_state = draw_state = 0..0, conf = 0, logz = -inf, marg = 0.  Limits: 1 <= G <= DSM_ASSIGN_MAX_G (4^10 ~ 10^6 states per
+ * position; above: DSM_ERR_UNSUPPORTED), S <= DSM_MAX_S, counts as dsm_ctx_set_counts takes them (DSM_ERR_ARG otherwise; gamma and
+ * eta must be finite and >= 0).  Positions are processed in chunks, device scratch stays below ~40 MB whatever N is.  The results
+ * do not depend on the chunking, on scheduling or on the entry point: dsm_ctx_assign_tau runs the same code on the count tensor
+ * resident in the context (N = its V; the chain state is neither needed nor touched).                                        */
+#define DSM_ASSIGN_MAX_G 10
+int dsm_assign_tau(int device, const int64_t *counts /*[N][S][4]*/, int N, int S, int G, const double *gamma, const double *eta,
+                   uint64_t seed, uint8_t *map_state, double *conf, double *logz, double *marg, uint8_t *draw_state);
+int dsm_ctx_assign_tau(dsm_ctx *ctx, const double *gamma, const double *eta, int G, uint64_t seed, uint8_t *map_state,
+                       double *conf, double *logz, double *marg, uint8_t *draw_state);
+/* test hook: positions per launch of the two calls above (0 = by the scratch bound, the default) */
+int dsm_assign_debug_set_chunk(int positions);
+
 /* ------------------------------------------------------------------------ */
 /* f4: accessory-gene assignment (desman/Eta_Sampler.py, desman/GeneAssign.py) */
 /* C genes, gene c owns the rows gene_off[c]..gene_off[c+1]-1 of one           */
