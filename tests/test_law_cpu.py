@@ -9,14 +9,22 @@ the law of the device draws.  What it is pinned to:
   * the reference's own sampleMu (/root/reference/desman/HaploSNP_Sampler.py:284-309, restated RandomState-exactly in
     oracle/ref_numpy.py and pinned by golden fixtures): two-sample chi-square on every marginal of sum_mu and Esum at
     G = 10 / 12, x 15 depth and a converged state with eta ~ 0.97 I.
+
+Law of the gamma / eta Dirichlet specification (oracle/desman_oracle.c: orc_dirichlet_counter), which the device draw follows to
+1e-13 (tests/test_gpu_parity.py: test_dirichlet_draws_match_spec): the exact JOINT law of every row by stick-breaking
+(tests/_law.py: stick_variables), the clamp, non-default priors, the reference's own RandomState.dirichlet draw -- and a proof
+that the judge rejects the mistakes it is there for.
 """
 import numpy as np
 import pytest
 from scipy import stats as st
 
-from oracle import cbind
+from oracle import cbind, ref_numpy as rn
 
-from _law import (LAW_CASES, assert_same_law, chi2_vs_binom, chi2_vs_pmf, law_case, reference_draws, sum_of_binomials_pmf)
+from _law import (DIRICHLET_CLAMP_CASE, DIRICHLET_LAW_CASES, DIRICHLET_LAW_ESUM, DIRICHLET_LAW_ETA_ITERS, LAW_CASES,
+                  assert_dirichlet_law, assert_same_law, assert_same_sticks, chi2_vs_binom, chi2_vs_pmf, clamp_law_violations,
+                  dirichlet_law_draws, dirichlet_law_violations, eta_law_violations, law_case, reference_draws, stick_breaking,
+                  sum_of_binomials_pmf)
 
 NV = 200000
 
@@ -186,3 +194,131 @@ def test_specification_has_the_law_of_the_reference_sampleMu(name, spec):
     z = (np.mean(mus, axis=0) - e_mu) / np.sqrt(v_mu / n + 1e-12)
     assert np.abs(z).max() < 5.0
     np.testing.assert_allclose(np.mean(es, axis=0), e_E, rtol=0.02, atol=5.0 * np.sqrt(e_E.max() / n) + 0.5)
+
+
+# ---------------------------------------------------------------- gamma / eta Dirichlet draws
+def _spec_draw(alpha, delta, epsilon, seed=99):
+    return lambda it, sum_mu, esum: cbind.dirichlet_counter(sum_mu, esum, seed, it, alpha, delta, epsilon)
+
+
+@pytest.mark.parametrize("name", sorted(DIRICHLET_LAW_CASES))
+def test_dirichlet_spec_has_the_exact_joint_law(name):
+    """orc_dirichlet_counter with the clamp off (epsilon = 0): 6400 rows a case (64 identical rows x 100 iteration counters) against
+    Dir(alpha + sum_mu) by stick-breaking.  Seed 99 gives: smallest Bonferroni-scaled p-value of a case 0.61 (one-huge), smallest
+    single p-value 0.042 (one of the 31 of G32), largest |rho| 0.021 against the bound 0.0625, no value twice."""
+    row, alpha = DIRICHLET_LAW_CASES[name]
+    g, _ = dirichlet_law_draws(_spec_draw(alpha, 0.1, 0.0), row)
+    assert g.shape == (6400, len(row))
+    assert_dirichlet_law(g, alpha + np.asarray(row, dtype=np.float64), name)
+
+
+@pytest.mark.parametrize("delta", [0.1, 2.0])
+def test_dirichlet_spec_eta_rows_follow_the_columns_of_esum(delta):
+    """eta row a ~ Dir(delta + esum[:, a]) exactly, over 6000 iteration counters -- and judged by esum[a, :] the same draws fail"""
+    _, e = dirichlet_law_draws(_spec_draw(0.1, delta, 0.0), [0, 3], iters=DIRICHLET_LAW_ETA_ITERS, S=1)
+    bad = eta_law_violations(e, DIRICHLET_LAW_ESUM, delta)
+    assert not bad, bad
+    assert eta_law_violations(e, DIRICHLET_LAW_ESUM, delta, transposed=True)
+
+
+def test_dirichlet_spec_clamp_has_the_exact_floor_share():
+    """epsilon = 1e-6 on a row with four empty haplotypes next to 1e4 reads: 66.26 % of their draws sit at the floor (|z| <= 1.2 at
+    seed 99), the others follow the Beta truncated at epsilon"""
+    row, alpha, eps = DIRICHLET_CLAMP_CASE
+    a = alpha + np.asarray(row, dtype=np.float64)
+    assert st.beta.cdf(eps, a[0], a.sum() - a[0]) == pytest.approx(0.6626, abs=5e-5)
+    g, _ = dirichlet_law_draws(_spec_draw(alpha, 0.1, eps), row)
+    bad = clamp_law_violations(g, a, eps)
+    assert not bad, bad
+    # the clamp matters: judged as an unclamped Dirichlet the same rows fail
+    assert dirichlet_law_violations(g, a)
+
+
+def test_dirichlet_spec_has_the_law_of_the_reference_at_other_priors():
+    """alpha = 0.5, delta = 2: the stick variables of the spec's rows against those of the reference's own draw
+    (rn.sample_gamma / rn.sample_eta = RandomState.dirichlet, HaploSNP_Sampler.py:263-281), two-sample, and both against theory"""
+    alpha, delta = 0.5, 2.0
+    row = DIRICHLET_LAW_CASES["mixed"][0]
+    S, n_it = 64, 100
+    g, _ = dirichlet_law_draws(_spec_draw(alpha, delta, 0.0, seed=7), row, iters=n_it, S=S)
+    _, e = dirichlet_law_draws(_spec_draw(alpha, delta, 0.0, seed=7), [0, 3], iters=DIRICHLET_LAW_ETA_ITERS, S=1)
+    rs = np.random.RandomState(2)
+    mu = np.zeros((1, S, 1, len(row)), dtype=np.int64); mu[0, :, 0, :] = row
+    E = np.zeros((1, 1, 4, 4), dtype=np.int64); E[0, 0] = DIRICHLET_LAW_ESUM
+    g_ref = np.concatenate([rn.sample_gamma(rs, mu, alpha=alpha, epsilon=0.0) for _ in range(n_it)], axis=0)
+    e_ref = np.array([rn.sample_eta(rs, E, delta=delta) for _ in range(DIRICHLET_LAW_ETA_ITERS)])
+    a = alpha + np.asarray(row, dtype=np.float64)
+    assert_same_sticks(g, g_ref, a, "gamma")
+    assert_dirichlet_law(g, a, "spec"); assert_dirichlet_law(g_ref, a, "reference")
+    for b in range(4):
+        assert_same_sticks(e[:, b, :], e_ref[:, b, :], delta + DIRICHLET_LAW_ESUM[:, b].astype(np.float64), ("eta", b))
+    assert not eta_law_violations(e_ref, DIRICHLET_LAW_ESUM, delta)
+    assert eta_law_violations(e_ref, DIRICHLET_LAW_ESUM, delta, transposed=True)
+
+
+def _mt_rows(rng, a, n, boost_exponent=None, no_boost=False, share_uniform=False):
+    """n rows of a Marsaglia-Tsang style Dirichlet sampler in numpy: Gamma(a + 1) u^(1/a) for a < 1 -- with the named defect"""
+    a = np.asarray(a, dtype=np.float64)
+    small = a < 1.0
+    y = rng.gamma(np.where(small, a + 1.0, a), size=(n, a.size))
+    u = rng.random((n, a.size))
+    if share_uniform:
+        u[:, 1] = u[:, 0]
+    if not no_boost:
+        ex = 1.0 / a if boost_exponent is None else boost_exponent(a)
+        y = np.where(small[None, :], y * u ** ex[None, :], y)
+    return y / y.sum(axis=1, keepdims=True)
+
+
+@pytest.mark.parametrize("name", ["all-empty", "mixed", "G32", "G2", "boundary"])
+def test_dirichlet_law_helper_rejects_wrong_samplers(name):
+    """A law test that cannot reject these is not done: the sound numpy sampler passes; without the boost (Gamma(a + 1) normalised),
+    with the boost exponent 1 / (a + 1), with one uniform shared by the first two variates of a row (the stand-in for a boost
+    uniform reused by the acceptance test), and with two identical rows it is rejected."""
+    row, alpha = DIRICHLET_LAW_CASES[name]
+    a = alpha + np.asarray(row, dtype=np.float64)
+    n = 6400
+    rng = np.random.default_rng(1)
+    sound = _mt_rows(rng, a, n)
+    assert_dirichlet_law(sound, a, name)
+    assert_dirichlet_law(rng.dirichlet(a, size=n), a, name)
+    rng = np.random.default_rng(2)
+    if (a < 1.0).any():
+        assert dirichlet_law_violations(_mt_rows(rng, a, n, no_boost=True), a)
+        assert dirichlet_law_violations(_mt_rows(rng, a, n, boost_exponent=lambda s: 1.0 / (s + 1.0)), a)
+        if (a[:2] < 1.0).all():
+            bad = dirichlet_law_violations(_mt_rows(rng, a, n, share_uniform=True), a)
+            assert bad and (len(a) == 2 or any("rank-correlated" in b for b in bad)), bad
+    sound[4001] = sound[17]                                       # two rows (or lanes, or iterations) on one counter
+    bad = dirichlet_law_violations(sound, a)
+    assert len(bad) == 1 and "repeated" in bad[0], bad
+
+
+def test_dirichlet_law_helper_rejects_transposed_eta_and_a_wrong_clamp():
+    rng = np.random.default_rng(6)
+    es = DIRICHLET_LAW_ESUM.astype(np.float64)
+    n = DIRICHLET_LAW_ETA_ITERS
+    right = np.stack([rng.dirichlet(0.1 + es[:, a], size=n) for a in range(4)], axis=1)
+    wrong = np.stack([rng.dirichlet(0.1 + es[a, :], size=n) for a in range(4)], axis=1)      # E[observed][true] read transposed
+    assert not eta_law_violations(right, es, 0.1)
+    assert eta_law_violations(wrong, es, 0.1)
+    # the clamp check: sound rows pass; a floor of 2 eps, or a clamp without the renormalisation of its neighbours' law, do not
+    row, alpha, eps = DIRICHLET_CLAMP_CASE
+    a = alpha + np.asarray(row, dtype=np.float64)
+    pre = rng.dirichlet(a, size=6400)
+    assert not clamp_law_violations(rn.clamp_renorm_gamma(pre, eps), a, eps)
+    assert clamp_law_violations(rn.clamp_renorm_gamma(pre, 2.0 * eps), a, eps)
+    assert clamp_law_violations(rn.clamp_renorm_gamma(_mt_rows(rng, a, 6400, no_boost=True), eps), a, eps)
+
+
+@pytest.mark.parametrize("alpha,delta", [(0.5, 2.0), (1.0, 1.0), (2.5, 0.3)])
+@pytest.mark.parametrize("V,S,G", [(40, 5, 3), (20, 3, 1), (15, 7, 12)])
+def test_oracle_logpost_under_other_priors_is_the_reference_logPosterior(V, S, G, alpha, delta):
+    """cbind.logpost(..., alpha, delta) -- what the GPU tests hold lp to under non-default priors -- against the restated
+    logPosterior of the reference (HaploSNP_Sampler.py:444-461, Desman_Utils.py:35-44)"""
+    from desman_amd.synth import synth_counts, random_state
+    counts, _, _ = synth_counts(V, S, max(G, 2), seed=V)
+    tau, gamma, eta = random_state(V, S, G, seed=S)
+    lp = cbind.logpost(cbind.onehot_to_idx(tau), gamma, eta, counts, alpha, delta)
+    assert lp == pytest.approx(rn.log_posterior(tau, gamma, eta, counts, alpha, delta), rel=1e-12)
+    assert cbind.logprior(gamma, eta, V, alpha, delta) == pytest.approx(lp - cbind.loglik(cbind.onehot_to_idx(tau), gamma, eta, counts), rel=1e-9)
