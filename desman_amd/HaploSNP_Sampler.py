@@ -252,6 +252,17 @@ class HaploSNP_Sampler:
         res = self._assign(assignMatrix, None)
         return dict(tau=self._onehot(res["map_state"]), conf=res["conf"], logz=res["logz"], marg=res["marg"])
 
+    # ---- samples that were not in the fit (no counterpart upstream)
+    def fitGamma(self, snps=None, tau=None, eta=None, presence=False, max_iter=_lib.FIT_MAX_ITER, tol=_lib.FIT_TOL):
+        """maximum-likelihood abundances with the haplotypes and the error matrix held fixed: a dict of gamma [S',G], loglik, deviance,
+        iters, converged (and lr_absent [S',G] with presence) for the samples of snps [V,S',4] -- default: the chain's own counts, on
+        the resident tensor -- under tau (default tau_star) and eta (default eta_star)"""
+        tau = self.tau_star if tau is None else tau
+        eta = self.eta_star if eta is None else eta
+        if snps is None:
+            return self._ctx.fit_gamma(eta, tau=tau, max_iter=max_iter, tol=tol, presence=presence)
+        return _lib.fit_gamma(snps, tau, eta, max_iter=max_iter, tol=tol, presence=presence, device=self._device)
+
     def calculateSND(self, tau):
         """pairwise single-nucleotide differences between haplotypes (:712-730)."""
         idx = np.argmax(tau, axis=2)

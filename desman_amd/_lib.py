@@ -112,6 +112,9 @@ SIGNATURES = {
     "dsm_assign_tau": (_i, [_i, _i64p, _i, _i, _i, _f64p, _f64p, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "dsm_ctx_assign_tau": (_i, [_vp, _f64p, _f64p, _i, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "dsm_assign_debug_set_chunk": (_i, [_i]),
+    "dsm_fit_gamma": (_i, [_i, _i64p, _i, _i, _i, _i64p, _f64p, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dsm_ctx_fit_gamma": (_i, [_vp, _i, _vp, _f64p, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dsm_abund_debug_set_chunk": (_i, [_i]),
     "dsm_genes_create": (_i, [C.POINTER(_vp), _i]),
     "dsm_genes_destroy": (_i, [_vp]),
     "dsm_genes_set_data": (_i, [_vp, _vp, _i, _i, _i, _i32p, _f64p]),
@@ -252,6 +255,57 @@ def assign_debug_set_chunk(positions=0):
     check(load().dsm_assign_debug_set_chunk(int(positions)))
 
 
+FIT_MAX_ITER, FIT_TOL = 20000, 1.0e-9     # defaults of fit_gamma: plain EM is slow near the boundary
+
+
+def _fit_tau(tau, V):
+    """tau as [V,G] int64 digits, from digits or from the one-hot form [V,G,4]"""
+    t = np.asarray(tau)
+    if t.ndim == 3 and t.shape[2] == 4:
+        t = np.argmax(t, axis=2)
+    t = np.ascontiguousarray(t, dtype=np.int64)
+    if t.ndim != 2 or t.shape[0] != V:
+        raise ValueError("fit_gamma: tau must be [V=%d, G] digits or [V, G, 4] one-hot; got %s" % (V, np.shape(tau)))
+    return t
+
+
+def _fit_eta(eta):
+    eta = np.ascontiguousarray(eta, dtype=np.float64)
+    if eta.shape != (4, 4):
+        raise ValueError("fit_gamma: eta must be [4, 4]; got %s" % (eta.shape,))
+    return eta
+
+
+def _fit_out(S, G, presence):
+    out = dict(gamma=np.zeros((S, G)), loglik=np.zeros(S), deviance=np.zeros(S), iters=np.zeros(S, dtype=np.int32),
+               converged=np.zeros(S, dtype=np.int32))
+    if presence:
+        out["lr_absent"] = np.zeros((S, G))
+    return out
+
+
+def fit_gamma(counts, tau, eta, max_iter=FIT_MAX_ITER, tol=FIT_TOL, presence=False, device=0):
+    """Maximum-likelihood abundances of the haplotypes ``tau`` ([V,G] digits or [V,G,4] one-hot) in the samples of ``counts`` [V,S,4]
+    with tau and eta [4,4] held fixed (dsm_fit_gamma): a dict of gamma [S,G], loglik [S], deviance [S], iters [S], converged [S] and --
+    with ``presence`` -- lr_absent [S,G], the likelihood-ratio statistic of "haplotype g is absent from sample s"."""
+    x = np.ascontiguousarray(counts, dtype=np.int64)
+    if x.ndim != 3 or x.shape[2] != 4:
+        raise ValueError("fit_gamma: counts must be [V,S,4]")
+    V, S = x.shape[0], x.shape[1]
+    t, eta = _fit_tau(tau, V), _fit_eta(eta)
+    G = t.shape[1]
+    out = _fit_out(S, G, presence)
+    check(load().dsm_fit_gamma(int(device), x, V, S, G, t, eta, int(max_iter), float(tol), int(bool(presence)), _ptr(out["gamma"]),
+                               _ptr(out["loglik"]), _ptr(out["deviance"]), _ptr(out["iters"]), _ptr(out["converged"]),
+                               _ptr(out.get("lr_absent"))))
+    return out
+
+
+def abund_debug_set_chunk(samples=0):
+    """test hook: samples per launch of fit_gamma / Context.fit_gamma (0 = the default bound); results do not depend on it"""
+    check(load().dsm_abund_debug_set_chunk(int(samples)))
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data
 
@@ -387,6 +441,18 @@ class Context:
         out = _assign_out(self.V, G, seed)
         check(self.lib.dsm_ctx_assign_tau(self._h, gamma, eta, G, int(seed or 0) & 0xFFFFFFFFFFFFFFFF, _ptr(out["map_state"]),
                                           _ptr(out["conf"]), _ptr(out["logz"]), _ptr(out["marg"]), _ptr(out.get("draw_state"))))
+        return out
+
+    def fit_gamma(self, eta, tau=None, max_iter=FIT_MAX_ITER, tol=FIT_TOL, presence=False):
+        """fit_gamma() of the module for the samples of the count tensor resident in this context (no second upload), with the given
+        tau or -- tau=None -- the context's resident tau; the chain state is not touched"""
+        eta = _fit_eta(eta)
+        t = None if tau is None else _fit_tau(tau, self.V)
+        G = self.G if t is None else t.shape[1]
+        out = _fit_out(self.S, G, presence)
+        check(self.lib.dsm_ctx_fit_gamma(self._h, G, _ptr(t), eta, int(max_iter), float(tol), int(bool(presence)), _ptr(out["gamma"]),
+                                         _ptr(out["loglik"]), _ptr(out["deviance"]), _ptr(out["iters"]), _ptr(out["converged"]),
+                                         _ptr(out.get("lr_absent"))))
         return out
 
     # ---- single steps

@@ -1,0 +1,154 @@
+"""`desman-abund`: abundances of a finished run's haplotypes in samples that were not in the fit.
+
+    python -m desman_amd.abund <run_dir> <table.freq> [-o DIR] [--tau FILE] [--only-new] [--presence] [--max-iter N] [--tol X] [--device N]
+
+`desman` drops every sample whose mean depth is not above -m, and a sample sequenced after the fit has no row in ``Gamma_star.csv``
+either; a refit would give new haplotypes with new labels.  This entry point holds the run's haplotypes and error matrix fixed and
+fits each sample's abundance row by maximum likelihood on the GPU (include/desman_hip.h: dsm_fit_gamma; the reference has no
+counterpart).  It reads ``Eta_star.csv`` and the haplotypes -- ``--tau FILE``, else ``Collated_Tau_star.csv`` (the -r path: every
+position), else ``Filtered_Tau_star.csv`` -- matches the model's positions to the rows of the base-count table by (contig,
+Position) and writes
+
+    Projected_Gamma.csv      layout and sample naming of Gamma_star.csv
+    Projected_fit.csv        per sample: reads, mean depth over the model's positions, loglik, deviance, deviance per read,
+                             iters, converged (0: --max-iter ended the iteration, the row is not the maximum)
+    Projected_presence.csv   with --presence: S x G likelihood-ratio statistics 2 (L - max L with haplotype g absent)
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import pandas as pd
+
+from .Output_Results import rchop
+
+MAX_ITER, TOL = 20000, 1.0e-9          # _lib.FIT_MAX_ITER / FIT_TOL (the parser must not need the library)
+TAU_FILES = ("Collated_Tau_star.csv", "Filtered_Tau_star.csv")
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(prog="desman-abund",
+                                 description="abundances of a finished desman run's haplotypes in further samples (MI355X)")
+    ap.add_argument("run_dir", help="output directory of a finished `desman` run")
+    ap.add_argument("freq_file", help="base-count table with the samples to fit: Contig,Position,<sample>-A,-C,-G,-T,...")
+    ap.add_argument("-o", "--output_dir", type=str, default=None, help="directory for the result files (default: run_dir)")
+    ap.add_argument("--tau", type=str, default=None, help="haplotype table to use instead of the run's Collated / Filtered_Tau_star.csv")
+    ap.add_argument("--only-new", action="store_true", help="fit only the samples without a row in the run's Gamma_star.csv")
+    ap.add_argument("--presence", action="store_true", help="also write the likelihood-ratio statistics of each haplotype's absence")
+    ap.add_argument("--max-iter", type=int, default=MAX_ITER, help="EM steps at most (default %d)" % MAX_ITER)
+    ap.add_argument("--tol", type=float, default=TOL, help="stop when no abundance moves by this much in a step (default %g)" % TOL)
+    ap.add_argument("--device", type=int, default=0, help="GPU ordinal")
+    return ap
+
+
+def tau_path(run_dir, tau=None):
+    """the haplotype table of a run: the one named, else the collated table of a -r run, else the filtered one"""
+    if tau is not None:
+        if not os.path.isfile(tau):
+            sys.exit("desman-abund: can't open '%s'" % tau)
+        return tau
+    for name in TAU_FILES:
+        path = os.path.join(run_dir, name)
+        if os.path.isfile(path):
+            return path
+    sys.exit("desman-abund: can't open '%s'" % os.path.join(run_dir, TAU_FILES[-1]))
+
+
+def load_model(run_dir, tau=None):
+    """(contigs, positions, tau digits [V,G], eta [4,4]) of a run directory; exits with a message naming what is missing"""
+    eta_path = os.path.join(run_dir, "Eta_star.csv")
+    if not os.path.isfile(eta_path):
+        sys.exit("desman-abund: can't open '%s'" % eta_path)
+    eta = pd.read_csv(eta_path, header=0, index_col=0, float_precision="round_trip").to_numpy(dtype=np.float64)
+    if eta.shape != (4, 4):
+        sys.exit("desman-abund: '%s' is not a 4 x 4 table" % eta_path)
+    path = tau_path(run_dir, tau)
+    table = pd.read_csv(path, header=0, index_col=0)
+    cols = [str(c) for c in table.columns.values.tolist()]
+    if not cols or cols[0] != "Position" or (len(cols) - 1) % 4 or len(cols) < 5:
+        sys.exit("desman-abund: '%s' needs a Position column followed by four columns per haplotype" % path)
+    onehot = table.to_numpy()[:, 1:].reshape(len(table), (len(cols) - 1) // 4, 4)
+    if not ((onehot == 0) | (onehot == 1)).all() or not (onehot.sum(axis=2) == 1).all():
+        sys.exit("desman-abund: '%s' is not a one-hot haplotype table" % path)
+    digits = np.ascontiguousarray(np.argmax(onehot, axis=2), dtype=np.int64)
+    return [str(n) for n in table.index.tolist()], table["Position"].to_numpy(), digits, np.ascontiguousarray(eta)
+
+
+def sample_names(table):
+    cols = [str(c) for c in table.columns.values.tolist()]
+    if not cols or cols[0] != "Position" or (len(cols) - 1) % 4 or len(cols) < 5:
+        sys.exit("desman-abund: the count table needs a Position column followed by four columns per sample")
+    return [rchop(cols[1 + 4 * k], "-A") for k in range((len(cols) - 1) // 4)]
+
+
+def match_positions(table, contigs, positions):
+    """row of the count table for every model position, by (contig, Position); a model position the table lacks is an error that
+    names it, rows of the table that are not in the model are ignored (a key that occurs twice: its first row)"""
+    where = {}
+    for r, key in enumerate(zip((str(n) for n in table.index.tolist()), table["Position"].tolist())):
+        where.setdefault(key, r)
+    rows = np.empty(len(contigs), dtype=np.int64)
+    for i, key in enumerate(zip(contigs, (int(p) for p in positions))):
+        if key not in where:
+            sys.exit("desman-abund: position %s,%d of the model is not in the count table" % key)
+        rows[i] = where[key]
+    return rows
+
+
+def fitted_names(run_dir):
+    """sample names with a row in the run's Gamma_star.csv (none if the run has no such file)"""
+    path = os.path.join(run_dir, "Gamma_star.csv")
+    if not os.path.isfile(path):
+        return []
+    return [str(n) for n in pd.read_csv(path, header=0, index_col=0).index.tolist()]
+
+
+def select_counts(table, rows, keep):
+    """counts [V,S',4] int64 of the samples number `keep` at the table rows `rows`"""
+    data = table.to_numpy()[rows, 1:]
+    cube = data.reshape(len(rows), (data.shape[1]) // 4, 4)
+    return np.ascontiguousarray(cube[:, keep, :].astype(np.int64))
+
+
+def write_results(out_dir, names, counts, res):
+    os.makedirs(out_dir, exist_ok=True)
+    pd.DataFrame(res["gamma"], index=names).to_csv(os.path.join(out_dir, "Projected_Gamma.csv"))      # Output_Results._abundance_table
+    reads = counts.sum(axis=(0, 2))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        per_read = np.where(reads > 0, res["deviance"] / np.maximum(reads, 1), 0.0)
+    fit = pd.DataFrame({"reads": reads.astype(np.int64), "mean_depth": reads / float(counts.shape[0]), "loglik": res["loglik"],
+                        "deviance": res["deviance"], "deviance_per_read": per_read, "iters": np.asarray(res["iters"], dtype=np.int64),
+                        "converged": np.asarray(res["converged"], dtype=np.int64)}, index=names)
+    fit.to_csv(os.path.join(out_dir, "Projected_fit.csv"))
+    if "lr_absent" in res:
+        pd.DataFrame(res["lr_absent"], index=names).to_csv(os.path.join(out_dir, "Projected_presence.csv"))
+
+
+def main(argv=None):
+    opts = build_parser().parse_args(argv)
+    contigs, positions, digits, eta = load_model(opts.run_dir, opts.tau)
+    if not os.path.isfile(opts.freq_file):
+        sys.exit("desman-abund: can't open '%s'" % opts.freq_file)
+    table = pd.read_csv(opts.freq_file, header=0, index_col=0)
+    names = sample_names(table)
+    rows = match_positions(table, contigs, positions)
+    keep = list(range(len(names)))
+    if opts.only_new:
+        old = set(fitted_names(opts.run_dir))
+        keep = [k for k in keep if names[k] not in old]
+    if not keep:
+        sys.exit("desman-abund: no sample to fit (--only-new: every sample of the table has a row in Gamma_star.csv)")
+    counts = select_counts(table, rows, keep)
+    from . import _lib                                                      # nothing above needs the library or a GPU
+    res = _lib.fit_gamma(counts, digits, eta, max_iter=opts.max_iter, tol=opts.tol, presence=opts.presence, device=opts.device)
+    write_results(opts.output_dir or opts.run_dir, [names[k] for k in keep], counts, res)
+    n_open = int((np.asarray(res["converged"]) == 0).sum())
+    if n_open:
+        print("desman-abund: %d of %d samples did not converge in %d steps (Projected_fit.csv: converged = 0)"
+              % (n_open, len(keep), opts.max_iter), file=sys.stderr)
+    return res
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,394 @@
+// kernels_abund.hip -- abundances of fitted haplotypes in samples that were not in the fit.
+//
+// With tau [V][G] and eta [4][4] ([true][observed]) held fixed the samples are independent and the log-likelihood of one sample,
+//     L(gamma) = sum_{v,b: x_vb > 0} x_vb ln p_vb,     p_vb = sum_g gamma_g eta[tau_vg][b],
+// is concave in its gamma row.  One EM step from an interior point:
+//     r_g = gamma_g sum_{v,b: x > 0} x_vb eta[tau_vg][b] / p_vb,     gamma'_g = r_g / N,     N = sum x,
+// evaluated through the class sums  c_a = sum_{g: tau_vg = a} gamma_g  (p_vb = sum_a c_a eta[a][b]) and the class weights
+// w_a = sum_b x_vb eta[a][b] / p_vb  (r_g = gamma_g sum_v w_{tau_vg}): 8 G + ~100 fp64 operations per position instead of 4 G per cell.
+// A FIT is a (sample, mask) pair: the full fit (f = 0), or the fit with haplotype f - 1 excluded (gamma_g = 0 from the start,
+// the start uniform over the others), whose maximum gives the likelihood-ratio statistic of "haplotype g is absent".
+//
+// Shape of the work:
+//   * a workgroup is ONE sample and NW of its F = 1 (+ G) fits, one WAVEFRONT per fit (more fits than a workgroup may have wavefronts -- NWMAX = 12 up to
+//     G = 8, 8 up to G = 16, 4 above, by the registers a lane needs --: the fits are cut into ceil(F / NWMAX) groups of equal size, blockIdx.y).  The 64 lanes of a fit stride over the positions; gamma and the G
+//     accumulators of sum_v w_{tau_vg} live in registers (the kernel is instantiated for G padded to 4 / 8 / 16 / 32).
+//   * the sample's counts (int32 x 4) and the packed tau words are staged in LDS in tiles of DSM_ABUND_TILE positions by the whole
+//     workgroup, and every wavefront of the workgroup reads the tile from there: the 1 + G fits of a sample fetch its counts from
+//     memory once per iteration and group, not 1 + G times.  V <= DSM_ABUND_TILE: the tile is loaded once and stays for all iterations.
+//   * the whole EM loop runs in the kernel: the stop test max_g |gamma' - gamma| < tol is a wave-uniform value, a fit that is done
+//     writes its results and idles through the barriers of the tiles until the workgroup's other fits are done too.
+//   * every sum has one order: a lane adds its positions lane, lane + 64, ... in turn, the 64 lane totals meet in the xor butterfly.
+//     Neither depends on the tile, on the other wavefronts of the workgroup or on which samples share a launch, so a sample's numbers
+//     are the same bits with and without the presence fits, for any chunking and from both entry points.
+//   * EM passes take no logarithm; one more pass at the end evaluates L at the gamma that is returned.
+//
+// Degenerate operands: N = 0 -> the start row, loglik 0, iters 0, converged 1.  A cell with x > 0 and p = 0 in any pass (exact zeros in
+// eta that contradict the counts: at the uniform start already) -> gamma row 0, loglik -inf, converged 0.
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "dsm_device.h"
+#include "dsm_host.h"
+#include "log_table.h"
+
+#define DSM_ABUND_TILE 2048          // positions per LDS tile: 32 KB of counts + 16 KB of tau words
+
+struct AbundParams {
+    const int32_t *cnt;         // [n][V][4] sample-major
+    const uint64_t *tau;        // [V] packed, haplotype g at bits 2 g
+    const double *eta;          // [16]
+    const double *log_tab;      // [256][2]
+    int V, G, F, NW, max_iter;
+    double tol;
+    double *gamma;              // [n][G] of the full fit
+    double *ll;                 // [n][F]
+    double *dev;                // [n]
+    int32_t *iters, *conv;      // [n]
+};
+
+// this lane's rows of the staged tile.  KIND 0: N and the saturated log-likelihood; 1: one EM pass (acc_g += w of g's class; bad: a
+// cell with reads and p = 0); 2: L at gam
+template <int GP, int KIND>
+__device__ __forceinline__ void abund_rows(int n, int lane, const int4 *__restrict__ xS, const uint64_t *__restrict__ tS,
+                                           const double *__restrict__ etaS, const double2 *__restrict__ ltab, const double (&gam)[GP],
+                                           double (&acc)[GP], double &o0, double &o1, bool &bad)
+{
+    for (int i = lane; i < n; i += 64) {
+        const int4 xi = xS[i];
+        const int xv[4] = {xi.x, xi.y, xi.z, xi.w};
+        if (KIND == 0) {
+            const double nv = (double)xi.x + (double)xi.y + (double)xi.z + (double)xi.w;       // exact: below 2^33
+            o0 += nv;                                                                          // exact below 2^53
+            const double ln = dsm_log(nv, ltab);
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                if (xv[b] > 0) o1 = fma((double)xv[b], dsm_log((double)xv[b], ltab) - ln, o1);
+            continue;
+        }
+        const uint64_t t = tS[i];
+        double c[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int g = 0; g < GP; ++g) {
+            const int d = (int)(t >> (2 * g)) & 3;
+#pragma unroll
+            for (int a = 0; a < 4; ++a) c[a] += (d == a) ? gam[g] : 0.0;
+        }
+        double q[4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const double pb = fma(c[3], etaS[12 + b], fma(c[2], etaS[8 + b], fma(c[1], etaS[4 + b], c[0] * etaS[b])));
+            const double x = (double)xv[b];
+            if (KIND == 1) {
+                q[b] = 0.0;
+                if (xv[b] > 0) {
+                    if (!(pb > 0.0)) bad = true;
+                    else q[b] = pb >= 0x1p-500 ? fdiv(x, pb) : x / pb;
+                }
+            } else if (xv[b] > 0) o0 = fma(x, dsm_log(pb, ltab), o0);
+        }
+        if (KIND == 1) {
+            double w[4];
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+                w[a] = fma(q[3], etaS[a * 4 + 3], fma(q[2], etaS[a * 4 + 2], fma(q[1], etaS[a * 4 + 1], q[0] * etaS[a * 4])));
+#pragma unroll
+            for (int g = 0; g < GP; ++g) {
+                const int d = (int)(t >> (2 * g)) & 3;
+                acc[g] += d == 0 ? w[0] : d == 1 ? w[1] : d == 2 ? w[2] : w[3];
+            }
+        }
+    }
+}
+
+template <int GP, int NWMAX>
+__global__ __launch_bounds__(NWMAX * 64) void abund_kernel(AbundParams p)
+{
+    __shared__ int4 xS[DSM_ABUND_TILE];
+    __shared__ uint64_t tS[DSM_ABUND_TILE];
+    __shared__ double2 ltab[DSM_LOG_TAB_N];
+    __shared__ double etaS[16];
+    __shared__ int doneS[NWMAX];
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nthr = blockDim.x, nw = nthr >> 6;
+    const int V = p.V, G = p.G, s = blockIdx.x, f = blockIdx.y * p.NW + wave;
+    const int4 *cnt4 = reinterpret_cast<const int4 *>(p.cnt) + (size_t)s * V;
+    const bool resident = V <= DSM_ABUND_TILE;
+    const double NINF = -INFINITY;
+
+    for (int i = threadIdx.x; i < DSM_LOG_TAB_N; i += nthr) ltab[i] = reinterpret_cast<const double2 *>(p.log_tab)[i];
+    if (threadIdx.x < 16) etaS[threadIdx.x] = p.eta[threadIdx.x];
+    auto stage = [&](int t0) {
+        __syncthreads();                                   // the previous tile has been read by every wavefront
+        const int n = min(DSM_ABUND_TILE, V - t0);
+        for (int i = threadIdx.x; i < n; i += nthr) { xS[i] = cnt4[t0 + i]; tS[i] = p.tau[t0 + i]; }
+        __syncthreads();
+    };
+
+    bool done = f >= p.F;                                  // a wavefront without a fit only keeps the barriers
+    const int Ga = f == 0 ? G : G - 1;                     // haplotypes of this fit (F > 1 only with G > 1)
+    double gam[GP], acc[GP];
+#pragma unroll
+    for (int g = 0; g < GP; ++g) { gam[g] = (g < G && g != f - 1) ? 1.0 / (double)Ga : 0.0; acc[g] = 0.0; }
+    int iters = 0, conv = 0;
+    double ll = 0.0, N = 0.0, Lsat = 0.0;
+    bool dead = false;
+
+    // N and the saturated model
+    {
+        double o0 = 0.0, o1 = 0.0; bool bad = false;
+        for (int t0 = 0; t0 < V; t0 += DSM_ABUND_TILE) {
+            if (!resident || t0 == 0) stage(t0);
+            if (!done) abund_rows<GP, 0>(min(DSM_ABUND_TILE, V - t0), lane, xS, tS, etaS, ltab, gam, acc, o0, o1, bad);
+        }
+        N = group_allreduce_sum<64>(o0);
+        Lsat = group_allreduce_sum<64>(o1);
+    }
+    bool finish = !done && N == 0.0;                       // no reads: the start row, L = 0
+    if (finish) conv = 1;
+
+    for (;;) {
+        if (finish) {
+            if (lane == 0) {
+                p.ll[(size_t)s * p.F + f] = dead ? NINF : ll;
+                if (f == 0) {
+                    p.dev[s] = dead ? INFINITY : 2.0 * (Lsat - ll);
+                    p.iters[s] = iters; p.conv[s] = dead ? 0 : conv;
+#pragma unroll
+                    for (int g = 0; g < GP; ++g) if (g < G) p.gamma[(size_t)s * G + g] = dead ? 0.0 : gam[g];
+                }
+            }
+            finish = false; done = true;
+        }
+        // the workgroup goes on until each of its fits is done
+        if (lane == 0) doneS[wave] = done ? 1 : 0;
+        __syncthreads();
+        bool all = true;
+        for (int w = 0; w < nw; ++w) all = all && doneS[w] != 0;
+        if (all) break;
+        __syncthreads();                                   // (V in one tile: no barrier below before doneS is written again)
+
+        const bool last = iters == p.max_iter || conv;     // wave-uniform: the pass that evaluates L at the final gamma
+        double o0 = 0.0, o1 = 0.0; bool bad = false;
+#pragma unroll
+        for (int g = 0; g < GP; ++g) acc[g] = 0.0;
+        for (int t0 = 0; t0 < V; t0 += DSM_ABUND_TILE) {
+            if (!resident) stage(t0);
+            if (done) continue;
+            const int n = min(DSM_ABUND_TILE, V - t0);
+            if (last) abund_rows<GP, 2>(n, lane, xS, tS, etaS, ltab, gam, acc, o0, o1, bad);
+            else abund_rows<GP, 1>(n, lane, xS, tS, etaS, ltab, gam, acc, o0, o1, bad);
+        }
+        if (done) continue;
+        if (last) {
+            ll = group_allreduce_sum<64>(o0);
+            if (!(ll > NINF)) dead = true;                 // (max_iter = 0 on a table the start contradicts; NaN cannot arise: p >= 0)
+            finish = true;
+            continue;
+        }
+        if (__ballot(bad) != 0ull) { dead = true; finish = true; continue; }
+        double delta = 0.0;
+#pragma unroll
+        for (int g = 0; g < GP; ++g) {
+            const double tot = group_allreduce_sum<64>(acc[g]);
+            const double gn = gam[g] > 0.0 ? gam[g] * tot / N : 0.0;
+            delta = fmax(delta, fabs(gn - gam[g]));
+            gam[g] = gn;
+        }
+        ++iters;
+        if (p.tol > 0.0 && delta < p.tol) conv = 1;
+    }
+}
+
+// the resident tensor [V][S][4] -> samples s0 .. s0 + n - 1 as [n][V][4]
+__global__ __launch_bounds__(256) void abund_repack_kernel(const int4 *__restrict__ in, int4 *__restrict__ out, int V, int S, int s0)
+{
+    const int v = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+    if (v < V) out[(size_t)i * V + v] = in[(size_t)v * S + s0 + i];
+}
+
+// ---------------------------------------------------------------- host side
+static int g_abund_chunk = 0;      // dsm_abund_debug_set_chunk: samples per launch (0 = by the scratch bound)
+
+extern "C" int dsm_abund_debug_set_chunk(int samples)
+{
+    if (samples < 0) { dsm_set_error("abund: chunk %d", samples); return DSM_ERR_ARG; }
+    g_abund_chunk = samples;
+    return DSM_OK;
+}
+
+namespace {
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int alloc(size_t n)
+    {
+        hipError_t e = hipMalloc((void **)&p, (n ? n : 1) * sizeof(T));
+        if (e != hipSuccess) { p = nullptr; dsm_set_error("abund: hipMalloc(%zu B) failed: %s", n * sizeof(T), hipGetErrorString(e)); return DSM_ERR_NOMEM; }
+        return DSM_OK;
+    }
+    operator T *() const { return p; }
+};
+}  // namespace
+
+#define ABTRY(x) do { int _r = (x); if (_r != DSM_OK) return _r; } while (0)
+
+template <int GP, int NWMAX>
+static void abund_launch(const AbundParams &q, int n, int groups)
+{
+    hipLaunchKernelGGL((abund_kernel<GP, NWMAX>), dim3((unsigned)n, (unsigned)groups), dim3((unsigned)q.NW * 64u), 0, 0, q);
+}
+
+static int abund_check_model(int V, int G, const double *eta, int max_iter, double tol)
+{
+    if (V < 1 || G < 1 || G > DSM_MAX_G) { dsm_set_error("fit_gamma: V=%d, G=%d (1 <= G <= DSM_MAX_G=%d)", V, G, DSM_MAX_G); return DSM_ERR_ARG; }
+    if (max_iter < 0 || !(tol >= 0.0) || !std::isfinite(tol)) { dsm_set_error("fit_gamma: max_iter=%d, tol=%g", max_iter, tol); return DSM_ERR_ARG; }
+    for (int i = 0; i < 16; ++i)
+        if (!(eta[i] >= 0.0) || !std::isfinite(eta[i])) { dsm_set_error("fit_gamma: eta[%d] is negative or not finite", i); return DSM_ERR_ARG; }
+    return DSM_OK;
+}
+
+// tau digits [V][G] -> packed words; DSM_ERR_ARG on a digit outside 0..3
+static int abund_pack_tau(const int64_t *tau, int V, int G, std::vector<uint64_t> &out)
+{
+    out.assign((size_t)V, 0ull);
+    for (int v = 0; v < V; ++v) {
+        uint64_t t = 0;
+        for (int g = 0; g < G; ++g) {
+            const int64_t d = tau[(size_t)v * G + g];
+            if (d < 0 || d > 3) { dsm_set_error("fit_gamma: tau[%d][%d] = %lld is not a base 0..3", v, g, (long long)d); return DSM_ERR_ARG; }
+            t |= (uint64_t)d << (2 * g);
+        }
+        out[(size_t)v] = t;
+    }
+    return DSM_OK;
+}
+
+// d_cnt: the resident tensor [V][S][4] (context form), or null with h_cnt = the caller's int64 tensor; d_tau: packed words on the device
+static int abund_run(const int32_t *d_cnt, const int64_t *h_cnt, int V, int S, int G, const uint64_t *d_tau, const double *eta,
+                     int max_iter, double tol, int presence, double *gamma, double *loglik, double *deviance, int32_t *iters,
+                     int32_t *converged, double *lr_absent)
+{
+    const int F = (presence && G > 1) ? 1 + G : 1;
+    const int GP = G <= 4 ? 4 : G <= 8 ? 8 : G <= 16 ? 16 : 32, NWMAX = GP <= 8 ? 12 : GP == 16 ? 8 : 4;      // wavefronts a workgroup may have, i.e. a budget of 168 / 256 / 512 vector registers per lane (used: DESIGN.md sec. 8b; no vector spills, no scratch)
+    const int groups = (F + NWMAX - 1) / NWMAX, NW = (F + groups - 1) / groups;
+    // samples per launch: the sample-major copy of the counts stays below 64 MB (one sample's V x 16 B at the least)
+    int NC = (int)std::max<size_t>(1, std::min<size_t>((size_t)1 << 15, ((size_t)64 << 20) / ((size_t)V * 16)));
+    if (g_abund_chunk > 0) NC = g_abund_chunk;
+    NC = std::min(NC, S);
+    DevBuf<int32_t> d_x, d_iters, d_conv; DevBuf<double> d_eta, d_ltab, d_gamma, d_ll, d_dev;
+    ABTRY(d_x.alloc((size_t)NC * V * 4)); ABTRY(d_eta.alloc(16)); ABTRY(d_ltab.alloc(2 * DSM_LOG_TAB_N));
+    ABTRY(d_gamma.alloc((size_t)NC * G)); ABTRY(d_ll.alloc((size_t)NC * F)); ABTRY(d_dev.alloc(NC));
+    ABTRY(d_iters.alloc(NC)); ABTRY(d_conv.alloc(NC));
+    HIP_TRY(hipMemcpy(d_eta, eta, 16 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ltab, dsm_log_table_host, sizeof dsm_log_table_host, hipMemcpyHostToDevice));
+    std::vector<int32_t> x32;
+    std::vector<double> ll((size_t)NC * F);
+    for (int s0 = 0; s0 < S; s0 += NC) {
+        const int n = std::min(NC, S - s0);
+        if (d_cnt) {
+            hipLaunchKernelGGL(abund_repack_kernel, dim3((unsigned)((V + 255) / 256), (unsigned)n), dim3(256), 0, 0,
+                               reinterpret_cast<const int4 *>(d_cnt), reinterpret_cast<int4 *>(d_x.p), V, S, s0);
+            HIP_TRY(hipGetLastError());
+        } else {
+            x32.resize((size_t)n * V * 4);
+            for (int v = 0; v < V; ++v)
+                for (int i = 0; i < n; ++i) {
+                    const int64_t *src = h_cnt + ((size_t)v * S + s0 + i) * 4;
+                    int32_t *dst = x32.data() + ((size_t)i * V + v) * 4;
+                    for (int b = 0; b < 4; ++b) dst[b] = (int32_t)src[b];
+                }
+            HIP_TRY(hipMemcpy(d_x, x32.data(), x32.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        }
+        AbundParams q{d_x, d_tau, d_eta, d_ltab, V, G, F, NW, max_iter, tol, d_gamma, d_ll, d_dev, d_iters, d_conv};
+        switch (GP) {
+        case 4: abund_launch<4, 12>(q, n, groups); break;
+        case 8: abund_launch<8, 12>(q, n, groups); break;
+        case 16: abund_launch<16, 8>(q, n, groups); break;
+        default: abund_launch<32, 4>(q, n, groups); break;
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(gamma + (size_t)s0 * G, d_gamma, (size_t)n * G * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ll.data(), d_ll, (size_t)n * F * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(deviance + s0, d_dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(iters + s0, d_iters, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(converged + s0, d_conv, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int i = 0; i < n; ++i) {
+            const double L = ll[(size_t)i * F];
+            loglik[s0 + i] = L;
+            if (!lr_absent) continue;
+            for (int g = 0; g < G; ++g) {
+                // G = 1: no haplotype is left, the restricted model gives the reads probability 0
+                const double d = F > 1 ? 2.0 * (L - ll[(size_t)i * F + 1 + g]) : INFINITY;
+                lr_absent[(size_t)(s0 + i) * G + g] = d < 0.0 ? 0.0 : d;       // (the restricted maximum cannot lie above: rounding only)
+            }
+        }
+    }
+    return DSM_OK;
+}
+
+static int abund_bind_device(int device)
+{
+    const int nd = dsm_device_count();
+    if (nd <= 0) { dsm_set_error("no HIP device visible"); return DSM_ERR_NODEVICE; }
+    if (device < 0 || device >= nd) { dsm_set_error("device %d out of range (0..%d)", device, nd - 1); return DSM_ERR_ARG; }
+    HIP_TRY(hipSetDevice(device));
+    return DSM_OK;
+}
+
+extern "C" int dsm_fit_gamma(int device, const int64_t *counts, int V, int S, int G, const int64_t *tau, const double *eta,
+                             int max_iter, double tol, int presence, double *gamma, double *loglik, double *deviance,
+                             int32_t *iters, int32_t *converged, double *lr_absent)
+{
+    if (S < 0 || !tau || !eta || (S > 0 && (!counts || !gamma || !loglik || !deviance || !iters || !converged))) {
+        dsm_set_error("fit_gamma: bad arguments");
+        return DSM_ERR_ARG;
+    }
+    ABTRY(abund_check_model(V, G, eta, max_iter, tol));
+    // the count rules of dsm_ctx_set_counts: no negative count, no cell above 2^31 - 1 reads
+    for (size_t i = 0; i < (size_t)V * S; ++i) {
+        int64_t tot = 0;
+        for (int b = 0; b < 4; ++b) {
+            const int64_t x = counts[i * 4 + b];
+            if (x < 0 || x > 2147483647ll) { dsm_set_error("fit_gamma: count %lld at position %zu, sample %zu", (long long)x, i / S, i % S); return DSM_ERR_ARG; }
+            tot += x;
+        }
+        if (tot > 2147483647ll) { dsm_set_error("fit_gamma: depth above 2^31-1 at position %zu, sample %zu", i / S, i % S); return DSM_ERR_ARG; }
+    }
+    std::vector<uint64_t> packed;
+    ABTRY(abund_pack_tau(tau, V, G, packed));
+    if (S == 0) return DSM_OK;
+    ABTRY(abund_bind_device(device));
+    DevBuf<uint64_t> d_tau;
+    ABTRY(d_tau.alloc((size_t)V));
+    HIP_TRY(hipMemcpy(d_tau, packed.data(), (size_t)V * sizeof(uint64_t), hipMemcpyHostToDevice));
+    return abund_run(nullptr, counts, V, S, G, d_tau, eta, max_iter, tol, presence, gamma, loglik, deviance, iters, converged, lr_absent);
+}
+
+extern "C" int dsm_ctx_fit_gamma(dsm_ctx *c, int G, const int64_t *tau, const double *eta, int max_iter, double tol, int presence,
+                                 double *gamma, double *loglik, double *deviance, int32_t *iters, int32_t *converged, double *lr_absent)
+{
+    if (!c) { dsm_set_error("null context"); return DSM_ERR_ARG; }
+    if (!c->cnt_vs) { dsm_set_error("no count tensor: call dsm_ctx_set_counts first"); return DSM_ERR_STATE; }
+    if (!eta || !gamma || !loglik || !deviance || !iters || !converged) { dsm_set_error("ctx_fit_gamma: null pointer"); return DSM_ERR_ARG; }
+    ABTRY(abund_check_model(c->V, G, eta, max_iter, tol));
+    if (!tau && (!c->have_state || c->G != G)) {
+        dsm_set_error("ctx_fit_gamma: no tau given and no resident state of G=%d haplotypes", G);
+        return DSM_ERR_STATE;
+    }
+    std::vector<uint64_t> packed;
+    if (tau) ABTRY(abund_pack_tau(tau, c->V, G, packed));
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));           // the resident tensors are read from the default stream below
+    DevBuf<uint64_t> d_tau;
+    if (tau) {
+        ABTRY(d_tau.alloc((size_t)c->V));
+        HIP_TRY(hipMemcpy(d_tau, packed.data(), (size_t)c->V * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    return abund_run(c->cnt_vs, nullptr, c->V, c->S, G, tau ? d_tau.p : c->tau, eta, max_iter, tol, presence, gamma, loglik, deviance,
+                     iters, converged, lr_absent);
+}

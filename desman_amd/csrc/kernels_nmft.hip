@@ -665,20 +665,7 @@ __device__ unsigned long long nm_dbg[12];
 // as ceil(G / 4) of these per step instead of one padded wide one.
 #define NM_MFMA4(a, b, c) __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0)
 
-// a / b for the operands of the update (positive, far from the ends of the exponent range): hardware reciprocal, one
-// Newton step, one residual correction -- 6 instructions / ~40 issue cycles instead of the 11 / ~80 of the IEEE expansion
-// (no v_div_scale / v_div_fmas / v_div_fixup).  The quotient is within 1 ulp of a / b (faithful, not always correctly
-// rounded); the factors stay within the 1e-7 of the reference goldens after 100 updates that the tests ask for.
-__device__ __forceinline__ double fdiv(double a, double b)
-{
-
-    // v_rcp_f64 is good to ~2^-23; one Newton step makes 2^-46, and the residual correction of the QUOTIENT below is itself a
-    // Newton step on it (its error is the product of r's and q's: 2^-92) -- a second step on r (rounds 2-3) bought nothing
-    double r = __builtin_amdgcn_rcp(b);
-    r = fma(fma(-b, r, 1.0), r, r);
-    const double q = a * r;
-    return fma(fma(-b, q, a), r, q);
-}
+// fdiv (a / b by hardware reciprocal + Newton steps, within 1 ulp): dsm_device.h
 // ... and where the operands ARE at the ends of the exponent range (round 5, found by scripts/dbg/fuzz_nmft.py: a tau row of subnormal start
 // values -- 8e-4 of a Dirichlet(0.01) draw's components are below 1e-308 -- against gamma columns that are as small: R = 5.6e-310, F / R =
 // 8.9e307 in the reference, but v_rcp_f64 of a subnormal is inf and the Newton step makes NaN of it): the operands are brought to within

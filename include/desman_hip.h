@@ -235,6 +235,42 @@ int dsm_ctx_assign_tau(dsm_ctx *ctx, const double *gamma, const double *eta, int
 /* test hook: positions per launch of the two calls above (0 = by the scratch bound, the default) */
 int dsm_assign_debug_set_chunk(int positions);
 
+/* Abundances of the fitted haplotypes in samples that were not in the fit: tau and eta are held fixed, every
+ * sample's gamma row is the maximiser of its own log-likelihood
+ *     L(gamma) = sum_{v,b} x_vb ln sum_g gamma_g eta[tau_vg][b]        (cells with x = 0 contribute exactly 0, as in dsm_assign_tau),
+ * found by EM from the uniform row: gamma'_g = gamma_g / N sum_{v,b: x > 0} x_vb eta[tau_vg][b] / p_vb, N = the sample's reads.  L is
+ * concave in gamma, so the iteration ends in the global maximum; it stops after the step with max_g |gamma' - gamma| < tol or after
+ * max_iter steps (tol = 0: exactly max_iter steps).  The whole loop runs on the device, in fp64.  Host pointers:
+ *     counts    [V][S][4] int64, as dsm_ctx_set_counts takes them (DSM_ERR_ARG otherwise)
+ *     tau       [V][G] int64 DIGITS 0..3 (not the one-hot form; DSM_ERR_ARG on any other value)
+ *     gamma     [S][G]   the estimate
+ *     loglik    [S]      L(gamma) at the estimate
+ *     deviance  [S]      2 (L_sat - L(gamma)),  L_sat = sum x_vb ln(x_vb / n_v),  n_v = sum_b x_vb
+ *     iters     [S]      EM steps taken;  converged [S]  1 if the stop test was met, 0 if max_iter ended the loop
+ *     lr_absent [S][G]   (may be NULL; computed when presence != 0) 2 (L(gamma) - max L with gamma_g forced to 0): the likelihood-ratio
+ *                        statistic of "haplotype g is absent", from G further fits per sample with the same max_iter and tol, each
+ *                        started uniform over the other haplotypes.  >= 0; a negative value (rounding, or a restricted fit ahead of
+ *                        an unconverged full one) is returned as 0.  G = 1: +inf (no haplotype is left).  A restricted model that
+ *                        gives some read probability 0: +inf.  `converged` speaks of the full fit only; a restricted fit that runs
+ *                        into max_iter understates its maximum and so overstates the statistic.
+ * Degenerate operands: a sample without reads (N = 0) -> the uniform row, loglik 0, deviance 0, iters 0, converged 1, lr_absent 0.
+ * A cell with x > 0 whose p is 0 (exact zeros in eta that contradict the counts) -> gamma row 0, loglik -inf, deviance +inf,
+ * iters = the steps taken before it was met, converged 0, lr_absent NaN; the other samples are not affected.  As a rule that is at
+ * the uniform start (iters 0); it can also come later, when under such an eta a gamma_g underflows to 0 (iters > 0).
+ * Limits: 1 <= G <= DSM_MAX_G, V >= 1, max_iter >= 0, tol >= 0 and finite, eta finite and >= 0 (DSM_ERR_ARG otherwise); any S >= 0:
+ * the samples are processed in chunks whose device copy of the counts stays below 64 MB (one sample's V x 16 B at the least).  A
+ * sample's results are the same bits from run to run, for any chunking, with and without `presence`, and from both entry points:
+ * dsm_ctx_fit_gamma fits the S samples of the count tensor resident in the context with the given tau, or -- tau = NULL -- with the
+ * context's resident tau (DSM_ERR_STATE without a resident state of G haplotypes); the chain state is not touched.               */
+int dsm_fit_gamma(int device, const int64_t *counts /*[V][S][4]*/, int V, int S, int G, const int64_t *tau /*[V][G] digits*/,
+                  const double *eta, int max_iter, double tol, int presence, double *gamma, double *loglik, double *deviance,
+                  int32_t *iters, int32_t *converged, double *lr_absent);
+int dsm_ctx_fit_gamma(dsm_ctx *ctx, int G, const int64_t *tau /*[V][G] digits or NULL*/, const double *eta, int max_iter, double tol,
+                      int presence, double *gamma, double *loglik, double *deviance, int32_t *iters, int32_t *converged,
+                      double *lr_absent);
+/* test hook: samples per launch of the two calls above (0 = by the scratch bound, the default) */
+int dsm_abund_debug_set_chunk(int samples);
+
 /* ------------------------------------------------------------------------ */
 /* f4: accessory-gene assignment (desman/Eta_Sampler.py, desman/GeneAssign.py) */
 /* C genes, gene c owns the rows gene_off[c]..gene_off[c+1]-1 of one           */
