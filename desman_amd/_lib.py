@@ -133,6 +133,7 @@ SIGNATURES = {
     "dsm_genes_loglik": (_i, [_vp, _vp]),
     "dsm_genes_get_star": (_i, [_vp, _vp, _vp]),
     "dsm_genes_set_star": (_i, [_vp, _vp, _vp]),
+    "dsm_genes_debug_tile": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_size_t)]),
     "dsm_kl_assign": (_i, [_i, _f64p, _f64p, _f64p, _i, _i, _i, _i, _d, C.POINTER(_i), C.POINTER(_d)]),
     "dsm_ctx_set_timing": (_i, [_vp, _i]),
     "dsm_ctx_get_timing": (_i, [_vp, _vp, _vp]),
@@ -808,3 +809,9 @@ class Genes:
     def set_star(self, eta_star, gene_llstar):
         check(load().dsm_genes_set_star(self._h, _ptr(np.ascontiguousarray(eta_star, dtype=np.int32)),
                                         _ptr(np.ascontiguousarray(gene_llstar, dtype=np.float64))))
+
+    def debug_tile(self):
+        """test hook: (lanes per variant row, samples per lane, lane groups per workgroup, dynamic LDS bytes) of a sweep launch"""
+        lpv, nsl, gpb, lds = _i(0), _i(0), _i(0), C.c_size_t(0)
+        check(load().dsm_genes_debug_tile(self._h, C.byref(lpv), C.byref(nsl), C.byref(gpb), C.byref(lds)))
+        return lpv.value, nsl.value, gpb.value, lds.value

@@ -938,11 +938,24 @@ static GeneSweepParams sweep_params(dsm_genes *gs, const int32_t *d_eta, const u
     return p;
 }
 
+// more than 64 KB of dynamic LDS has to be asked for, once per kernel instantiation
+#define GENE_LDS_ATTR(kernel, bytes)                                                                                           \
+    do {                                                                                                                       \
+        static bool attr_set = false;                                                                                          \
+        if ((bytes) > 64 * 1024 && !attr_set) {                                                                                \
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
+            attr_set = true;                                                                                                   \
+        }                                                                                                                      \
+    } while (0)
+
 template <int LPV, int NSL>
-static void launch_sweep_t(const GeneSweepParams &p, bool sweep, int nb, int ncand, int block, size_t sh, hipStream_t st)
+static int launch_sweep_t(const GeneSweepParams &p, bool sweep, int nb, int ncand, int block, size_t sh, hipStream_t st)
 {
+    GENE_LDS_ATTR((gene_sweep_kernel<LPV, NSL, true>), sh);
+    GENE_LDS_ATTR((gene_sweep_kernel<LPV, NSL, false>), sh);
     if (sweep) hipLaunchKernelGGL((gene_sweep_kernel<LPV, NSL, true>), dim3(nb, ncand), dim3(block), sh, st, p);
     else hipLaunchKernelGGL((gene_sweep_kernel<LPV, NSL, false>), dim3(nb, ncand), dim3(block), sh, st, p);
+    return DSM_OK;
 }
 
 static int launch_sweep(dsm_genes *gs, const GeneSweepParams &p, bool sweep, int ncand)
@@ -954,10 +967,27 @@ static int launch_sweep(dsm_genes *gs, const GeneSweepParams &p, bool sweep, int
     TRY(sweep_geometry(gs, &block, &sh));
     const int gpb = block / gs->LPV, nb = (ntask + gpb - 1) / gpb;
     hipStream_t st = gs->base->stream;
-#define GS_CASE(L, N) if (gs->LPV == L && gs->NSL == N) launch_sweep_t<L, N>(p, sweep, nb, ncand, block, sh, st)
-    GS_CASE(16, 1); GS_CASE(16, 2); GS_CASE(16, 3); GS_CASE(32, 1); GS_CASE(32, 2); GS_CASE(32, 3); GS_CASE(64, 1); GS_CASE(64, 2); GS_CASE(64, 3); GS_CASE(64, 4); GS_CASE(64, 6); GS_CASE(64, 8);
+    // one case per tile pick_tile can return; a tile without a case is an error, not an empty launch
+#define GS_CASE(L, N) if (gs->LPV == L && gs->NSL == N) TRY((launch_sweep_t<L, N>(p, sweep, nb, ncand, block, sh, st))); else
+    GS_CASE(16, 1) GS_CASE(16, 2) GS_CASE(16, 3) GS_CASE(32, 2) GS_CASE(32, 3)
+    GS_CASE(64, 2) GS_CASE(64, 3) GS_CASE(64, 4) GS_CASE(64, 6) GS_CASE(64, 8)
+    { dsm_set_error("gene sweep: no kernel for the tile %d x %d (S=%d)", gs->LPV, gs->NSL, gs->S); return DSM_ERR_UNSUPPORTED; }
 #undef GS_CASE
     HIP_TRY(hipGetLastError());
+    return DSM_OK;
+}
+
+// test hook: what pick_tile and sweep_geometry decided for the resident data and model
+extern "C" int dsm_genes_debug_tile(const dsm_genes *gs, int *lpv, int *nsl, int *groups_per_block, size_t *lds_bytes)
+{
+    if (!gs || !gs->have_data || !gs->have_model) { dsm_set_error("debug_tile: needs set_data and set_model"); return DSM_ERR_ARG; }
+    int block = 0;
+    size_t lds = 0;
+    TRY(sweep_geometry(gs, &block, &lds));
+    if (lpv) *lpv = gs->LPV;
+    if (nsl) *nsl = gs->NSL;
+    if (groups_per_block) *groups_per_block = block / gs->LPV;
+    if (lds_bytes) *lds_bytes = lds;
     return DSM_OK;
 }
 
@@ -1030,6 +1060,8 @@ extern "C" int dsm_genes_nmft_tau(dsm_genes *gs, const int32_t *eta_mask, const 
     const int GM = G <= 4 ? 4 : G <= 8 ? 8 : G <= 16 ? 16 : 32;
     const size_t sh = ((size_t)G * S + GM + 256) * sizeof(double);
     if (sh > 160 * 1024) { dsm_set_error("gamma tile (%zu B) exceeds LDS", sh); return DSM_ERR_UNSUPPORTED; }
+    GENE_LDS_ATTR(gene_nmft_kernel<16>, sh);              // G <= 8 stays below 64 KB at any S
+    GENE_LDS_ATTR(gene_nmft_kernel<32>, sh);
     if (GM == 4) hipLaunchKernelGGL(gene_nmft_kernel<4>, dim3(C), dim3(256), sh, st, p);
     else if (GM == 8) hipLaunchKernelGGL(gene_nmft_kernel<8>, dim3(C), dim3(256), sh, st, p);
     else if (GM == 16) hipLaunchKernelGGL(gene_nmft_kernel<16>, dim3(C), dim3(256), sh, st, p);
@@ -1277,6 +1309,8 @@ extern "C" int dsm_kl_assign(int device, const double *cov, const double *delta,
     const int GM = G <= 4 ? 4 : G <= 8 ? 8 : G <= 16 ? 16 : 32;
     const size_t sh = ((size_t)G * S + GM + 256) * sizeof(double);
     if (sh > 160 * 1024) { dsm_set_error("delta tile (%zu B) exceeds LDS", sh); return DSM_ERR_UNSUPPORTED; }
+    GENE_LDS_ATTR(kl_update_kernel<16>, sh);              // G <= 8 stays below 64 KB at any S
+    GENE_LDS_ATTR(kl_update_kernel<32>, sh);
     auto launch = [&](int upd) {
         if (GM == 4) hipLaunchKernelGGL(kl_update_kernel<4>, dim3(grid), dim3(256), sh, st, p, upd);
         else if (GM == 8) hipLaunchKernelGGL(kl_update_kernel<8>, dim3(grid), dim3(256), sh, st, p, upd);

@@ -333,6 +333,10 @@ int dsm_genes_update(dsm_genes *gs, int n_iter, int reset_star, int32_t *eta_sto
 int dsm_genes_loglik(dsm_genes *gs, double *gene_ll);
 int dsm_genes_get_star(dsm_genes *gs, int32_t *eta_star, double *gene_llstar);
 int dsm_genes_set_star(dsm_genes *gs, const int32_t *eta_star, const double *gene_llstar);
+/* test hook (read only): the sweep tiling chosen for the resident data and model -- lanes per variant row, samples
+ * per lane, lane groups per workgroup, dynamic LDS of a sweep launch.  Valid after set_data and set_model, DSM_ERR_ARG
+ * otherwise; any pointer may be NULL.                                                                                */
+int dsm_genes_debug_tile(const dsm_genes *gs, int *lpv, int *nsl, int *groups_per_block, size_t *lds_bytes);
 
 /* GeneAssign.KLAssign.factorize (GeneAssign.py:85-120): eta [C][G] in/out (start values drawn by
  * the caller), cov [C][S], delta [S][G]; *n_done updates, *div final divergence.               */

@@ -1,47 +1,21 @@
 """Edge shapes of the accessory-gene path against the CPU oracle (which tests/test_oracle_golden.py pins to the
-reference): more than 8 haplotypes (numpy's blocked row sums in maskGamma), more than 64 samples (two samples
-per lane), genes larger than one workgroup pass, three copy-number states, no variants at all, variant
-subsampling + restoreFullVariants."""
+reference): more than 8 haplotypes (numpy's blocked row sums in maskGamma), more than 64 samples (several samples
+per lane; every sweep tiling has its own case in tests/test_gpu_genes_tilings.py), genes larger than one workgroup
+pass, three copy-number states, no variants at all, variant subsampling + restoreFullVariants."""
 import numpy as np
 import pandas as pd
 import pytest
-from scipy.special import gammaln
 
-from desman_amd.synth import synth_genes
+from _genes_util import _case, _device
 
 pytestmark = pytest.mark.gpu
 
 
-def _case(C, S, G, vmax, seed, **kw):
-    d = synth_genes(C, S, G, seed=seed, vmax=vmax, **kw)
-    gamma = np.ascontiguousarray(d['gamma'])
-    delta = np.ascontiguousarray(gamma * d['total_mean'][:, None])
-    off = np.concatenate([[0], np.cumsum(np.bincount(d['gene_of'], minlength=C))]).astype(np.int32)
-    variants = [np.ascontiguousarray(d['counts'][off[c]:off[c + 1]]) for c in range(C)]
-    return dict(d=d, C=C, S=S, G=G, gamma=gamma, delta=delta, delta_gs=np.ascontiguousarray(delta.T), gene_off=off,
-                variants=variants, eps=np.ascontiguousarray(d['epsilon']), cov=np.ascontiguousarray(d['cov']))
-
-
-def _device(k, eta, tau, max_eta):
-    from desman_amd import _lib
-    from oracle import ref_genes as rg
-    dev = _lib.Genes(0)
-    x = k['d']['counts']
-    dev.set_data(x, k['gene_off'], k['cov'])
-    per_v = (gammaln(x.sum(axis=2) + 1.0) - gammaln(x + 1.0).sum(axis=2)).sum(axis=1) if len(x) else np.zeros(0)
-    mult = np.array([per_v[k['gene_off'][c]:k['gene_off'][c + 1]].sum() for c in range(k['C'])])
-    prior = rg.eta_log_prior(max_eta, 0.01)
-    dev.set_model(k['gamma'], k['eps'], k['delta_gs'], max_eta, prior, -gammaln(k['cov'] + 1.0).sum(axis=1), mult)
-    dev.set_state(eta.astype(np.int32), tau)
-    dev.seed(3)
-    return dev, prior
-
-
 @pytest.mark.parametrize("C,S,G,vmax,max_eta,kw", [
-    (10, 70, 9, 40, 3, dict(mean_lo=0.5, mean_hi=3.0)),      # blocked row sums, 2 samples / lane, multi-workgroup genes
-    (6, 5, 2, 3, 2, dict(mean_lo=0.3, mean_hi=1.5)),         # 16-lane groups
-    (8, 24, 5, 90, 2, dict(mean_lo=1.0, mean_hi=4.0)),       # 32-lane groups, a gene of > 64 variants
-    (4, 130, 12, 6, 2, dict(mean_lo=0.5, mean_hi=2.0)),      # 3 samples / lane
+    (10, 70, 9, 40, 3, dict(mean_lo=0.5, mean_hi=3.0)),      # blocked row sums, 32 lanes x 3 samples, multi-workgroup genes
+    (6, 5, 2, 3, 2, dict(mean_lo=0.3, mean_hi=1.5)),         # 16 lanes x 1 sample
+    (8, 24, 5, 90, 2, dict(mean_lo=1.0, mean_hi=4.0)),       # 16 lanes x 2 samples, a gene of > 64 variants
+    (4, 130, 12, 6, 2, dict(mean_lo=0.5, mean_hi=2.0)),      # 64 lanes x 3 samples
 ])
 def test_batched_update_edge_shapes(C, S, G, vmax, max_eta, kw):
     from oracle import ref_genes as rg
