@@ -263,6 +263,19 @@ class HaploSNP_Sampler:
             return self._ctx.fit_gamma(eta, tau=tau, max_iter=max_iter, tol=tol, presence=presence)
         return _lib.fit_gamma(snps, tau, eta, max_iter=max_iter, tol=tol, presence=presence, device=self._device)
 
+    def fitGammaInterval(self, level=0.95, snps=None, tau=None, eta=None, max_iter=_lib.FIT_MAX_ITER, tol=_lib.FIT_TOL, ctol=_lib.FIT_CTOL):
+        """fitGamma() and the profile-likelihood intervals of its abundances at confidence ``level``: fitGamma's dict with lo [S',G],
+        hi [S',G] and flags [S',G] added (_lib.fit_gamma_interval)"""
+        tau = self.tau_star if tau is None else tau
+        eta = self.eta_star if eta is None else eta
+        res = self.fitGamma(snps=snps, tau=tau, eta=eta, max_iter=max_iter, tol=tol)
+        kw = dict(level=level, max_iter=max_iter, tol=tol, ctol=ctol)
+        if snps is None:
+            res.update(self._ctx.fit_gamma_interval(eta, res["gamma"], tau=tau, **kw))
+        else:
+            res.update(_lib.fit_gamma_interval(snps, tau, eta, res["gamma"], device=self._device, **kw))
+        return res
+
     def calculateSND(self, tau):
         """pairwise single-nucleotide differences between haplotypes (:712-730)."""
         idx = np.argmax(tau, axis=2)

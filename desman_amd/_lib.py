@@ -115,6 +115,8 @@ SIGNATURES = {
     "dsm_fit_gamma": (_i, [_i, _i64p, _i, _i, _i, _i64p, _f64p, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dsm_ctx_fit_gamma": (_i, [_vp, _i, _vp, _f64p, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dsm_abund_debug_set_chunk": (_i, [_i]),
+    "dsm_fit_gamma_interval": (_i, [_i, _i64p, _i, _i, _i, _i64p, _f64p, _f64p, _d, _i, _d, _d, _vp, _vp, _vp]),
+    "dsm_ctx_fit_gamma_interval": (_i, [_vp, _i, _vp, _f64p, _f64p, _d, _i, _d, _d, _vp, _vp, _vp]),
     "dsm_genes_create": (_i, [C.POINTER(_vp), _i]),
     "dsm_genes_destroy": (_i, [_vp]),
     "dsm_genes_set_data": (_i, [_vp, _vp, _i, _i, _i, _i32p, _f64p]),
@@ -303,8 +305,45 @@ def fit_gamma(counts, tau, eta, max_iter=FIT_MAX_ITER, tol=FIT_TOL, presence=Fal
 
 
 def abund_debug_set_chunk(samples=0):
-    """test hook: samples per launch of fit_gamma / Context.fit_gamma (0 = the default bound); results do not depend on it"""
+    """test hook: samples per launch of fit_gamma / fit_gamma_interval and their Context forms (0 = the default bound); results do
+    not depend on it"""
     check(load().dsm_abund_debug_set_chunk(int(samples)))
+
+
+FIT_CTOL = 1.0e-6                         # default bracket width at which an interval search stops
+
+
+def chi2_quantile(level):
+    """the chi-square (1 d.o.f.) quantile of a confidence level in (0, 1): the square of the normal quantile at (1 + level) / 2"""
+    from statistics import NormalDist
+    level = float(level)
+    if not 0.0 < level < 1.0:
+        raise ValueError("interval level must lie in (0, 1); got %r" % level)
+    return NormalDist().inv_cdf(0.5 * (1.0 + level)) ** 2
+
+
+def _interval_args(gamma_hat, S, G, level, q):
+    g = np.ascontiguousarray(gamma_hat, dtype=np.float64)
+    if g.shape != (S, G):
+        raise ValueError("fit_gamma_interval: gamma_hat must be [S=%d, G=%d]; got %s" % (S, G, g.shape))
+    out = dict(lo=np.zeros((S, G)), hi=np.zeros((S, G)), flags=np.zeros((S, G), dtype=np.int32))
+    return g, float(chi2_quantile(level) if q is None else q), out
+
+
+def fit_gamma_interval(counts, tau, eta, gamma_hat, level=0.95, q=None, max_iter=FIT_MAX_ITER, tol=FIT_TOL, ctol=FIT_CTOL, device=0):
+    """Profile-likelihood intervals of the abundances ``gamma_hat`` [S,G] that fit_gamma returned for the same counts, tau and eta
+    (dsm_fit_gamma_interval): a dict of lo [S,G], hi [S,G] and flags [S,G] (bit 1: lo is the boundary 0, 2: hi is the boundary 1, 4: an
+    inner fit ended at max_iter, the interval is too narrow).  ``level`` is the confidence level; ``q`` overrides its chi-square quantile."""
+    x = np.ascontiguousarray(counts, dtype=np.int64)
+    if x.ndim != 3 or x.shape[2] != 4:
+        raise ValueError("fit_gamma_interval: counts must be [V,S,4]")
+    V, S = x.shape[0], x.shape[1]
+    t, eta = _fit_tau(tau, V), _fit_eta(eta)
+    G = t.shape[1]
+    g, q, out = _interval_args(gamma_hat, S, G, level, q)
+    check(load().dsm_fit_gamma_interval(int(device), x, V, S, G, t, eta, g, q, int(max_iter), float(tol), float(ctol), _ptr(out["lo"]),
+                                        _ptr(out["hi"]), _ptr(out["flags"])))
+    return out
 
 
 def _ptr(a):
@@ -454,6 +493,16 @@ class Context:
         check(self.lib.dsm_ctx_fit_gamma(self._h, G, _ptr(t), eta, int(max_iter), float(tol), int(bool(presence)), _ptr(out["gamma"]),
                                          _ptr(out["loglik"]), _ptr(out["deviance"]), _ptr(out["iters"]), _ptr(out["converged"]),
                                          _ptr(out.get("lr_absent"))))
+        return out
+
+    def fit_gamma_interval(self, eta, gamma_hat, tau=None, level=0.95, q=None, max_iter=FIT_MAX_ITER, tol=FIT_TOL, ctol=FIT_CTOL):
+        """fit_gamma_interval() of the module for the samples of the resident count tensor, with the given tau or the resident one"""
+        eta = _fit_eta(eta)
+        t = None if tau is None else _fit_tau(tau, self.V)
+        G = self.G if t is None else t.shape[1]
+        g, q, out = _interval_args(gamma_hat, self.S, G, level, q)
+        check(self.lib.dsm_ctx_fit_gamma_interval(self._h, G, _ptr(t), eta, g, q, int(max_iter), float(tol), float(ctol), _ptr(out["lo"]),
+                                                  _ptr(out["hi"]), _ptr(out["flags"])))
         return out
 
     # ---- single steps

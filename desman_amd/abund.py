@@ -1,6 +1,7 @@
 """`desman-abund`: abundances of a finished run's haplotypes in samples that were not in the fit.
 
-    python -m desman_amd.abund <run_dir> <table.freq> [-o DIR] [--tau FILE] [--only-new] [--presence] [--max-iter N] [--tol X] [--device N]
+    python -m desman_amd.abund <run_dir> <table.freq> [-o DIR] [--tau FILE] [--only-new] [--presence] [--interval [LEVEL]] [--ctol X]
+                                                      [--max-iter N] [--tol X] [--device N]
 
 `desman` drops every sample whose mean depth is not above -m, and a sample sequenced after the fit has no row in ``Gamma_star.csv``
 either; a refit would give new haplotypes with new labels.  This entry point holds the run's haplotypes and error matrix fixed and
@@ -13,6 +14,10 @@ Position) and writes
     Projected_fit.csv        per sample: reads, mean depth over the model's positions, loglik, deviance, deviance per read,
                              iters, converged (0: --max-iter ended the iteration, the row is not the maximum)
     Projected_presence.csv   with --presence: S x G likelihood-ratio statistics 2 (L - max L with haplotype g absent)
+    Projected_interval.csv   with --interval [LEVEL] (default 0.95): per sample and haplotype <g>_lo, <g>_hi, <g>_flag -- the
+                             profile-likelihood interval of the abundance in Projected_Gamma.csv (dsm_fit_gamma_interval; each end
+                             found to --ctol) and its flag bits: 1 lo is the boundary 0, 2 hi is the boundary 1, 4 an inner fit
+                             ended at --max-iter (the interval is too narrow)
 """
 import argparse
 import os
@@ -23,7 +28,7 @@ import pandas as pd
 
 from .Output_Results import rchop
 
-MAX_ITER, TOL = 20000, 1.0e-9          # _lib.FIT_MAX_ITER / FIT_TOL (the parser must not need the library)
+MAX_ITER, TOL, CTOL = 20000, 1.0e-9, 1.0e-6          # _lib.FIT_MAX_ITER / FIT_TOL / FIT_CTOL (the parser must not need the library)
 TAU_FILES = ("Collated_Tau_star.csv", "Filtered_Tau_star.csv")
 
 
@@ -36,6 +41,9 @@ def build_parser():
     ap.add_argument("--tau", type=str, default=None, help="haplotype table to use instead of the run's Collated / Filtered_Tau_star.csv")
     ap.add_argument("--only-new", action="store_true", help="fit only the samples without a row in the run's Gamma_star.csv")
     ap.add_argument("--presence", action="store_true", help="also write the likelihood-ratio statistics of each haplotype's absence")
+    ap.add_argument("--interval", type=float, nargs="?", const=0.95, default=None, metavar="LEVEL",
+                    help="also write the profile-likelihood intervals of the abundances at this confidence level (default 0.95)")
+    ap.add_argument("--ctol", type=float, default=CTOL, help="width to which an interval end is found (default %g)" % CTOL)
     ap.add_argument("--max-iter", type=int, default=MAX_ITER, help="EM steps at most (default %d)" % MAX_ITER)
     ap.add_argument("--tol", type=float, default=TOL, help="stop when no abundance moves by this much in a step (default %g)" % TOL)
     ap.add_argument("--device", type=int, default=0, help="GPU ordinal")
@@ -125,8 +133,20 @@ def write_results(out_dir, names, counts, res):
         pd.DataFrame(res["lr_absent"], index=names).to_csv(os.path.join(out_dir, "Projected_presence.csv"))
 
 
+def write_interval(out_dir, names, iv):
+    """Projected_interval.csv: rows and haplotype names of Projected_Gamma.csv, three columns per haplotype"""
+    cols = {}
+    for g in range(iv["lo"].shape[1]):
+        cols["%d_lo" % g] = iv["lo"][:, g]
+        cols["%d_hi" % g] = iv["hi"][:, g]
+        cols["%d_flag" % g] = np.asarray(iv["flags"][:, g], dtype=np.int64)
+    pd.DataFrame(cols, index=names).to_csv(os.path.join(out_dir, "Projected_interval.csv"))
+
+
 def main(argv=None):
     opts = build_parser().parse_args(argv)
+    if opts.interval is not None and not 0.0 < opts.interval < 1.0:
+        sys.exit("desman-abund: --interval needs a level between 0 and 1")
     contigs, positions, digits, eta = load_model(opts.run_dir, opts.tau)
     if not os.path.isfile(opts.freq_file):
         sys.exit("desman-abund: can't open '%s'" % opts.freq_file)
@@ -147,6 +167,15 @@ def main(argv=None):
     if n_open:
         print("desman-abund: %d of %d samples did not converge in %d steps (Projected_fit.csv: converged = 0)"
               % (n_open, len(keep), opts.max_iter), file=sys.stderr)
+    if opts.interval is not None:
+        iv = _lib.fit_gamma_interval(counts, digits, eta, res["gamma"], level=opts.interval, max_iter=opts.max_iter, tol=opts.tol,
+                                     ctol=opts.ctol, device=opts.device)
+        write_interval(opts.output_dir or opts.run_dir, [names[k] for k in keep], iv)
+        short = [names[k] for i, k in enumerate(keep) if (np.asarray(iv["flags"][i]) & 4).any()]
+        if short:
+            print("desman-abund: an inner fit of %d of %d samples ended at --max-iter %d, their intervals are too narrow "
+                  "(Projected_interval.csv: flag bit 4): %s" % (len(short), len(keep), opts.max_iter, ", ".join(short)), file=sys.stderr)
+        res.update(iv)
     return res
 
 

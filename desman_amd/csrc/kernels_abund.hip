@@ -252,6 +252,21 @@ static int abund_check_model(int V, int G, const double *eta, int max_iter, doub
     return DSM_OK;
 }
 
+// the count rules of dsm_ctx_set_counts: no negative count, no cell above 2^31 - 1 reads
+static int abund_check_counts(const int64_t *counts, int V, int S)
+{
+    for (size_t i = 0; i < (size_t)V * S; ++i) {
+        int64_t tot = 0;
+        for (int b = 0; b < 4; ++b) {
+            const int64_t x = counts[i * 4 + b];
+            if (x < 0 || x > 2147483647ll) { dsm_set_error("fit_gamma: count %lld at position %zu, sample %zu", (long long)x, i / S, i % S); return DSM_ERR_ARG; }
+            tot += x;
+        }
+        if (tot > 2147483647ll) { dsm_set_error("fit_gamma: depth above 2^31-1 at position %zu, sample %zu", i / S, i % S); return DSM_ERR_ARG; }
+    }
+    return DSM_OK;
+}
+
 // tau digits [V][G] -> packed words; DSM_ERR_ARG on a digit outside 0..3
 static int abund_pack_tau(const int64_t *tau, int V, int G, std::vector<uint64_t> &out)
 {
@@ -268,6 +283,34 @@ static int abund_pack_tau(const int64_t *tau, int V, int G, std::vector<uint64_t
     return DSM_OK;
 }
 
+// samples s0 .. s0 + n - 1 sample-major in d_x: from the resident tensor d_cnt [V][S][4], or -- d_cnt null -- from the caller's int64 tensor
+static int abund_stage_chunk(const int32_t *d_cnt, const int64_t *h_cnt, int V, int S, int s0, int n, int32_t *d_x, std::vector<int32_t> &x32)
+{
+    if (d_cnt) {
+        hipLaunchKernelGGL(abund_repack_kernel, dim3((unsigned)((V + 255) / 256), (unsigned)n), dim3(256), 0, 0,
+                           reinterpret_cast<const int4 *>(d_cnt), reinterpret_cast<int4 *>(d_x), V, S, s0);
+        HIP_TRY(hipGetLastError());
+        return DSM_OK;
+    }
+    x32.resize((size_t)n * V * 4);
+    for (int v = 0; v < V; ++v)
+        for (int i = 0; i < n; ++i) {
+            const int64_t *src = h_cnt + ((size_t)v * S + s0 + i) * 4;
+            int32_t *dst = x32.data() + ((size_t)i * V + v) * 4;
+            for (int b = 0; b < 4; ++b) dst[b] = (int32_t)src[b];
+        }
+    HIP_TRY(hipMemcpy(d_x, x32.data(), x32.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    return DSM_OK;
+}
+
+// samples per launch: the sample-major copy of the counts stays below 64 MB (one sample's V x 16 B at the least)
+static int abund_chunk(int V, int S)
+{
+    int NC = (int)std::max<size_t>(1, std::min<size_t>((size_t)1 << 15, ((size_t)64 << 20) / ((size_t)V * 16)));
+    if (g_abund_chunk > 0) NC = g_abund_chunk;
+    return std::min(NC, S);
+}
+
 // d_cnt: the resident tensor [V][S][4] (context form), or null with h_cnt = the caller's int64 tensor; d_tau: packed words on the device
 static int abund_run(const int32_t *d_cnt, const int64_t *h_cnt, int V, int S, int G, const uint64_t *d_tau, const double *eta,
                      int max_iter, double tol, int presence, double *gamma, double *loglik, double *deviance, int32_t *iters,
@@ -276,10 +319,7 @@ static int abund_run(const int32_t *d_cnt, const int64_t *h_cnt, int V, int S, i
     const int F = (presence && G > 1) ? 1 + G : 1;
     const int GP = G <= 4 ? 4 : G <= 8 ? 8 : G <= 16 ? 16 : 32, NWMAX = GP <= 8 ? 12 : GP == 16 ? 8 : 4;      // wavefronts a workgroup may have, i.e. a budget of 168 / 256 / 512 vector registers per lane (used: DESIGN.md sec. 8b; no vector spills, no scratch)
     const int groups = (F + NWMAX - 1) / NWMAX, NW = (F + groups - 1) / groups;
-    // samples per launch: the sample-major copy of the counts stays below 64 MB (one sample's V x 16 B at the least)
-    int NC = (int)std::max<size_t>(1, std::min<size_t>((size_t)1 << 15, ((size_t)64 << 20) / ((size_t)V * 16)));
-    if (g_abund_chunk > 0) NC = g_abund_chunk;
-    NC = std::min(NC, S);
+    const int NC = abund_chunk(V, S);
     DevBuf<int32_t> d_x, d_iters, d_conv; DevBuf<double> d_eta, d_ltab, d_gamma, d_ll, d_dev;
     ABTRY(d_x.alloc((size_t)NC * V * 4)); ABTRY(d_eta.alloc(16)); ABTRY(d_ltab.alloc(2 * DSM_LOG_TAB_N));
     ABTRY(d_gamma.alloc((size_t)NC * G)); ABTRY(d_ll.alloc((size_t)NC * F)); ABTRY(d_dev.alloc(NC));
@@ -290,20 +330,7 @@ static int abund_run(const int32_t *d_cnt, const int64_t *h_cnt, int V, int S, i
     std::vector<double> ll((size_t)NC * F);
     for (int s0 = 0; s0 < S; s0 += NC) {
         const int n = std::min(NC, S - s0);
-        if (d_cnt) {
-            hipLaunchKernelGGL(abund_repack_kernel, dim3((unsigned)((V + 255) / 256), (unsigned)n), dim3(256), 0, 0,
-                               reinterpret_cast<const int4 *>(d_cnt), reinterpret_cast<int4 *>(d_x.p), V, S, s0);
-            HIP_TRY(hipGetLastError());
-        } else {
-            x32.resize((size_t)n * V * 4);
-            for (int v = 0; v < V; ++v)
-                for (int i = 0; i < n; ++i) {
-                    const int64_t *src = h_cnt + ((size_t)v * S + s0 + i) * 4;
-                    int32_t *dst = x32.data() + ((size_t)i * V + v) * 4;
-                    for (int b = 0; b < 4; ++b) dst[b] = (int32_t)src[b];
-                }
-            HIP_TRY(hipMemcpy(d_x, x32.data(), x32.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
+        ABTRY(abund_stage_chunk(d_cnt, h_cnt, V, S, s0, n, d_x, x32));
         AbundParams q{d_x, d_tau, d_eta, d_ltab, V, G, F, NW, max_iter, tol, d_gamma, d_ll, d_dev, d_iters, d_conv};
         switch (GP) {
         case 4: abund_launch<4, 12>(q, n, groups); break;
@@ -349,16 +376,7 @@ extern "C" int dsm_fit_gamma(int device, const int64_t *counts, int V, int S, in
         return DSM_ERR_ARG;
     }
     ABTRY(abund_check_model(V, G, eta, max_iter, tol));
-    // the count rules of dsm_ctx_set_counts: no negative count, no cell above 2^31 - 1 reads
-    for (size_t i = 0; i < (size_t)V * S; ++i) {
-        int64_t tot = 0;
-        for (int b = 0; b < 4; ++b) {
-            const int64_t x = counts[i * 4 + b];
-            if (x < 0 || x > 2147483647ll) { dsm_set_error("fit_gamma: count %lld at position %zu, sample %zu", (long long)x, i / S, i % S); return DSM_ERR_ARG; }
-            tot += x;
-        }
-        if (tot > 2147483647ll) { dsm_set_error("fit_gamma: depth above 2^31-1 at position %zu, sample %zu", i / S, i % S); return DSM_ERR_ARG; }
-    }
+    ABTRY(abund_check_counts(counts, V, S));
     std::vector<uint64_t> packed;
     ABTRY(abund_pack_tau(tau, V, G, packed));
     if (S == 0) return DSM_OK;
@@ -391,4 +409,290 @@ extern "C" int dsm_ctx_fit_gamma(dsm_ctx *c, int G, const int64_t *tau, const do
     }
     return abund_run(c->cnt_vs, nullptr, c->V, c->S, G, tau ? d_tau.p : c->tau, eta, max_iter, tol, presence, gamma, loglik, deviance,
                      iters, converged, lr_absent);
+}
+
+// ---------------------------------------------------------------- profile-likelihood intervals of the abundances
+// For haplotype g the profile log-likelihood  l_g(c) = max { L(gamma) : gamma_g = c, gamma_h >= 0, sum gamma = 1 }  is concave in c; the
+// interval is { c : 2 (L(gamma_hat) - l_g(c)) <= q }.  A SEARCH is a (haplotype, side) pair, k = 2 g + side (0: lower end, 1: upper end):
+// a bisection on c whose every trial is an inner fit -- EM over the other haplotypes with gamma_g held at c,
+//     r_h = gamma_h sum_v w_{tau_vh},     gamma'_h = (1 - c) r_h / sum_{h != g} r_h      (the sum in index order),
+// stopped as the fit is, followed by one pass that evaluates L.  The exact rules (bracket, endpoint test, start of an inner fit, what
+// counts as outside) are in include/desman_hip.h and restated in tests/_abund_interval_ref.py.
+//
+// Shape of the work: that of abund_kernel, with a search where it has a fit -- a workgroup is one sample and NW of its 2 G searches, one
+// wavefront per search, which runs its whole bisection here (fit, evaluate, halve, refit); the tiles, their barriers and the order of
+// every sum are the fit's (abund_rows<GP, 1> and <GP, 2> are called, not copied).  The number of passes a search needs is wave-uniform
+// and differs between the searches of a workgroup: a search that is done idles through the tile barriers until the others are.
+// The held haplotype takes part in every pass with gamma_g = c (the class sums need it) and is never updated: its accumulator is
+// formed like the others and ignored.  The search state (c, the bracket, L(gamma_hat), counters) is wave-uniform.
+struct AbundIvParams {
+    const int32_t *cnt;         // [n][V][4] sample-major
+    const uint64_t *tau;        // [V] packed
+    const double *eta;          // [16]
+    const double *log_tab;      // [256][2]
+    const double *ghat;         // [n][G] the fitted rows
+    int V, G, NW, max_iter;
+    double tol, ctol, q;
+    double *res;                // [n][2 G] the end that search k found
+    int32_t *fl;                // [n][2 G] its flag bits
+};
+
+template <int GP, int NWMAX>
+__global__ __launch_bounds__(NWMAX * 64) void abund_interval_kernel(AbundIvParams p)
+{
+    __shared__ int4 xS[DSM_ABUND_TILE];
+    __shared__ uint64_t tS[DSM_ABUND_TILE];
+    __shared__ double2 ltab[DSM_LOG_TAB_N];
+    __shared__ double etaS[16];
+    __shared__ int doneS[NWMAX];
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nthr = blockDim.x, nw = nthr >> 6;
+    const int V = p.V, G = p.G, s = blockIdx.x, k = blockIdx.y * p.NW + wave, g = k >> 1, side = k & 1;
+    const int4 *cnt4 = reinterpret_cast<const int4 *>(p.cnt) + (size_t)s * V;
+    const double *ghat = p.ghat + (size_t)s * G;
+    const bool resident = V <= DSM_ABUND_TILE;
+    const double NINF = -INFINITY;
+
+    for (int i = threadIdx.x; i < DSM_LOG_TAB_N; i += nthr) ltab[i] = reinterpret_cast<const double2 *>(p.log_tab)[i];
+    if (threadIdx.x < 16) etaS[threadIdx.x] = p.eta[threadIdx.x];
+    auto stage = [&](int t0) {
+        __syncthreads();                                   // the previous tile has been read by every wavefront
+        const int n = min(DSM_ABUND_TILE, V - t0);
+        for (int i = threadIdx.x; i < n; i += nthr) { xS[i] = cnt4[t0 + i]; tS[i] = p.tau[t0 + i]; }
+        __syncthreads();
+    };
+
+    bool done = k >= 2 * G;                                // a wavefront without a search only keeps the barriers
+    double gam[GP], acc[GP];
+    double sumhat = 0.0;
+#pragma unroll
+    for (int h = 0; h < GP; ++h) { gam[h] = h < G ? ghat[h] : 0.0; acc[h] = 0.0; sumhat += gam[h]; }
+
+    enum { M_LHAT, M_EM, M_EVAL };                          // the pass in flight: L(gamma_hat), an EM step, l at the end of an inner fit
+    int mode = M_LHAT, iters = 0, conv = 0, flags = 0;
+    double c = 0.0, b_in = 0.0, b_out = 0.0, Lhat = 0.0, result = 0.0, N = 0.0;
+    bool endpoint = false, finish = false;
+
+    {
+        double o0 = 0.0, o1 = 0.0; bool bad = false;
+        for (int t0 = 0; t0 < V; t0 += DSM_ABUND_TILE) {
+            if (!resident || t0 == 0) stage(t0);
+            if (!done) abund_rows<GP, 0>(min(DSM_ABUND_TILE, V - t0), lane, xS, tS, etaS, ltab, gam, acc, o0, o1, bad);
+        }
+        N = group_allreduce_sum<64>(o0);
+    }
+    if (!done) {
+        if (!(sumhat > 0.0)) { result = NAN; finish = true; }                                      // a dead row of the fit
+        else if (G == 1) { result = 1.0; flags = side ? 2 : 0; finish = true; }                    // nothing is free: [1, 1]
+        else if (N == 0.0) { result = side ? 1.0 : 0.0; flags = side ? 2 : 1; finish = true; }     // no reads: [0, 1]
+    }
+
+    for (;;) {
+        if (finish) {
+            if (lane == 0) { p.res[(size_t)s * 2 * G + k] = result; p.fl[(size_t)s * 2 * G + k] = flags; }
+            finish = false; done = true;
+        }
+        // the workgroup goes on until each of its searches is done
+        if (lane == 0) doneS[wave] = done ? 1 : 0;
+        __syncthreads();
+        bool all = true;
+        for (int w = 0; w < nw; ++w) all = all && doneS[w] != 0;
+        if (all) break;
+        __syncthreads();                                   // (V in one tile: no barrier below before doneS is written again)
+
+        double o0 = 0.0, o1 = 0.0; bool bad = false;
+#pragma unroll
+        for (int h = 0; h < GP; ++h) acc[h] = 0.0;
+        for (int t0 = 0; t0 < V; t0 += DSM_ABUND_TILE) {
+            if (!resident) stage(t0);
+            if (done) continue;
+            const int n = min(DSM_ABUND_TILE, V - t0);
+            if (mode == M_EM) abund_rows<GP, 1>(n, lane, xS, tS, etaS, ltab, gam, acc, o0, o1, bad);
+            else abund_rows<GP, 2>(n, lane, xS, tS, etaS, ltab, gam, acc, o0, o1, bad);
+        }
+        if (done) continue;
+
+        // everything below is wave-uniform
+        bool decided = false, inside = false, start = false;
+        if (mode == M_EM) {
+            if (__ballot(bad) != 0ull) decided = true;     // a cell with reads and p = 0: this c is outside
+            else {
+                double R = 0.0;
+#pragma unroll
+                for (int h = 0; h < GP; ++h) {
+                    acc[h] = gam[h] * group_allreduce_sum<64>(acc[h]);
+                    R += h != g ? acc[h] : 0.0;
+                }
+                if (!(R > 0.0)) { conv = 1; mode = M_EVAL; }                    // the free haplotypes explain no read: nothing moves
+                else {
+                    const double omc = 1.0 - c;
+                    double delta = 0.0;
+#pragma unroll
+                    for (int h = 0; h < GP; ++h) {
+                        const double gn = h == g ? c : gam[h] > 0.0 ? omc * acc[h] / R : 0.0;      // gamma_g = c survives the step
+                        delta = fmax(delta, fabs(gn - gam[h]));
+                        gam[h] = gn;
+                    }
+                    ++iters;
+                    if (p.tol > 0.0 && delta < p.tol) conv = 1;
+                    if (conv || iters == p.max_iter) mode = M_EVAL;
+                }
+            }
+        } else {
+            const double ll = group_allreduce_sum<64>(o0);
+            if (mode == M_LHAT) {
+                Lhat = ll;
+                double gg = 0.0;
+#pragma unroll
+                for (int h = 0; h < GP; ++h) gg = h == g ? gam[h] : gg;
+                b_in = gg; b_out = side ? 1.0 : 0.0;
+                if (!(Lhat > NINF)) { result = NAN; finish = true; }             // gamma_hat itself contradicts the counts
+                else if (b_in == b_out) { result = b_out; flags = side ? 2 : 1; finish = true; }
+                else { endpoint = true; c = b_out; start = true; }               // the far end of the bracket first
+            } else {
+                if (!conv) flags |= 4;
+                decided = true;
+                inside = 2.0 * (Lhat - ll) <= p.q;                               // (l = -inf: outside)
+            }
+        }
+        if (decided) {
+            if (endpoint) {
+                endpoint = false;
+                if (inside) { result = b_out; flags |= side ? 2 : 1; finish = true; }
+            } else if (inside) b_in = c;
+            else b_out = c;
+            if (!finish) {
+                const double m = 0.5 * (b_in + b_out);
+                if (!(fabs(b_out - b_in) > p.ctol) || m == b_in || m == b_out) { result = b_in; finish = true; }
+                else { c = m; start = true; }
+            }
+        }
+        if (start) {
+            // the inner fit at c starts from the free part of the previous one (of gamma_hat: the first; whenever that part is all 0)
+            double F = 0.0;
+#pragma unroll
+            for (int h = 0; h < GP; ++h) F += h != g ? gam[h] : 0.0;
+            if (!(F > 0.0)) {
+                F = 0.0;
+#pragma unroll
+                for (int h = 0; h < GP; ++h) { gam[h] = h < G ? ghat[h] : 0.0; F += h != g ? gam[h] : 0.0; }
+                if (!(F > 0.0)) {
+#pragma unroll
+                    for (int h = 0; h < GP; ++h) gam[h] = (h < G && h != g) ? 1.0 : 0.0;
+                    F = (double)(G - 1);
+                }
+            }
+            const double omc = 1.0 - c, u = 0.001 / (double)(G - 1);
+#pragma unroll
+            for (int h = 0; h < GP; ++h)
+                gam[h] = h == g ? c : h >= G ? 0.0 : G == 2 ? omc : omc * (0.999 * (gam[h] / F) + u);
+            const bool nofit = G == 2 || c == 1.0;                               // the free part is determined: one evaluation
+            iters = 0; conv = nofit ? 1 : 0;
+            mode = (nofit || p.max_iter == 0) ? M_EVAL : M_EM;
+        }
+    }
+}
+
+template <int GP, int NWMAX>
+static void abund_interval_launch(const AbundIvParams &q, int n, int groups)
+{
+    hipLaunchKernelGGL((abund_interval_kernel<GP, NWMAX>), dim3((unsigned)n, (unsigned)groups), dim3((unsigned)q.NW * 64u), 0, 0, q);
+}
+
+static int abund_check_interval(int S, int G, const double *gamma_hat, double q, double ctol)
+{
+    if (!(q > 0.0) || !std::isfinite(q) || !(ctol > 0.0) || !(ctol < 1.0)) { dsm_set_error("fit_gamma_interval: q=%g, ctol=%g", q, ctol); return DSM_ERR_ARG; }
+    for (int s = 0; s < S; ++s) {
+        double sum = 0.0;
+        for (int g = 0; g < G; ++g) {
+            const double x = gamma_hat[(size_t)s * G + g];
+            if (!(x >= 0.0) || !(x <= 1.0)) { dsm_set_error("fit_gamma_interval: gamma_hat[%d][%d] = %g is outside [0, 1]", s, g, x); return DSM_ERR_ARG; }
+            sum += x;
+        }
+        if (sum != 0.0 && !(fabs(sum - 1.0) <= 1e-9)) { dsm_set_error("fit_gamma_interval: gamma_hat row %d sums to %.17g", s, sum); return DSM_ERR_ARG; }
+    }
+    return DSM_OK;
+}
+
+// as abund_run: d_cnt the resident tensor or null with h_cnt; d_tau the packed words on the device
+static int abund_interval_run(const int32_t *d_cnt, const int64_t *h_cnt, int V, int S, int G, const uint64_t *d_tau, const double *eta,
+                              const double *gamma_hat, double q, int max_iter, double tol, double ctol, double *lo, double *hi, int32_t *flags)
+{
+    const int K = 2 * G;
+    const int GP = G <= 4 ? 4 : G <= 8 ? 8 : G <= 16 ? 16 : 32, NWMAX = GP == 4 ? 12 : GP <= 16 ? 8 : 4;      // a budget of 168 / 256 / 256 / 512 vector registers per lane (used: DESIGN.md sec. 8b; no scratch)
+    const int groups = (K + NWMAX - 1) / NWMAX, NW = (K + groups - 1) / groups;
+    const int NC = abund_chunk(V, S);
+    DevBuf<int32_t> d_x, d_fl; DevBuf<double> d_eta, d_ltab, d_ghat, d_res;
+    ABTRY(d_x.alloc((size_t)NC * V * 4)); ABTRY(d_eta.alloc(16)); ABTRY(d_ltab.alloc(2 * DSM_LOG_TAB_N));
+    ABTRY(d_ghat.alloc((size_t)NC * G)); ABTRY(d_res.alloc((size_t)NC * K)); ABTRY(d_fl.alloc((size_t)NC * K));
+    HIP_TRY(hipMemcpy(d_eta, eta, 16 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ltab, dsm_log_table_host, sizeof dsm_log_table_host, hipMemcpyHostToDevice));
+    std::vector<int32_t> x32, fl((size_t)NC * K);
+    std::vector<double> res((size_t)NC * K);
+    for (int s0 = 0; s0 < S; s0 += NC) {
+        const int n = std::min(NC, S - s0);
+        ABTRY(abund_stage_chunk(d_cnt, h_cnt, V, S, s0, n, d_x, x32));
+        HIP_TRY(hipMemcpy(d_ghat, gamma_hat + (size_t)s0 * G, (size_t)n * G * sizeof(double), hipMemcpyHostToDevice));
+        AbundIvParams a{d_x, d_tau, d_eta, d_ltab, d_ghat, V, G, NW, max_iter, tol, ctol, q, d_res, d_fl};
+        switch (GP) {
+        case 4: abund_interval_launch<4, 12>(a, n, groups); break;
+        case 8: abund_interval_launch<8, 8>(a, n, groups); break;
+        case 16: abund_interval_launch<16, 8>(a, n, groups); break;
+        default: abund_interval_launch<32, 4>(a, n, groups); break;
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(res.data(), d_res, (size_t)n * K * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(fl.data(), d_fl, (size_t)n * K * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < (size_t)n * G; ++i) {
+            lo[(size_t)s0 * G + i] = res[2 * i];
+            hi[(size_t)s0 * G + i] = res[2 * i + 1];
+            flags[(size_t)s0 * G + i] = fl[2 * i] | fl[2 * i + 1];
+        }
+    }
+    return DSM_OK;
+}
+
+extern "C" int dsm_fit_gamma_interval(int device, const int64_t *counts, int V, int S, int G, const int64_t *tau, const double *eta,
+                                      const double *gamma_hat, double q, int max_iter, double tol, double ctol, double *lo, double *hi,
+                                      int32_t *flags)
+{
+    if (S < 0 || !tau || !eta || (S > 0 && (!counts || !gamma_hat || !lo || !hi || !flags))) {
+        dsm_set_error("fit_gamma_interval: bad arguments");
+        return DSM_ERR_ARG;
+    }
+    ABTRY(abund_check_model(V, G, eta, max_iter, tol));
+    ABTRY(abund_check_counts(counts, V, S));
+    ABTRY(abund_check_interval(S, G, gamma_hat, q, ctol));
+    std::vector<uint64_t> packed;
+    ABTRY(abund_pack_tau(tau, V, G, packed));
+    if (S == 0) return DSM_OK;
+    ABTRY(abund_bind_device(device));
+    DevBuf<uint64_t> d_tau;
+    ABTRY(d_tau.alloc((size_t)V));
+    HIP_TRY(hipMemcpy(d_tau, packed.data(), (size_t)V * sizeof(uint64_t), hipMemcpyHostToDevice));
+    return abund_interval_run(nullptr, counts, V, S, G, d_tau, eta, gamma_hat, q, max_iter, tol, ctol, lo, hi, flags);
+}
+
+extern "C" int dsm_ctx_fit_gamma_interval(dsm_ctx *c, int G, const int64_t *tau, const double *eta, const double *gamma_hat, double q,
+                                          int max_iter, double tol, double ctol, double *lo, double *hi, int32_t *flags)
+{
+    if (!c) { dsm_set_error("null context"); return DSM_ERR_ARG; }
+    if (!c->cnt_vs) { dsm_set_error("no count tensor: call dsm_ctx_set_counts first"); return DSM_ERR_STATE; }
+    if (!eta || !gamma_hat || !lo || !hi || !flags) { dsm_set_error("ctx_fit_gamma_interval: null pointer"); return DSM_ERR_ARG; }
+    ABTRY(abund_check_model(c->V, G, eta, max_iter, tol));
+    ABTRY(abund_check_interval(c->S, G, gamma_hat, q, ctol));
+    if (!tau && (!c->have_state || c->G != G)) {
+        dsm_set_error("ctx_fit_gamma_interval: no tau given and no resident state of G=%d haplotypes", G);
+        return DSM_ERR_STATE;
+    }
+    std::vector<uint64_t> packed;
+    if (tau) ABTRY(abund_pack_tau(tau, c->V, G, packed));
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));           // the resident tensors are read from the default stream below
+    DevBuf<uint64_t> d_tau;
+    if (tau) {
+        ABTRY(d_tau.alloc((size_t)c->V));
+        HIP_TRY(hipMemcpy(d_tau, packed.data(), (size_t)c->V * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    return abund_interval_run(c->cnt_vs, nullptr, c->V, c->S, G, tau ? d_tau.p : c->tau, eta, gamma_hat, q, max_iter, tol, ctol, lo, hi, flags);
 }

@@ -268,8 +268,42 @@ int dsm_fit_gamma(int device, const int64_t *counts /*[V][S][4]*/, int V, int S,
 int dsm_ctx_fit_gamma(dsm_ctx *ctx, int G, const int64_t *tau /*[V][G] digits or NULL*/, const double *eta, int max_iter, double tol,
                       int presence, double *gamma, double *loglik, double *deviance, int32_t *iters, int32_t *converged,
                       double *lr_absent);
-/* test hook: samples per launch of the two calls above (0 = by the scratch bound, the default) */
+/* test hook: samples per launch of the two calls above and of the two interval calls below (0 = by the scratch bound, the default) */
 int dsm_abund_debug_set_chunk(int samples);
+
+/* Profile-likelihood intervals of the abundances: tau and eta fixed, gamma_hat [S][G] the fitted rows (input: what
+ * dsm_fit_gamma returned).  For haplotype g of a sample the profile log-likelihood is
+ *     l_g(c) = max { L(gamma) : gamma_g = c, gamma_h >= 0, sum_h gamma_h = 1 }          (L as above: zero cells contribute 0),
+ * concave in c, and the interval is { c in [0, 1] : 2 (Lhat - l_g(c)) <= q }, Lhat = L(gamma_hat) evaluated by the call in the summation
+ * order of dsm_fit_gamma's final pass, q the chi-square (1 d.o.f.) quantile of the level (3.841... for 0.95).  Deterministic: no prior, no RNG.
+ *   Inner fit at c.  gamma_g is held at c on every pass and never updated; EM over the others: r_h = gamma_h sum_{v,b: x > 0} x_vb
+ *     eta[tau_vh][b] / p_vb as in the fit, R = sum_{h != g} r_h added in index order, gamma'_h = (1 - c) r_h / R.  (EM with one component of
+ *     known weight: L does not decrease.)  Stop rule of the fit: the step with max_h |gamma' - gamma| < tol, or max_iter steps; then one pass
+ *     evaluates l.  R = 0 (the free haplotypes explain no read): the fit ends where it is, as converged.  G = 2 or c = 1: the free part is
+ *     determined (gamma_h = 1 - c, resp. 0), l is one evaluation and counts as converged.
+ *   Start of an inner fit.  w = the free part (h != g) of the row at which the search's previous inner fit ended, of gamma_hat for the first
+ *     one and whenever that part sums to 0 (after c = 1), uniform if gamma_hat's free part sums to 0 too; normalised by its sum F added in
+ *     index order; gamma_h = (1 - c) (0.999 (w_h / F) + 0.001 / (G - 1)): a warm start that cannot be trapped at an underflowed zero.
+ *   Outer search, one per (haplotype, side).  The bracket is [0, gamma_hat_g] for lo, [gamma_hat_g, 1] for hi; gamma_hat_g is its inside end
+ *     (not evaluated).  gamma_hat_g = 0: lo = 0, bit 1, no fit; gamma_hat_g = 1: hi = 1, bit 2, no fit.  Otherwise the far end (c = 0, c = 1)
+ *     is tried first: inside the threshold -> lo = 0 (hi = 1) exactly, bit 1 (2).  Else bisection: c = (inside end + outside end) / 2, an
+ *     inside c replaces the inside end, any other c the outside end, until |outside - inside| <= ctol (or c equals one of the ends: ctol
+ *     below the spacing of doubles); the reported end is the INSIDE end -- itself inside the threshold, and short of the true end by at
+ *     most ctol.  The sequence of c depends on nothing but the outcomes, so a search is ~log2(bracket / ctol) + 1 inner fits.
+ *   Outside: 2 (Lhat - l) > q; an inner fit that meets p = 0 at a cell with reads (in an EM pass or in the evaluation).
+ *     lo, hi  [S][G]   the ends;   flags [S][G]   bit 1: lo is the boundary 0; bit 2: hi is the boundary 1; bit 4: some inner fit of this
+ *                      haplotype ended at max_iter (it understates l, the interval comes out too narrow).
+ * Degenerate operands: G = 1 -> [1, 1], flags 2.  A sample without reads (N = 0, G > 1) -> [0, 1], flags 3.  A gamma_hat row that is all 0
+ * (the fit's result for a sample that eta contradicts) or whose L is -inf -> lo = hi = NaN, flags 0; the other samples are not affected.
+ * Limits: those of dsm_fit_gamma, and q > 0 and finite, 0 < ctol < 1, every gamma_hat entry in [0, 1], every row summing to 1 within 1e-9
+ * or all 0 (DSM_ERR_ARG otherwise).  Chunks as in dsm_fit_gamma.  A sample's lo, hi and flags are the same bits from run to run, for any
+ * chunking and from both entry points (dsm_ctx_fit_gamma_interval: the resident counts, tau given or -- NULL -- resident).              */
+int dsm_fit_gamma_interval(int device, const int64_t *counts /*[V][S][4]*/, int V, int S, int G, const int64_t *tau /*[V][G] digits*/,
+                           const double *eta, const double *gamma_hat /*[S][G]*/, double q, int max_iter, double tol, double ctol,
+                           double *lo, double *hi, int32_t *flags);
+int dsm_ctx_fit_gamma_interval(dsm_ctx *ctx, int G, const int64_t *tau /*[V][G] digits or NULL*/, const double *eta,
+                               const double *gamma_hat, double q, int max_iter, double tol, double ctol, double *lo, double *hi,
+                               int32_t *flags);
 
 /* ------------------------------------------------------------------------ */
 /* f4: accessory-gene assignment (desman/Eta_Sampler.py, desman/GeneAssign.py) */

@@ -5,9 +5,11 @@ that time per step and fit is a plain quotient; the default stop test is timed o
 took.  Timing: HIP events on the default stream (the library's launches of this call run there) around the context form, which has
 the counts resident -- a sample holds the call's scratch allocations and frees (dsm_ctx_fit_gamma keeps none between calls), the
 repack launch, the EM launch, the parameter upload and the synchronous result copies, not the count upload; after a warm-up call,
-median of --reps.  With one sample and no presence fits that fixed cost is a visible part of the total.  The CPU comparator is the numpy restatement of tests/_abund_ref.py at one small shape.
+median of --reps.  One more leg per shape times the profile-likelihood intervals (dsm_ctx_fit_gamma_interval) of the default fit's
+abundances with a fixed --interval-steps EM steps per inner fit (tol = 0) and the default ctol; the number of inner fits is that of
+the bisections and is recorded from the bracket widths.  With one sample and no presence fits that fixed cost is a visible part of the total.  The CPU comparator is the numpy restatement of tests/_abund_ref.py at one small shape.
 
-    python scripts/bench_abund.py [--reps 7] [--steps 200] [--out profiles/abund_bench.json]
+    python scripts/bench_abund.py [--reps 7] [--steps 200] [--interval-steps 20] [--out profiles/abund_bench.json]
 """
 import argparse
 import json
@@ -43,6 +45,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--steps", type=int, default=200, help="EM steps of the fixed-length runs")
+    ap.add_argument("--interval-steps", type=int, default=20, help="EM steps of every inner fit of the interval leg")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "abund_bench.json"))
     a = ap.parse_args()
     import torch
@@ -67,6 +70,14 @@ def main():
                          event_ms_all=every, iters_min=int(res["iters"].min()), iters_median=float(np.median(res["iters"])),
                          iters_max=int(res["iters"].max()), converged=int(res["converged"].sum())))
         print(json.dumps(rows[-1]), flush=True)
+        ghat = res["gamma"]
+        ms, every, iv = timed(lambda: ctx.fit_gamma_interval(eta, ghat, tau=tau, max_iter=a.interval_steps, tol=0.0), min(a.reps, 3))
+        # inner fits of a search: the endpoint test and one per halving of its bracket down to ctol (none where an end is a boundary)
+        width = np.stack([ghat, 1.0 - ghat])
+        fits = int(np.where(width > 0, 1 + np.ceil(np.log2(np.maximum(width, _lib.FIT_CTOL) / _lib.FIT_CTOL)), 0).sum())
+        rows.append(dict(V=V, G=G, S_new=S, interval=True, searches=2 * G * S, inner_fits_at_most=fits, steps_per_inner_fit=a.interval_steps,
+                         ctol=_lib.FIT_CTOL, event_ms_median=ms, event_ms_all=every, boundary_ends=int(((iv["flags"] & 3) != 0).sum())))
+        print(json.dumps(rows[-1]), flush=True)
         ctx.close()
     # CPU comparator: the numpy restatement, one process
     import _abund_ref as R
@@ -79,7 +90,7 @@ def main():
     cpu = dict(what="numpy restatement (tests/_abund_ref.py: fit), one process, BLAS threads as the environment sets them", V=Vc, G=Gc, fits=Sc,
                steps=nc, seconds=tc, us_per_step_and_fit=tc * 1e6 / nc / Sc, position_steps_per_s=Vc * Sc * nc / tc)
     print(json.dumps(dict(cpu=cpu)))
-    out = dict(command="python scripts/bench_abund.py --reps %d --steps %d" % (a.reps, a.steps), device=torch.cuda.get_device_name(0),
+    out = dict(command="python scripts/bench_abund.py --reps %d --steps %d --interval-steps %d" % (a.reps, a.steps, a.interval_steps), device=torch.cuda.get_device_name(0),
                timing="HIP events around Context.fit_gamma (counts resident), warm-up call, median of reps", cases=rows, cpu=cpu)
     if a.out:
         with open(a.out, "w") as fh:
