@@ -107,6 +107,7 @@ SIGNATURES = {
     "dsm_nmft_get": (_i, [_vp, _vp, _vp]),
     "dsm_nmft_factorize": (_i, [_vp, _i, _d, _i, C.POINTER(_i), _vp]),
     "dsm_nmft_objective": (_i, [_vp, C.POINTER(_d)]),
+    "dsm_nmft_debug_path": (_i, [_vp, _i, C.POINTER(_i)]),
     "dsm_nmft_get_tau": (_i, [_vp, _i64p]),
     "dsm_lrt_step": (_i, [_i, _f64p, _i32p, _i32p, _f64p, _d, _i, _i, _f64p, _f64p, _f64p]),
     "dsm_assign_tau": (_i, [_i, _i64p, _i, _i, _i, _f64p, _f64p, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
@@ -717,6 +718,15 @@ class Context:
         d = _d(0)
         check(self.lib.dsm_nmft_objective(self._h, C.byref(d)))
         return d.value
+
+    def nmft_debug_path(self, fix_gamma=False):
+        """test hook: which kernels nmft_factorize(fix_gamma=...) takes for this context, nothing launched
+        (include/desman_hip.h: dsm_nmft_debug_path) -> dict"""
+        out = (_i * 8)()
+        check(self.lib.dsm_nmft_debug_path(self._h, int(bool(fix_gamma)), out))
+        fam, nt, kb, ncb, nwv, grid, lds, flags = (int(x) for x in out)
+        return {"family": ("two-pass", "mfma", "split", "persist")[fam], "NT": nt, "KB": kb, "NCB": ncb, "NWV": nwv, "grid": grid,
+                "lds": lds, "xpar": bool(flags & 1), "gstep": bool(flags & 2), "VT": (flags >> 8) & 255, "cus": flags >> 16}
 
     def nmft_get_tau(self):
         out = np.empty((self.V, self.nG, 4), dtype=np.int64)

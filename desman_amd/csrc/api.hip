@@ -1494,6 +1494,16 @@ extern "C" int dsm_batch_nmft_factorize(dsm_ctx *const *ctxs, int K, int max_ite
     return DSM_OK;
 }
 
+// test hook (read only): the kernel family and instantiation dsm_nmft_factorize takes for this context as it is set up now
+extern "C" int dsm_nmft_debug_path(dsm_ctx *c, int fix_gamma, int *out)
+{
+    TRY(need(c, true, false));
+    if (!out) { dsm_set_error("nmft_debug_path: out is null"); return DSM_ERR_ARG; }
+    if (!c->ntau) { dsm_set_error("nmft_debug_path: call dsm_nmft_set first"); return DSM_ERR_STATE; }
+    BIND(c);
+    return nmft_debug_path(c, fix_gamma, out);
+}
+
 extern "C" int dsm_nmft_objective(dsm_ctx *c, double *div)
 {
     TRY(need(c, true, false));

@@ -260,3 +260,4 @@ int nmft_wide_grid(const dsm_ctx *c);
 int nmft_mfma_grid(const dsm_ctx *c, bool fix = false);     // up to four workgroups per CU (five for the fused pass of factorize_tau)
 int k_nmft_wave(dsm_ctx *c, int adjust, int do_update);
 int k_nmft_persist(dsm_ctx *c, int max_iter, double min_change, int fix_gamma, int adjust, int *used);
+int nmft_debug_path(const dsm_ctx *c, int fix_gamma, int out[8]);      // dsm_nmft_debug_path: which kernels dsm_nmft_factorize takes (nothing is launched)

@@ -488,18 +488,21 @@ static int spad_for(int S)
     while (p < S && p < 256) p <<= 1;
     return p;
 }
+// the instantiation of nmft_pass_a_kernel a haplotype count takes: accumulators per lane (k_nmft_pass_a pairs each with its workgroup size)
+static int pass_a_gm(int G) { return G <= 4 ? 4 : G <= 8 ? 8 : G <= 16 ? 16 : 32; }
 
 int k_nmft_pass_a(dsm_ctx *c)
 {
     KTimer tm(c, DSM_K_NMFT_A);
     const int G = c->nG, S = c->S, SPAD = spad_for(S);
+    const int gm = pass_a_gm(G);
 #define LAUNCH_A(GM, TH)                                                                                          \
     hipLaunchKernelGGL((nmft_pass_a_kernel<GM, TH>), dim3(c->nmft_blocks), dim3(TH),                              \
                        ((size_t)(TH / SPAD) * (GM + 2) * SPAD + 2 * DSM_LOG_TAB_N) * sizeof(double), c->stream,   \
                        c->F, c->ntau, c->ngam, c->V, S, G, SPAD, NMFT_CTL(c), c->log_tab, c->npart)
-    if (G <= 4) LAUNCH_A(4, 1024);
-    else if (G <= 8) LAUNCH_A(8, 512);
-    else if (G <= 16) LAUNCH_A(16, 512);
+    if (gm == 4) LAUNCH_A(4, 1024);
+    else if (gm == 8) LAUNCH_A(8, 512);
+    else if (gm == 16) LAUNCH_A(16, 512);
     else LAUNCH_A(32, 256);
 #undef LAUNCH_A
     HIP_TRY(hipGetLastError());
@@ -575,17 +578,29 @@ bool nmft_gstep_applies(const dsm_ctx *c, int fix_gamma)
     return c->nmft_fused < 0 ? nmft_mfma_grid(c, false) > 128 : c->nmft_fused == 3;
 }
 
-int k_nmft_pass_b(dsm_ctx *c, int adjust)
+// variants a workgroup of nmft_pass_b_kernel takes per step (*vt), the launch's workgroups and its dynamic LDS: about 8192 Q' entries per step, eight variants at
+// most; fewer where gamma [G][S + 1] leaves less than that of the 160 KB (S = 512 from G = 27 on: two variants, from G = 31 on: one).
+// The rows of a variant are computed alone, so the factors do not depend on VT.
+static size_t pass_b_tile(int V, int S, int G, int *vt, int *grid)
 {
-    KTimer tm(c, DSM_K_NMFT_B);
-    const int G = c->nG, S = c->S, SP = S + 1;
+    const int SP = S + 1;
     int VT = 8192 / (4 * SP);
     if (VT > 8) VT = 8;
     if (VT < 1) VT = 1;
-    const size_t sh = ((size_t)G * SP + G + 2 * (size_t)4 * VT * G + (size_t)4 * VT * SP) * sizeof(double);
+    auto bytes = [&](int n) { return ((size_t)G * SP + G + 2 * (size_t)4 * n * G + (size_t)4 * n * SP) * sizeof(double); };
+    while (VT > 1 && bytes(VT) > 160 * 1024) --VT;
+    *vt = VT;
+    *grid = std::min((V + VT - 1) / VT, 2048);
+    return bytes(VT);
+}
+
+int k_nmft_pass_b(dsm_ctx *c, int adjust)
+{
+    KTimer tm(c, DSM_K_NMFT_B);
+    const int G = c->nG, S = c->S;
+    int VT, grid;
+    const size_t sh = pass_b_tile(c->V, S, G, &VT, &grid);
     if (sh > 160 * 1024) { dsm_set_error("NMFT tile (%zu B) exceeds LDS", sh); return DSM_ERR_UNSUPPORTED; }
-    int grid = (c->V + VT - 1) / VT;
-    if (grid > 2048) grid = 2048;
     hipLaunchKernelGGL(nmft_pass_b_kernel, dim3(grid), dim3(256), sh, c->stream, c->F, c->ntau, c->ngam_raw, c->V, S, G, VT,
                        adjust, NMFT_CTL(c));
     HIP_TRY(hipGetLastError());
@@ -2212,8 +2227,9 @@ struct PersistGate {
 };
 static PersistGate g_persist_gate[16];
 
+// launch = false: the residency test alone (nmft_debug_path)
 template <int NT, int KB, int NWV>
-static int launch_persist(dsm_ctx *c, const NmftPersistParams &q, int grid, size_t sh, int *fits)
+static int launch_persist(const dsm_ctx *c, const NmftPersistParams &q, int grid, size_t sh, int *fits, bool launch)
 {
     auto fn = nmft_persist_kernel<NT, KB, true, NWV>;          // F stays in registers for the whole loop (round 4: the tau numerators on the matrix cores freed the registers; before, three tiles spilled at 3 wavefronts per SIMD and F was re-read from L2 twice per update)
     int occ = 0, cus = 0;
@@ -2221,7 +2237,7 @@ static int launch_persist(dsm_ctx *c, const NmftPersistParams &q, int grid, size
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 64 * NWV, sh));
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
     *fits = grid <= occ * cus;
-    if (!*fits) return DSM_OK;
+    if (!*fits || !launch) return DSM_OK;
     hipLaunchKernelGGL(fn, dim3(grid), dim3(64 * NWV), sh, c->stream, q);
     HIP_TRY(hipGetLastError());
     return DSM_OK;
@@ -2254,6 +2270,18 @@ static int nmft_persist_shape(const dsm_ctx *c, int fix_gamma, int *nt_out, int 
     if (sh > 160 * 1024) return 0;
     *nt_out = nt; *kb_out = kb; *nwv_out = nwv; *sh_out = sh; *cus_out = cus;
     return grid;
+}
+// the instantiation of a (tiles, K-blocks, wavefronts) triple that nmft_persist_shape admits
+static int persist_dispatch(const dsm_ctx *c, const NmftPersistParams &q, int nt, int kb, int nwv, int grid, size_t sh, int *fits, bool launch)
+{
+    int rc = DSM_OK;
+#define PCASE(N, K) if (nt == N && kb == K) rc = (nwv == 4) ? launch_persist<N, K, 4>(c, q, grid, sh, fits, launch) : launch_persist<N, K, NMFT_P_WAVES>(c, q, grid, sh, fits, launch)
+    PCASE(1, 1); PCASE(1, 2); PCASE(1, 3); PCASE(2, 1); PCASE(2, 2); PCASE(2, 3); PCASE(3, 1); PCASE(3, 2); PCASE(3, 3); PCASE(4, 1); PCASE(4, 2); PCASE(4, 3);
+#define PCASE4(N, K) if (nt == N && kb == K) rc = launch_persist<N, K, 4>(c, q, grid, sh, fits, launch)
+    PCASE4(5, 1); PCASE4(5, 2); PCASE4(5, 3); PCASE4(6, 1); PCASE4(6, 2); PCASE4(6, 3);
+#undef PCASE4
+#undef PCASE
+    return rc;
 }
 int k_nmft_persist(dsm_ctx *c, int max_iter, double min_change, int fix_gamma, int adjust, int *used)
 {
@@ -2297,12 +2325,7 @@ int k_nmft_persist(dsm_ctx *c, int max_iter, double min_change, int fix_gamma, i
     HIP_TRY(hipMemsetAsync(c->np_bar, 0, 1024, c->stream));
     int fits = 0, rc = DSM_OK;
     KTimer tm(c, DSM_K_NMFT_B);
-#define PCASE(N, K) if (nt == N && kb == K) rc = (nwv == 4) ? launch_persist<N, K, 4>(c, q, grid, sh, &fits) : launch_persist<N, K, NMFT_P_WAVES>(c, q, grid, sh, &fits)
-    PCASE(1, 1); PCASE(1, 2); PCASE(1, 3); PCASE(2, 1); PCASE(2, 2); PCASE(2, 3); PCASE(3, 1); PCASE(3, 2); PCASE(3, 3); PCASE(4, 1); PCASE(4, 2); PCASE(4, 3);
-#define PCASE4(N, K) if (nt == N && kb == K) rc = launch_persist<N, K, 4>(c, q, grid, sh, &fits)
-    PCASE4(5, 1); PCASE4(5, 2); PCASE4(5, 3); PCASE4(6, 1); PCASE4(6, 2); PCASE4(6, 3);
-#undef PCASE4
-#undef PCASE
+    rc = persist_dispatch(c, q, nt, kb, nwv, grid, sh, &fits, true);
     if (rc != DSM_OK) return rc;
     if (!fits) return DSM_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));           // the lock is held until the resident workgroups are gone
@@ -2326,5 +2349,43 @@ int k_nmft_persist(dsm_ctx *c, int max_iter, double min_change, int fix_gamma, i
         return DSM_OK;                                  // *used stays 0: the caller's loop takes over from the untouched start
     }
     *used = 1;
+    return DSM_OK;
+}
+
+// dsm_nmft_debug_path (include/desman_hip.h): the kernel family and instantiation dsm_nmft_factorize takes for this context, from the
+// functions the launchers themselves ask.  Launches nothing, allocates nothing.
+int nmft_debug_path(const dsm_ctx *c, int fix_gamma, int out[8])
+{
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    int nt, kb, ncb, nwv, cus = 0;
+    size_t sh;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));      // what the grid caps and the persistent gate ask
+    struct Flags { int *out, cus; ~Flags() { out[7] |= cus << 16; } } flags_guard{out, cus};
+    const int pgrid = nmft_persist_shape(c, fix_gamma, &nt, &kb, &nwv, &sh, &cus);
+    if (pgrid > 0) {
+        int fits = 0;
+        const int rc = persist_dispatch(c, NmftPersistParams{}, nt, kb, nwv, pgrid, sh, &fits, false);
+        if (rc != DSM_OK) return rc;
+        if (fits) {
+            out[0] = 3; out[1] = nt; out[2] = kb; out[4] = nwv; out[5] = pgrid; out[6] = (int)sh;
+            return DSM_OK;
+        }
+    }
+    if (mfma_shape(c, &nt, &kb)) {
+        const bool fix = fix_gamma != 0;              // gamma fixed: the fused pass, its own instantiation, grid and tile
+        out[0] = 1; out[1] = nt; out[2] = kb; out[5] = nmft_mfma_grid(c, fix); out[6] = (int)mfma_lds_bytes(nt, kb, fix);
+        out[7] = nmft_gstep_applies(c, fix_gamma) ? 2 : 0;
+        return DSM_OK;
+    }
+    if (wide_shape(c, &nt, &kb, &ncb)) {
+        const bool xpar = split_xpar(nt, kb, ncb);
+        out[0] = 2; out[1] = nt; out[2] = kb; out[3] = ncb; out[5] = nmft_wide_grid(c); out[6] = (int)split_lds_bytes(nt, kb, ncb, xpar);
+        out[7] = xpar ? 1 : 0;
+        return DSM_OK;
+    }
+    int vt;
+    out[0] = 0; out[1] = spad_for(c->S); out[2] = pass_a_gm(c->nG);
+    sh = pass_b_tile(c->V, c->S, c->nG, &vt, &out[5]);
+    out[6] = (int)sh; out[7] = vt << 8;
     return DSM_OK;
 }

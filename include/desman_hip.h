@@ -184,7 +184,9 @@ int dsm_ctx_get_tau_sum(dsm_ctx *ctx, int64_t *tau_sum);
 int dsm_ctx_get_tau_at(dsm_ctx *ctx, int it, int64_t *tau);
 
 /* A8-A12: Init_NMFT (desman/Init_NMFT.py).  F is derived from the resident
- * counts (:49-60).  tau [4V][G] row v + a*V, gamma [G][S] as in the reference.*/
+ * counts (:49-60).  tau [4V][G] row v + a*V, gamma [G][S] as in the reference.
+ * Every shape up to S = DSM_MAX_S, G = DSM_MAX_G has a kernel (tests/test_gpu_nmft_forms.py
+ * walks the dispatch, both limits together included).                        */
 int dsm_nmft_set(dsm_ctx *ctx, const double *tau, const double *gamma, int G);
 int dsm_nmft_get(dsm_ctx *ctx, double *tau, double *gamma);
 /* factorize (:98-115) incl. _adjustment; fix_gamma != 0 -> factorize_tau
@@ -193,11 +195,26 @@ int dsm_nmft_get(dsm_ctx *ctx, double *tau, double *gamma);
 int dsm_nmft_factorize(dsm_ctx *ctx, int max_iter, double min_change, int fix_gamma,
                        int *n_done, double *div_trace);
 /* The same for n_ctx (1..8) chains of one shape at once (replicate chains: one launch of each kernel of an update for all
- * of them; the stop test stays per chain).  Matrix-core path only (S <= 128, G <= 16; DSM_ERR_UNSUPPORTED otherwise).
+ * of them; the stop test stays per chain).  One-pass kernels only (families 1 and 2 of dsm_nmft_debug_path; DSM_ERR_UNSUPPORTED otherwise).
  * n_done [n_ctx]; div_traces [n_ctx][max_iter + 1] or NULL.                                                          */
 int dsm_batch_nmft_factorize(dsm_ctx *const *ctxs, int n_ctx, int max_iter, double min_change, int fix_gamma,
                              int *n_done, double *div_traces);
 int dsm_nmft_objective(dsm_ctx *ctx, double *div);
+/* test hook (read only; launches nothing, allocates nothing): the kernels dsm_nmft_factorize (fix_gamma as there) takes for this
+ * context as it is set up now -- dsm_nmft_set's shape, dsm_ctx_set_nmft_persist, dsm_ctx_set_nmft_fused, timing -- answered by the
+ * functions the launchers ask.  DSM_ERR_STATE before dsm_nmft_set.
+ *   out[0] family: 0 two-pass (nmft_pass_a_kernel + nmft_pass_b_kernel), 1 nmft_mfma_kernel (gamma fixed: nmft_mfma_fix_kernel),
+ *          2 nmft_split_kernel, 3 nmft_persist_kernel (the shape gate and the residency test of the launch both passed)
+ *   out[1] NT, sample tiles of 16 (per column block for family 2);  family 0: the padded sample lanes of pass A (32..256)
+ *   out[2] KB, haplotype blocks of 4;                               family 0: the accumulators GM of pass A (4, 8, 16, 32)
+ *   out[3] NCB, column blocks (family 2, else 0)       out[4] wavefronts per workgroup (family 3, else 0)
+ *   out[5] workgroups of the update launch (family 0: of pass B)    out[6] its dynamic LDS in bytes
+ *   out[7] flags: bit 0 nmft_split_kernel runs with two exchange buffers (split_xpar); bit 1 the update kernel begins with the
+ *          gamma / control step (see dsm_ctx_set_nmft_fused); bits 8..15 variants per workgroup step of pass B (family 0);
+ *          bits 16..30 the device's compute units, which cap the grids and gate family 3
+ * Read only for the context; where the shape gate admits family 3 it sets that kernel's maximum dynamic LDS attribute
+ * (hipFuncSetAttribute) as the launch would, for the residency test.                                                         */
+int dsm_nmft_debug_path(dsm_ctx *ctx, int fix_gamma, int out[8]);
 /* get_tau (:230-245) -> one-hot [V][G][4] int64                              */
 int dsm_nmft_get_tau(dsm_ctx *ctx, int64_t *tau_onehot);
 
