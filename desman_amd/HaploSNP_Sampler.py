@@ -263,6 +263,16 @@ class HaploSNP_Sampler:
             return self._ctx.fit_gamma(eta, tau=tau, max_iter=max_iter, tol=tol, presence=presence)
         return _lib.fit_gamma(snps, tau, eta, max_iter=max_iter, tol=tol, presence=presence, device=self._device)
 
+    def fitGammaEta(self, snps=None, tau=None, eta0=None, max_iter=_lib.FIT_MAX_ITER, tol=_lib.FIT_TOL):
+        """abundances AND one error matrix of the samples of snps [V,S',4] -- default: the chain's own counts, on the resident tensor --
+        fitted jointly with the haplotypes tau (default tau_star) held fixed, from eta0 (default eta_star): the dict of
+        _lib.fit_gamma_eta (gamma, eta, loglik, loglik0, deviance, iters, converged, dead_rows, lr_eta)"""
+        tau = self.tau_star if tau is None else tau
+        eta0 = self.eta_star if eta0 is None else eta0
+        if snps is None:
+            return self._ctx.fit_gamma_eta(eta0, tau=tau, max_iter=max_iter, tol=tol)
+        return _lib.fit_gamma_eta(snps, tau, eta0, max_iter=max_iter, tol=tol, device=self._device)
+
     def fitGammaInterval(self, level=0.95, snps=None, tau=None, eta=None, max_iter=_lib.FIT_MAX_ITER, tol=_lib.FIT_TOL, ctol=_lib.FIT_CTOL):
         """fitGamma() and the profile-likelihood intervals of its abundances at confidence ``level``: fitGamma's dict with lo [S',G],
         hi [S',G] and flags [S',G] added (_lib.fit_gamma_interval)"""

@@ -118,6 +118,10 @@ SIGNATURES = {
     "dsm_abund_debug_set_chunk": (_i, [_i]),
     "dsm_fit_gamma_interval": (_i, [_i, _i64p, _i, _i, _i, _i64p, _f64p, _f64p, _d, _i, _d, _d, _vp, _vp, _vp]),
     "dsm_ctx_fit_gamma_interval": (_i, [_vp, _i, _vp, _f64p, _f64p, _d, _i, _d, _d, _vp, _vp, _vp]),
+    "dsm_fit_gamma_eta": (_i, [_i, _i64p, _i, _i, _i, _i64p, _f64p, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dsm_ctx_fit_gamma_eta": (_i, [_vp, _i, _vp, _f64p, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dsm_abund_debug_set_eta_batch": (_i, [_i]),
+    "dsm_abund_debug_set_eta_stage_max": (_i, [C.c_longlong]),
     "dsm_genes_create": (_i, [C.POINTER(_vp), _i]),
     "dsm_genes_destroy": (_i, [_vp]),
     "dsm_genes_set_data": (_i, [_vp, _vp, _i, _i, _i, _i32p, _f64p]),
@@ -347,6 +351,48 @@ def fit_gamma_interval(counts, tau, eta, gamma_hat, level=0.95, q=None, max_iter
     return out
 
 
+def _fit_eta_out(S, G):
+    out = dict(gamma=np.zeros((S, G)), eta=np.zeros((4, 4)), loglik=np.zeros(S), loglik0=np.zeros(S), deviance=np.zeros(S))
+    scal = dict(iters=np.zeros(1, dtype=np.int32), converged=np.zeros(1, dtype=np.int32), dead_rows=np.zeros(1, dtype=np.int32),
+                lr_eta=np.zeros(1))
+    ptrs = [_ptr(out[k]) for k in ("gamma", "eta", "loglik", "loglik0", "deviance")] \
+        + [_ptr(scal[k]) for k in ("iters", "converged", "dead_rows", "lr_eta")]
+    return out, scal, ptrs
+
+
+def _fit_eta_result(out, scal):
+    out.update(iters=int(scal["iters"][0]), converged=int(scal["converged"][0]), dead_rows=int(scal["dead_rows"][0]),
+               lr_eta=float(scal["lr_eta"][0]))
+    return out
+
+
+def fit_gamma_eta(counts, tau, eta0, max_iter=FIT_MAX_ITER, tol=FIT_TOL, device=0):
+    """Abundances of the haplotypes ``tau`` in the samples of ``counts`` [V,S,4] AND one error matrix shared by these samples, fitted
+    jointly by EM from the uniform rows and ``eta0`` with tau held fixed (dsm_fit_gamma_eta): a dict of gamma [S,G], eta [4,4], loglik
+    [S], deviance [S], loglik0 [S] (the fit with eta held at eta0: fit_gamma's loglik) and the call's iters, converged, dead_rows (bit a:
+    row a of eta had no mass in some step and kept its values) and lr_eta = 2 (sum loglik - sum loglik0) >= 0."""
+    x = np.ascontiguousarray(counts, dtype=np.int64)
+    if x.ndim != 3 or x.shape[2] != 4:
+        raise ValueError("fit_gamma_eta: counts must be [V,S,4]")
+    V, S = x.shape[0], x.shape[1]
+    t, eta0 = _fit_tau(tau, V), _fit_eta(eta0)
+    G = t.shape[1]
+    out, scal, ptrs = _fit_eta_out(S, G)
+    check(load().dsm_fit_gamma_eta(int(device), x, V, S, G, t, eta0, int(max_iter), float(tol), *ptrs))
+    return _fit_eta_result(out, scal)
+
+
+def abund_debug_set_eta_batch(steps=0):
+    """test hook: EM steps of fit_gamma_eta enqueued between two reads of the device's stop word (0 = the default); results do not
+    depend on it"""
+    check(load().dsm_abund_debug_set_eta_batch(int(steps)))
+
+
+def abund_debug_set_eta_stage_max(nbytes=0):
+    """test hook: the bound of fit_gamma_eta's sample-major copy of the counts in bytes (0 = the default, 1 GiB)"""
+    check(load().dsm_abund_debug_set_eta_stage_max(int(nbytes)))
+
+
 def _ptr(a):
     return None if a is None else a.ctypes.data
 
@@ -495,6 +541,15 @@ class Context:
                                          _ptr(out["loglik"]), _ptr(out["deviance"]), _ptr(out["iters"]), _ptr(out["converged"]),
                                          _ptr(out.get("lr_absent"))))
         return out
+
+    def fit_gamma_eta(self, eta0, tau=None, max_iter=FIT_MAX_ITER, tol=FIT_TOL):
+        """fit_gamma_eta() of the module for the samples of the resident count tensor, with the given tau or the resident one"""
+        eta0 = _fit_eta(eta0)
+        t = None if tau is None else _fit_tau(tau, self.V)
+        G = self.G if t is None else t.shape[1]
+        out, scal, ptrs = _fit_eta_out(self.S, G)
+        check(self.lib.dsm_ctx_fit_gamma_eta(self._h, G, _ptr(t), eta0, int(max_iter), float(tol), *ptrs))
+        return _fit_eta_result(out, scal)
 
     def fit_gamma_interval(self, eta, gamma_hat, tau=None, level=0.95, q=None, max_iter=FIT_MAX_ITER, tol=FIT_TOL, ctol=FIT_CTOL):
         """fit_gamma_interval() of the module for the samples of the resident count tensor, with the given tau or the resident one"""

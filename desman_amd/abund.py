@@ -1,7 +1,7 @@
 """`desman-abund`: abundances of a finished run's haplotypes in samples that were not in the fit.
 
     python -m desman_amd.abund <run_dir> <table.freq> [-o DIR] [--tau FILE] [--only-new] [--presence] [--interval [LEVEL]] [--ctol X]
-                                                      [--max-iter N] [--tol X] [--device N]
+                                                      [--fit-eta] [--max-iter N] [--tol X] [--device N]
 
 `desman` drops every sample whose mean depth is not above -m, and a sample sequenced after the fit has no row in ``Gamma_star.csv``
 either; a refit would give new haplotypes with new labels.  This entry point holds the run's haplotypes and error matrix fixed and
@@ -18,6 +18,16 @@ Position) and writes
                              profile-likelihood interval of the abundance in Projected_Gamma.csv (dsm_fit_gamma_interval; each end
                              found to --ctol) and its flag bits: 1 lo is the boundary 0, 2 hi is the boundary 1, 4 an inner fit
                              ended at --max-iter (the interval is too narrow)
+
+With --fit-eta the error matrix is not the run's: the samples may come from another library preparation, sequencer or mapper than the
+fit's.  One error matrix shared by the samples of the call is estimated together with their abundances, from ``Eta_star.csv`` as the
+start (dsm_fit_gamma_eta); Projected_Gamma.csv and Projected_fit.csv then hold the joint fit's rows (iters and converged are the
+call's), Projected_fit.csv has one more column, loglik_eta0 (the fit with the run's error matrix), --presence and --interval use the
+fitted matrix, and two more files are written:
+
+    Projected_Eta.csv        the fitted error matrix, in the format of Eta_star.csv
+    Projected_eta_fit.csv    one row: loglik, loglik_eta0 (both summed over the samples), lr_eta = 2 (loglik - loglik_eta0), iters,
+                             converged, dead_rows (bit a: no haplotype with abundance carries base a, row a is the run's)
 """
 import argparse
 import os
@@ -43,6 +53,8 @@ def build_parser():
     ap.add_argument("--presence", action="store_true", help="also write the likelihood-ratio statistics of each haplotype's absence")
     ap.add_argument("--interval", type=float, nargs="?", const=0.95, default=None, metavar="LEVEL",
                     help="also write the profile-likelihood intervals of the abundances at this confidence level (default 0.95)")
+    ap.add_argument("--fit-eta", action="store_true",
+                    help="estimate one error matrix for the samples of the table together with their abundances (start: Eta_star.csv)")
     ap.add_argument("--ctol", type=float, default=CTOL, help="width to which an interval end is found (default %g)" % CTOL)
     ap.add_argument("--max-iter", type=int, default=MAX_ITER, help="EM steps at most (default %d)" % MAX_ITER)
     ap.add_argument("--tol", type=float, default=TOL, help="stop when no abundance moves by this much in a step (default %g)" % TOL)
@@ -128,9 +140,31 @@ def write_results(out_dir, names, counts, res):
     fit = pd.DataFrame({"reads": reads.astype(np.int64), "mean_depth": reads / float(counts.shape[0]), "loglik": res["loglik"],
                         "deviance": res["deviance"], "deviance_per_read": per_read, "iters": np.asarray(res["iters"], dtype=np.int64),
                         "converged": np.asarray(res["converged"], dtype=np.int64)}, index=names)
+    if "loglik0" in res:
+        fit["loglik_eta0"] = res["loglik0"]
     fit.to_csv(os.path.join(out_dir, "Projected_fit.csv"))
     if "lr_absent" in res:
         pd.DataFrame(res["lr_absent"], index=names).to_csv(os.path.join(out_dir, "Projected_presence.csv"))
+
+
+def write_eta(out_dir, res):
+    """Projected_Eta.csv in the format of Eta_star.csv (Output_Results), and the one-row Projected_eta_fit.csv"""
+    pd.DataFrame(res["eta"]).to_csv(os.path.join(out_dir, "Projected_Eta.csv"))
+    row = {"loglik": [float(np.sum(res["loglik"]))], "loglik_eta0": [float(np.sum(res["loglik0"]))], "lr_eta": [res["lr_eta"]],
+           "iters": [int(res["iters"])], "converged": [int(res["converged"])], "dead_rows": [int(res["dead_rows"])]}
+    pd.DataFrame(row).to_csv(os.path.join(out_dir, "Projected_eta_fit.csv"), index=False)
+
+
+def fit_eta(counts, digits, eta, opts):
+    """the joint fit in the layout of fit_gamma's result: iters and converged per sample (the call's), the call's scalars under eta_fit"""
+    from . import _lib
+    S = counts.shape[1]
+    joint = _lib.fit_gamma_eta(counts, digits, eta, max_iter=opts.max_iter, tol=opts.tol, device=opts.device)
+    res = dict(joint)
+    res["iters"] = np.full(S, joint["iters"], dtype=np.int64)
+    res["converged"] = np.full(S, joint["converged"], dtype=np.int64)
+    res["eta_fit"] = joint
+    return res
 
 
 def write_interval(out_dir, names, iv):
@@ -161,9 +195,30 @@ def main(argv=None):
         sys.exit("desman-abund: no sample to fit (--only-new: every sample of the table has a row in Gamma_star.csv)")
     counts = select_counts(table, rows, keep)
     from . import _lib                                                      # nothing above needs the library or a GPU
-    res = _lib.fit_gamma(counts, digits, eta, max_iter=opts.max_iter, tol=opts.tol, presence=opts.presence, device=opts.device)
-    write_results(opts.output_dir or opts.run_dir, [names[k] for k in keep], counts, res)
-    n_open = int((np.asarray(res["converged"]) == 0).sum())
+    if opts.fit_eta:
+        res = fit_eta(counts, digits, eta, opts)
+        joint = res["eta_fit"]
+        if not np.isfinite(joint["eta"]).all() or not joint["gamma"].any():
+            print("desman-abund: --fit-eta: Eta_star.csv gives some read probability 0, nothing was fitted "
+                  "(Projected_fit.csv: loglik = -inf)", file=sys.stderr)
+        elif not joint["converged"]:
+            print("desman-abund: --fit-eta did not converge in %d steps (Projected_eta_fit.csv: converged = 0)" % opts.max_iter,
+                  file=sys.stderr)
+        if joint["dead_rows"]:
+            print("desman-abund: --fit-eta: no haplotype with abundance carries base %s, the rows of Projected_Eta.csv for them are "
+                  "the run's (Projected_eta_fit.csv: dead_rows = %d)"
+                  % (", ".join("ACGT"[a] for a in range(4) if joint["dead_rows"] >> a & 1), joint["dead_rows"]), file=sys.stderr)
+        eta = np.ascontiguousarray(joint["eta"])                            # --presence and --interval below: the fitted matrix
+        if opts.presence:
+            res["lr_absent"] = _lib.fit_gamma(counts, digits, eta, max_iter=opts.max_iter, tol=opts.tol, presence=True,
+                                              device=opts.device)["lr_absent"]
+        write_results(opts.output_dir or opts.run_dir, [names[k] for k in keep], counts, res)
+        write_eta(opts.output_dir or opts.run_dir, joint)
+        n_open = 0
+    else:
+        res = _lib.fit_gamma(counts, digits, eta, max_iter=opts.max_iter, tol=opts.tol, presence=opts.presence, device=opts.device)
+        write_results(opts.output_dir or opts.run_dir, [names[k] for k in keep], counts, res)
+        n_open = int((np.asarray(res["converged"]) == 0).sum())
     if n_open:
         print("desman-abund: %d of %d samples did not converge in %d steps (Projected_fit.csv: converged = 0)"
               % (n_open, len(keep), opts.max_iter), file=sys.stderr)

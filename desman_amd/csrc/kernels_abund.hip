@@ -51,11 +51,11 @@ struct AbundParams {
 };
 
 // this lane's rows of the staged tile.  KIND 0: N and the saturated log-likelihood; 1: one EM pass (acc_g += w of g's class; bad: a
-// cell with reads and p = 0); 2: L at gam
-template <int GP, int KIND>
-__device__ __forceinline__ void abund_rows(int n, int lane, const int4 *__restrict__ xS, const uint64_t *__restrict__ tS,
-                                           const double *__restrict__ etaS, const double2 *__restrict__ ltab, const double (&gam)[GP],
-                                           double (&acc)[GP], double &o0, double &o1, bool &bad)
+// cell with reads and p = 0); 2: L at gam.  ETA (with KIND 1, the joint fit of gamma and eta below): m[4 a + b] += c_a q_b as well
+template <int GP, int KIND, bool ETA>
+__device__ __forceinline__ void abund_rows_impl(int n, int lane, const int4 *__restrict__ xS, const uint64_t *__restrict__ tS,
+                                                const double *__restrict__ etaS, const double2 *__restrict__ ltab, const double (&gam)[GP],
+                                                double (&acc)[GP], double &o0, double &o1, bool &bad, double *__restrict__ m)
 {
     for (int i = lane; i < n; i += 64) {
         const int4 xi = xS[i];
@@ -100,8 +100,20 @@ __device__ __forceinline__ void abund_rows(int n, int lane, const int4 *__restri
                 const int d = (int)(t >> (2 * g)) & 3;
                 acc[g] += d == 0 ? w[0] : d == 1 ? w[1] : d == 2 ? w[2] : w[3];
             }
+            if (ETA) {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) m[k] = fma(c[k >> 2], q[k & 3], m[k]);
+            }
         }
     }
+}
+
+template <int GP, int KIND>
+__device__ __forceinline__ void abund_rows(int n, int lane, const int4 *__restrict__ xS, const uint64_t *__restrict__ tS,
+                                           const double *__restrict__ etaS, const double2 *__restrict__ ltab, const double (&gam)[GP],
+                                           double (&acc)[GP], double &o0, double &o1, bool &bad)
+{
+    abund_rows_impl<GP, KIND, false>(n, lane, xS, tS, etaS, ltab, gam, acc, o0, o1, bad, nullptr);
 }
 
 template <int GP, int NWMAX>
@@ -695,4 +707,344 @@ extern "C" int dsm_ctx_fit_gamma_interval(dsm_ctx *c, int G, const int64_t *tau,
         HIP_TRY(hipMemcpy(d_tau, packed.data(), (size_t)c->V * sizeof(uint64_t), hipMemcpyHostToDevice));
     }
     return abund_interval_run(c->cnt_vs, nullptr, c->V, c->S, G, tau ? d_tau.p : c->tau, eta, gamma_hat, q, max_iter, tol, ctol, lo, hi, flags);
+}
+
+// ---------------------------------------------------------------- the error matrix of new samples, fitted with gamma
+// tau fixed; gamma [S][G] and ONE eta [4][4] shared by the samples of the call maximise  L(gamma, eta) = sum_s sum_{v,b: x > 0} x ln p
+// by plain EM.  One step, from one E-step at (gamma, eta):  q_svb = x / p,
+//     gamma'_sg = gamma_sg / N_s sum_v w_{s,v,tau_vg}        (the fit's step),
+//     M[a][b] = eta[a][b] sum_s sum_v c_sva q_svb,           eta'[a][b] = M[a][b] / sum_b M[a][b]   (a row of sum 0 keeps its values).
+// The eta statistics couple the samples, so a step is a PAIR OF LAUNCHES on the stream and the loop is the host's:
+//   * abund_eta_step_kernel: a workgroup is one sample.  There are no presence fits, so the NW wavefronts of the workgroup SHARE the
+//     sample's positions: the workgroup stages the fit's LDS tiles, wavefront w takes the w-th contiguous slice of every tile (slices of
+//     ceil(n / (64 NW)) 64 positions of a tile of n), its lanes stride over the slice with the fit's arithmetic (abund_rows_impl) and add
+//     the 16 sums c_a q_b besides.  Lane totals meet in the xor butterfly, the wavefront totals in LDS, added in wavefront order by
+//     wavefront 0.  NW depends on the G class alone (8 / 8 / 8 / 4), so every sum has one order for a given V.
+//   * abund_eta_reduce_kernel: one wavefront adds the samples' 16 partial sums in sample order, forms eta', the step's delta and the
+//     device-side stop word (converged, dead, or max_iter reached).  Both kernels return at once when stop is set, so the host may
+//     enqueue steps in batches and read stop between batches: a step launched after stop changes nothing.
+//   * abund_eta_eval_kernel: N and the saturated model before the first step, L at the returned (gamma, eta) after the last, in the
+//     order of the fit's final pass (one wavefront per sample over the fit's tiles, abund_rows<GP, 2>).
+// No atomics; no launch depends on another workgroup of the same launch.
+enum { AE_STOP = 0, AE_ITERS, AE_CONV, AE_DEAD, AE_ROWS, AE_NCTRL = 8 };
+
+struct AbundEtaParams {
+    const int32_t *cnt;         // [S][V][4] sample-major, every sample of the call
+    const uint64_t *tau;        // [V] packed
+    const double *log_tab;      // [256][2]
+    int V, G, S, max_iter;
+    double tol;
+    double *gamma;              // [S][G] the current rows, updated in place by the sample's workgroup
+    double *eta;                // [16] the current matrix, updated by the reduce kernel
+    double *N, *Lsat, *ll;      // [S]
+    double *part;               // [S][16] sum_v c_a q_b of the step
+    double *delta;              // [S] max_g |gamma' - gamma| of the step
+    int32_t *bad;               // [S] a cell with reads and p = 0
+    int32_t *ctrl;              // [AE_NCTRL]
+};
+
+template <int GP, int NW>
+__global__ __launch_bounds__(NW * 64) void abund_eta_step_kernel(AbundEtaParams p)
+{
+    __shared__ int4 xS[DSM_ABUND_TILE];
+    __shared__ uint64_t tS[DSM_ABUND_TILE];
+    __shared__ double etaS[16];
+    __shared__ double redS[NW][GP + 16];
+    __shared__ int badS[NW];
+
+    if (p.ctrl[AE_STOP] != 0) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nthr = NW * 64;
+    const int V = p.V, G = p.G, s = blockIdx.x;
+    const double N = p.N[s];
+    if (N == 0.0) return;                                  // no reads: nothing for M (part, delta and bad stay 0), the row stays
+    const int4 *cnt4 = reinterpret_cast<const int4 *>(p.cnt) + (size_t)s * V;
+    double *grow = p.gamma + (size_t)s * G;
+
+    if (threadIdx.x < 16) etaS[threadIdx.x] = p.eta[threadIdx.x];
+    double gam[GP], acc[GP], m[16];
+#pragma unroll
+    for (int g = 0; g < GP; ++g) { gam[g] = g < G ? grow[g] : 0.0; acc[g] = 0.0; }
+#pragma unroll
+    for (int k = 0; k < 16; ++k) m[k] = 0.0;
+    double o0 = 0.0, o1 = 0.0; bool bad = false;
+
+    for (int t0 = 0; t0 < V; t0 += DSM_ABUND_TILE) {
+        __syncthreads();                                   // the previous tile has been read by every wavefront
+        const int n = min(DSM_ABUND_TILE, V - t0);
+        for (int i = threadIdx.x; i < n; i += nthr) { xS[i] = cnt4[t0 + i]; tS[i] = p.tau[t0 + i]; }
+        __syncthreads();
+        const int per = (n + nthr - 1) / nthr * 64, lo = min(n, wave * per), cnt = min(per, n - lo);
+        abund_rows_impl<GP, 1, true>(cnt, lane, xS + lo, tS + lo, etaS, nullptr, gam, acc, o0, o1, bad, m);
+    }
+#pragma unroll
+    for (int g = 0; g < GP; ++g) acc[g] = group_allreduce_sum<64>(acc[g]);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) m[k] = group_allreduce_sum<64>(m[k]);
+    const bool wbad = __ballot(bad) != 0ull;
+    if (lane == 0) {
+#pragma unroll
+        for (int g = 0; g < GP; ++g) redS[wave][g] = acc[g];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) redS[wave][GP + k] = m[k];
+        badS[wave] = wbad ? 1 : 0;
+    }
+    __syncthreads();                                       // (every wavefront has read its gamma row long before)
+    if (wave != 0) return;
+    bool anybad = false;
+    for (int w = 0; w < NW; ++w) anybad = anybad || badS[w] != 0;
+    if (anybad) { if (lane == 0) p.bad[s] = 1; return; }
+    // lane j: entry j of the wavefront totals, added in wavefront order -- j < GP: haplotype j, GP <= j < GP + 16: c_a q_b
+    double tot = 0.0, d = 0.0;
+    if (lane < GP + 16) {
+        tot = redS[0][lane];
+        for (int w = 1; w < NW; ++w) tot += redS[w][lane];
+    }
+    if (lane < G) {
+        const double g0 = grow[lane], gn = g0 > 0.0 ? g0 * tot / N : 0.0;
+        d = fabs(gn - g0);
+        grow[lane] = gn;
+    }
+    if (lane >= GP && lane < GP + 16) p.part[(size_t)s * 16 + (lane - GP)] = tot;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) d = fmax(d, __shfl_xor(d, off, 64));
+    if (lane == 0) p.delta[s] = d;
+}
+
+__global__ __launch_bounds__(64) void abund_eta_reduce_kernel(AbundEtaParams p)
+{
+    if (p.ctrl[AE_STOP] != 0) return;
+    const int lane = threadIdx.x, k = lane & 15, a = k >> 2, S = p.S;
+    int bad = 0;
+    double dg = 0.0;
+    for (int s = lane; s < S; s += 64) { bad |= p.bad[s]; dg = fmax(dg, p.delta[s]); }
+    if (__ballot(bad != 0) != 0ull) {                      // eta is shared: the whole call's fit is dead, nothing else is written
+        if (lane == 0) { p.ctrl[AE_DEAD] = 1; p.ctrl[AE_STOP] = 1; }
+        return;
+    }
+    double sum = 0.0;                                      // (lanes k, k + 16, k + 32, k + 48 hold the same entry)
+    for (int s = 0; s < S; ++s) sum += p.part[(size_t)s * 16 + k];
+    const double e0 = p.eta[k], M = e0 * sum;
+    const double rs = ((__shfl(M, 4 * a, 64) + __shfl(M, 4 * a + 1, 64)) + __shfl(M, 4 * a + 2, 64)) + __shfl(M, 4 * a + 3, 64);
+    const bool live = rs > 0.0;
+    const double en = live ? M / rs : e0;                  // a dead row keeps its values
+    double d = fmax(dg, fabs(en - e0));
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) d = fmax(d, __shfl_xor(d, off, 64));
+    const unsigned long long deadl = __ballot(!live);
+    if (lane < 16) p.eta[k] = en;
+    if (lane == 0) {
+        int rows = 0;
+        for (int r = 0; r < 4; ++r) rows |= (int)((deadl >> (4 * r)) & 1ull) << r;
+        const int iters = p.ctrl[AE_ITERS] + 1;
+        p.ctrl[AE_ITERS] = iters;
+        p.ctrl[AE_ROWS] |= rows;
+        if (p.tol > 0.0 && d < p.tol) { p.ctrl[AE_CONV] = 1; p.ctrl[AE_STOP] = 1; }
+        if (iters >= p.max_iter) p.ctrl[AE_STOP] = 1;
+    }
+}
+
+// MODE 0: N, the saturated model, the uniform start row and zeroed step outputs; MODE 1: L at (gamma, eta).  Wavefront 0 computes, in the
+// order of abund_kernel's passes; the other wavefronts of the workgroup help to stage the tiles.
+template <int GP, int MODE>
+__global__ __launch_bounds__(256) void abund_eta_eval_kernel(AbundEtaParams p)
+{
+    __shared__ int4 xS[DSM_ABUND_TILE];
+    __shared__ uint64_t tS[DSM_ABUND_TILE];
+    __shared__ double2 ltab[DSM_LOG_TAB_N];
+    __shared__ double etaS[16];
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int V = p.V, G = p.G, s = blockIdx.x;
+    const int4 *cnt4 = reinterpret_cast<const int4 *>(p.cnt) + (size_t)s * V;
+    for (int i = threadIdx.x; i < DSM_LOG_TAB_N; i += 256) ltab[i] = reinterpret_cast<const double2 *>(p.log_tab)[i];
+    if (threadIdx.x < 16) etaS[threadIdx.x] = p.eta[threadIdx.x];
+    double gam[GP], acc[GP];
+#pragma unroll
+    for (int g = 0; g < GP; ++g) { gam[g] = (MODE == 1 && g < G) ? p.gamma[(size_t)s * G + g] : 0.0; acc[g] = 0.0; }
+    double o0 = 0.0, o1 = 0.0; bool bad = false;
+    for (int t0 = 0; t0 < V; t0 += DSM_ABUND_TILE) {
+        __syncthreads();
+        const int n = min(DSM_ABUND_TILE, V - t0);
+        for (int i = threadIdx.x; i < n; i += 256) { xS[i] = cnt4[t0 + i]; tS[i] = p.tau[t0 + i]; }
+        __syncthreads();
+        if (wave == 0) abund_rows<GP, MODE == 0 ? 0 : 2>(n, lane, xS, tS, etaS, ltab, gam, acc, o0, o1, bad);
+    }
+    if (wave != 0) return;
+    o0 = group_allreduce_sum<64>(o0);
+    if (MODE == 0) {
+        o1 = group_allreduce_sum<64>(o1);
+        if (lane == 0) { p.N[s] = o0; p.Lsat[s] = o1; p.delta[s] = 0.0; p.bad[s] = 0; }
+        if (lane < 16) p.part[(size_t)s * 16 + lane] = 0.0;
+        if (lane < G) p.gamma[(size_t)s * G + lane] = 1.0 / (double)G;
+    } else if (lane == 0) p.ll[s] = o0;
+}
+
+static int g_abund_eta_batch = 0;            // dsm_abund_debug_set_eta_batch: steps enqueued between two reads of the stop word (0 = the default)
+static size_t g_abund_eta_stage_max = 0;     // dsm_abund_debug_set_eta_stage_max: bound of the sample-major copy in bytes (0 = 1 GiB)
+#define DSM_ABUND_ETA_BATCH 32               // 64 launches of a few microseconds per host read; a finished call idles through at most 31 steps
+
+extern "C" int dsm_abund_debug_set_eta_batch(int steps)
+{
+    if (steps < 0) { dsm_set_error("abund: eta batch %d", steps); return DSM_ERR_ARG; }
+    g_abund_eta_batch = steps;
+    return DSM_OK;
+}
+
+extern "C" int dsm_abund_debug_set_eta_stage_max(long long bytes)
+{
+    if (bytes < 0) { dsm_set_error("abund: eta stage bound %lld", bytes); return DSM_ERR_ARG; }
+    g_abund_eta_stage_max = (size_t)bytes;
+    return DSM_OK;
+}
+
+static int abund_eta_check(int V, int S, const double *eta0)
+{
+    for (int a = 0; a < 4; ++a) {
+        const double sum = ((eta0[4 * a] + eta0[4 * a + 1]) + eta0[4 * a + 2]) + eta0[4 * a + 3];
+        if (!(fabs(sum - 1.0) <= 1e-9)) { dsm_set_error("fit_gamma_eta: row %d of eta0 sums to %.17g", a, sum); return DSM_ERR_ARG; }
+    }
+    // every step reads every sample: the whole sample-major copy is staged at once (checked before anything is allocated)
+    const size_t bound = g_abund_eta_stage_max ? g_abund_eta_stage_max : (size_t)1 << 30;
+    if ((size_t)V * (size_t)S * 16 > bound) {
+        dsm_set_error("fit_gamma_eta: V=%d x S=%d needs a %zu B copy of the counts, above the bound of %zu B", V, S, (size_t)V * (size_t)S * 16, bound);
+        return DSM_ERR_UNSUPPORTED;
+    }
+    return DSM_OK;
+}
+
+template <int GP, int NW>
+static void abund_eta_launch_step(const AbundEtaParams &q)
+{
+    hipLaunchKernelGGL((abund_eta_step_kernel<GP, NW>), dim3((unsigned)q.S), dim3(NW * 64u), 0, 0, q);
+    hipLaunchKernelGGL(abund_eta_reduce_kernel, dim3(1), dim3(64), 0, 0, q);
+}
+
+template <int MODE>
+static void abund_eta_launch_eval(const AbundEtaParams &q, int GP)
+{
+    switch (GP) {
+    case 4: hipLaunchKernelGGL((abund_eta_eval_kernel<4, MODE>), dim3((unsigned)q.S), dim3(256), 0, 0, q); break;
+    case 8: hipLaunchKernelGGL((abund_eta_eval_kernel<8, MODE>), dim3((unsigned)q.S), dim3(256), 0, 0, q); break;
+    case 16: hipLaunchKernelGGL((abund_eta_eval_kernel<16, MODE>), dim3((unsigned)q.S), dim3(256), 0, 0, q); break;
+    default: hipLaunchKernelGGL((abund_eta_eval_kernel<32, MODE>), dim3((unsigned)q.S), dim3(256), 0, 0, q); break;
+    }
+}
+
+// as abund_run: d_cnt the resident tensor or null with h_cnt; d_tau the packed words on the device.  The arguments have been checked.
+static int abund_eta_run(const int32_t *d_cnt, const int64_t *h_cnt, int V, int S, int G, const uint64_t *d_tau, const double *eta0,
+                         int max_iter, double tol, double *gamma, double *eta, double *loglik, double *loglik0, double *deviance,
+                         int32_t *iters, int32_t *converged, int32_t *dead_rows, double *lr_eta)
+{
+    // the reference fit: eta held at eta0, the path of dsm_fit_gamma itself
+    {
+        std::vector<double> g0((size_t)S * G), dev0((size_t)S);
+        std::vector<int32_t> it0((size_t)S), cv0((size_t)S);
+        ABTRY(abund_run(d_cnt, h_cnt, V, S, G, d_tau, eta0, max_iter, tol, 0, g0.data(), loglik0, dev0.data(), it0.data(), cv0.data(), nullptr));
+    }
+    const int GP = G <= 4 ? 4 : G <= 8 ? 8 : G <= 16 ? 16 : 32;
+    DevBuf<int32_t> d_x, d_bad, d_ctrl; DevBuf<double> d_eta, d_ltab, d_gamma, d_N, d_Lsat, d_ll, d_part, d_delta;
+    ABTRY(d_x.alloc((size_t)S * V * 4)); ABTRY(d_bad.alloc(S)); ABTRY(d_ctrl.alloc(AE_NCTRL)); ABTRY(d_eta.alloc(16));
+    ABTRY(d_ltab.alloc(2 * DSM_LOG_TAB_N)); ABTRY(d_gamma.alloc((size_t)S * G)); ABTRY(d_N.alloc(S)); ABTRY(d_Lsat.alloc(S));
+    ABTRY(d_ll.alloc(S)); ABTRY(d_part.alloc((size_t)S * 16)); ABTRY(d_delta.alloc(S));
+    HIP_TRY(hipMemcpy(d_eta, eta0, 16 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ltab, dsm_log_table_host, sizeof dsm_log_table_host, hipMemcpyHostToDevice));
+    int32_t ctrl[AE_NCTRL] = {0};
+    ctrl[AE_STOP] = max_iter == 0 ? 1 : 0;
+    HIP_TRY(hipMemcpy(d_ctrl, ctrl, sizeof ctrl, hipMemcpyHostToDevice));
+    std::vector<int32_t> x32;
+    for (int s0 = 0; s0 < S; s0 += 1 << 15) {              // (the repack kernel's grid holds 65535 samples at the most)
+        const int n = std::min(1 << 15, S - s0);
+        ABTRY(abund_stage_chunk(d_cnt, h_cnt, V, S, s0, n, d_x.p + (size_t)s0 * V * 4, x32));
+    }
+    std::vector<int32_t>().swap(x32);
+    AbundEtaParams q{d_x, d_tau, d_ltab, V, G, S, max_iter, tol, d_gamma, d_eta, d_N, d_Lsat, d_ll, d_part, d_delta, d_bad, d_ctrl};
+    abund_eta_launch_eval<0>(q, GP);
+    HIP_TRY(hipGetLastError());
+    const int batch = g_abund_eta_batch > 0 ? g_abund_eta_batch : DSM_ABUND_ETA_BATCH;
+    while (ctrl[AE_STOP] == 0) {
+        for (int i = 0; i < batch; ++i)
+            switch (GP) {                                  // wavefronts per workgroup by the registers a lane needs
+            case 4: abund_eta_launch_step<4, 8>(q); break;
+            case 8: abund_eta_launch_step<8, 8>(q); break;
+            case 16: abund_eta_launch_step<16, 8>(q); break;
+            default: abund_eta_launch_step<32, 4>(q); break;
+            }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(ctrl, d_ctrl, sizeof ctrl, hipMemcpyDeviceToHost));
+    }
+    abund_eta_launch_eval<1>(q, GP);
+    HIP_TRY(hipGetLastError());
+    std::vector<double> Lsat((size_t)S);
+    HIP_TRY(hipMemcpy(gamma, d_gamma, (size_t)S * G * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(eta, d_eta, 16 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(loglik, d_ll, (size_t)S * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(Lsat.data(), d_Lsat, (size_t)S * sizeof(double), hipMemcpyDeviceToHost));
+    bool dead = ctrl[AE_DEAD] != 0;
+    for (int s = 0; s < S; ++s) dead = dead || !(loglik[s] > -INFINITY);       // (the final pass: max_iter = 0 on a table eta0 contradicts)
+    *iters = ctrl[AE_ITERS];
+    *dead_rows = ctrl[AE_ROWS];
+    if (dead) {
+        for (size_t i = 0; i < (size_t)S * G; ++i) gamma[i] = 0.0;
+        for (int s = 0; s < S; ++s) { loglik[s] = -INFINITY; deviance[s] = INFINITY; }
+        memcpy(eta, eta0, 16 * sizeof(double));
+        *converged = 0;
+        *lr_eta = NAN;
+        return DSM_OK;
+    }
+    *converged = ctrl[AE_CONV];
+    double L = 0.0, L0 = 0.0;
+    for (int s = 0; s < S; ++s) { deviance[s] = 2.0 * (Lsat[s] - loglik[s]); L += loglik[s]; L0 += loglik0[s]; }
+    const double lr = 2.0 * (L - L0);
+    *lr_eta = lr < 0.0 ? 0.0 : lr;                         // (eta0 is in the model: rounding, or a joint fit that max_iter ended early)
+    return DSM_OK;
+}
+
+extern "C" int dsm_fit_gamma_eta(int device, const int64_t *counts, int V, int S, int G, const int64_t *tau, const double *eta0,
+                                 int max_iter, double tol, double *gamma, double *eta, double *loglik, double *loglik0, double *deviance,
+                                 int32_t *iters, int32_t *converged, int32_t *dead_rows, double *lr_eta)
+{
+    if (S < 1 || !counts || !tau || !eta0 || !gamma || !eta || !loglik || !loglik0 || !deviance || !iters || !converged || !dead_rows || !lr_eta) {
+        dsm_set_error("fit_gamma_eta: bad arguments");
+        return DSM_ERR_ARG;
+    }
+    ABTRY(abund_check_model(V, G, eta0, max_iter, tol));
+    ABTRY(abund_eta_check(V, S, eta0));
+    ABTRY(abund_check_counts(counts, V, S));
+    std::vector<uint64_t> packed;
+    ABTRY(abund_pack_tau(tau, V, G, packed));
+    ABTRY(abund_bind_device(device));
+    DevBuf<uint64_t> d_tau;
+    ABTRY(d_tau.alloc((size_t)V));
+    HIP_TRY(hipMemcpy(d_tau, packed.data(), (size_t)V * sizeof(uint64_t), hipMemcpyHostToDevice));
+    return abund_eta_run(nullptr, counts, V, S, G, d_tau, eta0, max_iter, tol, gamma, eta, loglik, loglik0, deviance, iters, converged,
+                         dead_rows, lr_eta);
+}
+
+extern "C" int dsm_ctx_fit_gamma_eta(dsm_ctx *c, int G, const int64_t *tau, const double *eta0, int max_iter, double tol, double *gamma,
+                                     double *eta, double *loglik, double *loglik0, double *deviance, int32_t *iters, int32_t *converged,
+                                     int32_t *dead_rows, double *lr_eta)
+{
+    if (!c) { dsm_set_error("null context"); return DSM_ERR_ARG; }
+    if (!c->cnt_vs) { dsm_set_error("no count tensor: call dsm_ctx_set_counts first"); return DSM_ERR_STATE; }
+    if (!eta0 || !gamma || !eta || !loglik || !loglik0 || !deviance || !iters || !converged || !dead_rows || !lr_eta) {
+        dsm_set_error("ctx_fit_gamma_eta: null pointer");
+        return DSM_ERR_ARG;
+    }
+    ABTRY(abund_check_model(c->V, G, eta0, max_iter, tol));
+    ABTRY(abund_eta_check(c->V, c->S, eta0));
+    if (!tau && (!c->have_state || c->G != G)) {
+        dsm_set_error("ctx_fit_gamma_eta: no tau given and no resident state of G=%d haplotypes", G);
+        return DSM_ERR_STATE;
+    }
+    std::vector<uint64_t> packed;
+    if (tau) ABTRY(abund_pack_tau(tau, c->V, G, packed));
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));           // the resident tensors are read from the default stream below
+    DevBuf<uint64_t> d_tau;
+    if (tau) {
+        ABTRY(d_tau.alloc((size_t)c->V));
+        HIP_TRY(hipMemcpy(d_tau, packed.data(), (size_t)c->V * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    return abund_eta_run(c->cnt_vs, nullptr, c->V, c->S, G, tau ? d_tau.p : c->tau, eta0, max_iter, tol, gamma, eta, loglik, loglik0,
+                         deviance, iters, converged, dead_rows, lr_eta);
 }

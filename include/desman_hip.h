@@ -322,6 +322,49 @@ int dsm_ctx_fit_gamma_interval(dsm_ctx *ctx, int G, const int64_t *tau /*[V][G] 
                                const double *gamma_hat, double q, int max_iter, double tol, double ctol, double *lo, double *hi,
                                int32_t *flags);
 
+/* The error matrix of samples that were not in the fit, estimated with their abundances: tau is held fixed; the call
+ * fits gamma [S][G], one row per sample, and ONE eta [4][4] ([true][observed], rows summing to 1) shared by all samples of the call, by
+ * plain EM on
+ *     L(gamma, eta) = sum_s sum_{v,b: x > 0} x_svb ln p_svb,   p_svb = sum_a c_sva eta[a][b],   c_sva = sum_{g: tau_vg = a} gamma_sg
+ * (cells with x = 0 contribute exactly 0).  One step, from a single E-step at the current (gamma, eta):
+ *     q_svb = x_svb / p_svb where x > 0, else 0;        w_sva = sum_b q_svb eta[a][b];
+ *     gamma'_sg = gamma_sg / N_s sum_v w_{s,v,tau_vg}                                  (the step of dsm_fit_gamma),
+ *     M[a][b] = eta[a][b] sum_s sum_v c_sva q_svb   (the samples added in index order),  eta'[a][b] = M[a][b] / sum_b M[a][b]  (b in order).
+ *   A row a with sum_b M[a][b] = 0 (no haplotype of positive abundance carries base a anywhere) keeps its previous values; bit a of
+ *   dead_rows is set if that happened in any step of the call.
+ *   Start: every gamma row uniform, eta = eta0 (the run's Eta_star.csv).  Stop: the step with max(max |gamma' - gamma|, max |eta' - eta|) < tol,
+ *   or max_iter steps (tol = 0: exactly max_iter steps; max_iter = 0: eta0 and the uniform rows).  After the stop one pass evaluates L
+ *   per sample at the returned (gamma, eta), in the summation order of dsm_fit_gamma's final pass.  L does not decrease along the steps.
+ *     gamma [S][G], eta [16]   the estimate;     loglik [S], deviance [S]   as in dsm_fit_gamma, at the estimate
+ *     loglik0 [S]   the log-likelihood of the fit with eta held at eta0: what dsm_fit_gamma returns in loglik for the same counts, tau,
+ *                   eta = eta0, max_iter and tol (it is that call, the same bits)
+ *     iters, converged, dead_rows   one value each per call: steps taken; 1 if the stop test was met; the bit mask above
+ *     lr_eta        2 (sum_s loglik - sum_s loglik0), a negative value returned as 0: how much better the re-estimated eta explains the
+ *                   samples.  A likelihood-ratio statistic of "eta0 holds for these samples" on at most 12 free parameters, with a
+ *                   NOMINAL chi-square(12) reference: exact zeros in eta0 (EM keeps them) and dead rows lower the degrees of freedom,
+ *                   and gamma is re-fitted under both hypotheses.  A fit that max_iter ended early understates it.
+ * Degenerate operands: a sample without reads contributes nothing to M, keeps the start row and has loglik 0, deviance 0.  A cell with
+ * reads and p = 0 in any pass (exact zeros in eta0 that the counts contradict; at the uniform start as a rule, later when a gamma_sg
+ * underflows to 0) kills the whole call's fit, because eta is shared: every gamma row 0, every loglik -inf, every deviance +inf, converged
+ * 0, iters = the steps completed before, eta returned as eta0, lr_eta NaN; loglik0 is still returned per sample.  G = 1 is valid: the
+ * gamma step leaves 1 (to rounding, as in dsm_fit_gamma) and only eta moves.
+ * Limits: those of dsm_fit_gamma, S >= 1, and every row of eta0 sums to 1 within 1e-9 (DSM_ERR_ARG otherwise).  Every step reads every
+ * sample, so -- unlike dsm_fit_gamma -- the sample-major copy of ALL the counts is staged at once: V x S x 16 B above 1 GiB is
+ * DSM_ERR_UNSUPPORTED (checked before anything is allocated); dsm_abund_debug_set_chunk does not apply to the joint fit (it does to the
+ * loglik0 fit, whose results do not depend on it).  The host enqueues the steps in batches of 32 and reads the device's stop word
+ * between batches; a step launched after the stop changes nothing, so the results do not depend on the batch size.  No atomics, every
+ * sum has one order: the results are the same bits from run to run and from both entry points (dsm_ctx_fit_gamma_eta: the resident
+ * counts, tau given or -- NULL -- resident; the chain state is not touched).                                                          */
+int dsm_fit_gamma_eta(int device, const int64_t *counts /*[V][S][4]*/, int V, int S, int G, const int64_t *tau /*[V][G] digits*/,
+                      const double *eta0, int max_iter, double tol, double *gamma, double *eta, double *loglik, double *loglik0,
+                      double *deviance, int32_t *iters, int32_t *converged, int32_t *dead_rows, double *lr_eta);
+int dsm_ctx_fit_gamma_eta(dsm_ctx *ctx, int G, const int64_t *tau /*[V][G] digits or NULL*/, const double *eta0, int max_iter, double tol,
+                          double *gamma, double *eta, double *loglik, double *loglik0, double *deviance, int32_t *iters,
+                          int32_t *converged, int32_t *dead_rows, double *lr_eta);
+/* test hooks: steps per batch of the two calls above (0 = the default, 32); the bound of their sample-major copy in bytes (0 = 1 GiB) */
+int dsm_abund_debug_set_eta_batch(int steps);
+int dsm_abund_debug_set_eta_stage_max(long long bytes);
+
 /* ------------------------------------------------------------------------ */
 /* f4: accessory-gene assignment (desman/Eta_Sampler.py, desman/GeneAssign.py) */
 /* C genes, gene c owns the rows gene_off[c]..gene_off[c+1]-1 of one           */
