@@ -6,6 +6,8 @@ are fetched from HBM only when asked for (tau_store is materialised lazily).
 assignTau (dead in the reference's CLI, bin/desman:213-214) runs on the device as an
 exact enumeration of the 4^G joint states (dsm_assign_tau, G <= 10); the tauStates
 table it walks upstream is never built.
+update_fixed_tau (the reduced runs of the reference's Chib estimators, :409-428)
+runs on the device as well (dsm_ctx_gibbs_update_fixed_tau).
 Not mirrored (never reached by the CLI): the pure-Python
 samplers, Chib marginal likelihood, DIC.
 """
@@ -14,6 +16,7 @@ import logging
 import numpy as np
 
 from . import _lib
+from . import fixed_tau as _fixed_tau
 from . import sampletau as _sampletau
 
 
@@ -176,6 +179,19 @@ class HaploSNP_Sampler:
         self._collect(prefix='nll', keep_gamma_eta=True)
         self.gamma_store, self.eta_store = gs, es
 
+    def update_fixed_tau(self, fix_eta=False, pool=-1):
+        """max_iter iterations with tau held (HaploSNP_Sampler.py:409-428): sampleMu, sampleGamma, sampleEta and logPosterior per
+        iteration, on the device (dsm_ctx_gibbs_update_fixed_tau).  Fills gamma_store, eta_store, ll_store, lp_store, the star state and
+        lp; tau is unchanged and the GSL stream of the tau draws is not consumed.  The reference also keeps mu_store and E_store, the
+        auxiliary counts of every iteration: they are not kept here (the sums live on the device for one iteration only).
+        fix_eta: eta is held as well.  pool: 0 = on the table as it is, 1 = on the counts pooled per distinct tau word (the same law,
+        other draws), -1 = pooled where that makes the table smaller."""
+        self._push_state()
+        self._bind_rng()
+        self._ctx.gibbs_update_fixed_tau(self.max_iter, fix_eta=fix_eta, pool=pool)
+        self._release_rng()
+        self._collect(prefix='nlp')
+
     def _collect(self, prefix, keep_gamma_eta=False):
         tr = self._ctx.get_trace()
         n = self.max_iter
@@ -285,6 +301,19 @@ class HaploSNP_Sampler:
         else:
             res.update(_lib.fit_gamma_interval(snps, tau, eta, res["gamma"], device=self._device, **kw))
         return res
+
+    def posteriorGamma(self, snps=None, tau=None, eta=None, n_iter=1000, burn=200, fix_eta=True, level=0.95,
+                       seed=_fixed_tau.POSTERIOR_SEED, pool=-1):
+        """the counterpart of fitGamma under the chain's Dirichlet prior: the posterior of the abundances of the samples of snps [V,S',4]
+        -- default: the chain's own counts -- with tau (default tau_star) held and eta (default eta_star) held or, with fix_eta=False,
+        sampled from it as the start.  A chain of its own (uniform gamma rows, stream key ``seed``: the same call gives the same bits;
+        the sampler's chain and streams are not touched).  Dict of mean, sd, lo, med, hi [S',G] (quantiles (1 - level) / 2, 0.5,
+        1 - (1 - level) / 2 of the kept draws), draws [n_iter - burn, S', G], ll, and eta_mean / eta_sd / eta_draws with fix_eta=False."""
+        tau = self.tau_star if tau is None else tau
+        eta = self.eta_star if eta is None else eta
+        snps = self.variants if snps is None else snps
+        return _fixed_tau.posterior_gamma(snps, tau, eta, n_iter=n_iter, burn=burn, fix_eta=fix_eta, level=level, seed=seed, pool=pool,
+                                          alpha=self.alpha_constant, delta=self.delta_constant, epsilon=self.epsilon, device=self._device)
 
     def calculateSND(self, tau):
         """pairwise single-nucleotide differences between haplotypes (:712-730)."""

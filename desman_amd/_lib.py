@@ -79,6 +79,9 @@ SIGNATURES = {
     "dsm_ctx_draw_gamma_eta": (_i, [_vp, C.c_uint32, _u64p, _u64p, _f64p, _f64p]),
     "dsm_ctx_loglik": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),
     "dsm_ctx_gibbs_update": (_i, [_vp, _i]),
+    "dsm_ctx_gibbs_update_fixed_tau": (_i, [_vp, _i, _i, _i]),
+    "dsm_ctx_debug_fixtau_pool": (_i, [_vp, C.POINTER(_i), _vp, _vp, _vp]),
+    "dsm_ctx_debug_fixtau_sample_stats": (_i, [_vp, C.c_uint32, _u64p, _u64p]),
     "dsm_ctx_get_counters": (_i, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "dsm_ctx_set_counters": (_i, [_vp, C.c_uint64, C.c_uint32]),
     "dsm_ctx_get_screen_state": (_i, [_vp, _u32p]),
@@ -650,6 +653,29 @@ class Context:
     def gibbs_update(self, n_iter):
         check(self.lib.dsm_ctx_gibbs_update(self._h, int(n_iter)))
         self.n_trace = int(n_iter)
+
+    def gibbs_update_fixed_tau(self, n_iter, fix_eta=False, pool=-1):
+        """n_iter iterations of the chain with tau held (include/desman_hip.h: dsm_ctx_gibbs_update_fixed_tau): results as after
+        gibbs_update.  fix_eta: eta is held too.  pool: 0 = on the table as it is, 1 = on the counts pooled per distinct tau word,
+        -1 = pooled where that makes the table smaller."""
+        check(self.lib.dsm_ctx_gibbs_update_fixed_tau(self._h, int(n_iter), 1 if fix_eta else 0, int(pool)))
+        self.n_trace = int(n_iter)
+
+    def debug_fixtau_pool(self):
+        """the pooled table of the resident state: dict of W, pooled [W,S,4] int32, words [W] uint64 ascending, row [V] int32"""
+        w = _i(0)
+        pooled = np.zeros((self.V, self.S, 4), dtype=np.int32)
+        words = np.zeros(self.V, dtype=np.uint64)
+        row = np.zeros(self.V, dtype=np.int32)
+        check(self.lib.dsm_ctx_debug_fixtau_pool(self._h, C.byref(w), _ptr(pooled), _ptr(words), _ptr(row)))
+        return dict(W=w.value, pooled=pooled[:w.value].copy(), words=words[:w.value].copy(), row=row)
+
+    def debug_fixtau_sample_stats(self, it):
+        """sample_stats(it) drawn on the pooled state of the resident one"""
+        mu = np.zeros((self.S, self.G), dtype=np.uint64)
+        E = np.zeros((4, 4), dtype=np.uint64)
+        check(self.lib.dsm_ctx_debug_fixtau_sample_stats(self._h, int(it), mu, E))
+        return mu, E
 
     def gibbs_update_sharded(self, n_iter, v_offset, v_total, exchange):
         """n_iter iterations of ONE chain sharded by positions (include/desman_hip.h: dsm_ctx_gibbs_update_sharded): this context

@@ -1,7 +1,8 @@
 """`desman-abund`: abundances of a finished run's haplotypes in samples that were not in the fit.
 
     python -m desman_amd.abund <run_dir> <table.freq> [-o DIR] [--tau FILE] [--only-new] [--presence] [--interval [LEVEL]] [--ctol X]
-                                                      [--fit-eta] [--max-iter N] [--tol X] [--device N]
+                                                      [--fit-eta] [--posterior [N]] [--burn B] [--posterior-seed X]
+                                                      [--max-iter N] [--tol X] [--device N]
 
 `desman` drops every sample whose mean depth is not above -m, and a sample sequenced after the fit has no row in ``Gamma_star.csv``
 either; a refit would give new haplotypes with new labels.  This entry point holds the run's haplotypes and error matrix fixed and
@@ -19,6 +20,13 @@ Position) and writes
                              found to --ctol) and its flag bits: 1 lo is the boundary 0, 2 hi is the boundary 1, 4 an inner fit
                              ended at --max-iter (the interval is too narrow)
 
+    Projected_posterior.csv  with --posterior [N] (default 1000 iterations, the first --burn B = 200 dropped): per sample and haplotype
+                             <g>_mean, <g>_sd, <g>_lo, <g>_med, <g>_hi of the abundance's posterior under the run's Dirichlet prior
+                             (alpha = 0.1) with the haplotypes held (dsm_ctx_gibbs_update_fixed_tau); lo / hi at the level of
+                             --interval when given, else 0.95.  --posterior-seed X keys the chain's streams: the same call writes
+                             the same file.  Where the profile interval of an absent haplotype says lo = 0 and no more, this says
+                             how much abundance the data still allow.
+
 With --fit-eta the error matrix is not the run's: the samples may come from another library preparation, sequencer or mapper than the
 fit's.  One error matrix shared by the samples of the call is estimated together with their abundances, from ``Eta_star.csv`` as the
 start (dsm_fit_gamma_eta); Projected_Gamma.csv and Projected_fit.csv then hold the joint fit's rows (iters and converged are the
@@ -28,6 +36,8 @@ fitted matrix, and two more files are written:
     Projected_Eta.csv        the fitted error matrix, in the format of Eta_star.csv
     Projected_eta_fit.csv    one row: loglik, loglik_eta0 (both summed over the samples), lr_eta = 2 (loglik - loglik_eta0), iters,
                              converged, dead_rows (bit a: no haplotype with abundance carries base a, row a is the run's)
+    Projected_Eta_posterior.csv   with --posterior: the chain samples the error matrix too, from the fitted one as its start; per
+                             true base (row) <b>_mean and <b>_sd of the posterior of eta[row, b]
 """
 import argparse
 import os
@@ -38,6 +48,7 @@ import pandas as pd
 
 from .Output_Results import rchop
 
+POSTERIOR_N, POSTERIOR_BURN, POSTERIOR_SEED = 1000, 200, 0x8C1F3A5D7E9B2468      # fixed_tau.POSTERIOR_SEED
 MAX_ITER, TOL, CTOL = 20000, 1.0e-9, 1.0e-6          # _lib.FIT_MAX_ITER / FIT_TOL / FIT_CTOL (the parser must not need the library)
 TAU_FILES = ("Collated_Tau_star.csv", "Filtered_Tau_star.csv")
 
@@ -55,6 +66,13 @@ def build_parser():
                     help="also write the profile-likelihood intervals of the abundances at this confidence level (default 0.95)")
     ap.add_argument("--fit-eta", action="store_true",
                     help="estimate one error matrix for the samples of the table together with their abundances (start: Eta_star.csv)")
+    ap.add_argument("--posterior", type=int, nargs="?", const=POSTERIOR_N, default=None, metavar="N",
+                    help="also write the posterior of the abundances under the run's Dirichlet prior, from N iterations of the "
+                         "fixed-haplotype chain (default %d); with --fit-eta the chain samples the error matrix too" % POSTERIOR_N)
+    ap.add_argument("--burn", type=int, default=POSTERIOR_BURN, metavar="B",
+                    help="iterations of --posterior dropped at the start (default %d)" % POSTERIOR_BURN)
+    ap.add_argument("--posterior-seed", type=lambda v: int(v, 0), default=POSTERIOR_SEED, metavar="X",
+                    help="stream key of the --posterior chain (default 0x%X)" % POSTERIOR_SEED)
     ap.add_argument("--ctol", type=float, default=CTOL, help="width to which an interval end is found (default %g)" % CTOL)
     ap.add_argument("--max-iter", type=int, default=MAX_ITER, help="EM steps at most (default %d)" % MAX_ITER)
     ap.add_argument("--tol", type=float, default=TOL, help="stop when no abundance moves by this much in a step (default %g)" % TOL)
@@ -177,10 +195,30 @@ def write_interval(out_dir, names, iv):
     pd.DataFrame(cols, index=names).to_csv(os.path.join(out_dir, "Projected_interval.csv"))
 
 
+def write_posterior(out_dir, names, post):
+    """Projected_posterior.csv: rows and haplotype names of Projected_Gamma.csv, five columns per haplotype"""
+    cols = {}
+    for g in range(post["mean"].shape[1]):
+        for key in ("mean", "sd", "lo", "med", "hi"):
+            cols["%d_%s" % (g, key)] = post[key][:, g]
+    pd.DataFrame(cols, index=names).to_csv(os.path.join(out_dir, "Projected_posterior.csv"))
+
+
+def write_eta_posterior(out_dir, post):
+    """Projected_Eta_posterior.csv: rows of Eta_star.csv (true base), <b>_mean and <b>_sd per observed base"""
+    cols = {}
+    for b in range(4):
+        cols["%d_mean" % b] = post["eta_mean"][:, b]
+        cols["%d_sd" % b] = post["eta_sd"][:, b]
+    pd.DataFrame(cols).to_csv(os.path.join(out_dir, "Projected_Eta_posterior.csv"))
+
+
 def main(argv=None):
     opts = build_parser().parse_args(argv)
     if opts.interval is not None and not 0.0 < opts.interval < 1.0:
         sys.exit("desman-abund: --interval needs a level between 0 and 1")
+    if opts.posterior is not None and not (opts.posterior >= 1 and 0 <= opts.burn < opts.posterior):
+        sys.exit("desman-abund: --posterior needs N >= 1 iterations and 0 <= --burn < N")
     contigs, positions, digits, eta = load_model(opts.run_dir, opts.tau)
     if not os.path.isfile(opts.freq_file):
         sys.exit("desman-abund: can't open '%s'" % opts.freq_file)
@@ -231,6 +269,15 @@ def main(argv=None):
             print("desman-abund: an inner fit of %d of %d samples ended at --max-iter %d, their intervals are too narrow "
                   "(Projected_interval.csv: flag bit 4): %s" % (len(short), len(keep), opts.max_iter, ", ".join(short)), file=sys.stderr)
         res.update(iv)
+    if opts.posterior is not None:
+        from . import fixed_tau
+        post = fixed_tau.posterior_gamma(counts, digits, eta, n_iter=opts.posterior, burn=opts.burn, fix_eta=not opts.fit_eta,
+                                         level=0.95 if opts.interval is None else opts.interval, seed=opts.posterior_seed,
+                                         device=opts.device)
+        write_posterior(opts.output_dir or opts.run_dir, [names[k] for k in keep], post)
+        if opts.fit_eta:
+            write_eta_posterior(opts.output_dir or opts.run_dir, post)
+        res["posterior"] = post
     return res
 
 

@@ -214,11 +214,13 @@ static void free_traces(dsm_ctx *c)
     c->in_cap = 0;
     c->n_trace = 0;
     c->trace_cap = 0;
+    c->tau_fixed_trace = false;
 }
 
 extern "C" int dsm_ctx_destroy(dsm_ctx *c)
 {
     if (!c) return DSM_OK;
+    if (c->fixtau_child) { dsm_ctx_destroy(c->fixtau_child); c->fixtau_child = nullptr; }
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     collect_spans(c);
@@ -792,6 +794,7 @@ static int alloc_traces(dsm_ctx *c, int n)
         n = want;
     }
     c->n_trace = n;
+    c->tau_fixed_trace = false;             // (the fixed-tau chain sets it after this call)
     return DSM_OK;
 }
 
@@ -1130,6 +1133,206 @@ extern "C" int dsm_batch_update_tau(dsm_ctx *const *ctxs, int K, int n_iter, con
     return update_tau(ctxs, K, true, n_iter, gamma_stores, eta_stores);
 }
 
+// ---------------------------------------------------------------- the chain with tau held (HaploSNP_Sampler.py:409-428, update_fixed_tau)
+// Per iteration: the mu/E pass at (tau, gamma, eta), the Dirichlet launch (gamma_new, eta_new, traces, prior terms; it finalizes the
+// previous iteration), the likelihood-only pass at (tau, gamma_new, eta_new).  No sweep: no MT19937 word is generated or consumed, tau is
+// stored once (slot 0 of the trace stands for every iteration: dsm_host.h, tau_fixed_trace).  fix_eta: the E sums and the eta draw are
+// still made, but the chain's eta, the trace rows, the prior terms and the likelihood all stay at the matrix the call came in with.
+static int fixed_tau_loop(dsm_ctx *c, int n_iter, bool fix_eta)
+{
+    const int spec = stats_spec(c);
+    const bool agg = spec >= 2;
+    const bool fuse_s2 = agg && c->G < 10;
+    const size_t sg = (size_t)c->S * c->G;
+    TRY(alloc_traces(c, n_iter));
+    c->tau_fixed_trace = true;
+    HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
+    HIP_TRY(hipMemsetAsync(c->sum_mu, 0, sg * sizeof(unsigned long long), c->stream));
+    TRY(esum_reset(c));                                                        // Esum and every partial copy of it (a failed pass may have left counts there)
+    TRY(eval_state(c, c->gamma, c->eta, c->tau_trace, 1));                     // entry state: ll, lp, storeStarState(0); tau -> slot 0
+    TRY(stats_ensure_ntab(c));
+    Scratch<double> held;                                                      // fix_eta: the four prior terms of the held matrix
+    if (fix_eta && n_iter > 0) {
+        TRY(held.alloc((size_t)c->S + 4));
+        TRY(k_prior(c, c->gamma, c->eta, held));
+        TRY(k_fixtau_fill_eta(c, c->eta, c->eta_trace, n_iter));
+    }
+    int nb_prev = 0;
+    for (int it = 0; it < n_iter; ++it) {
+        const uint32_t ic = c->iter_ctr++;
+        TRY(agg ? k_stats_stage1(c, ic) : k_stats_v1(c, ic));
+        if (agg && !fuse_s2) TRY(k_stats_stage2(c, ic));
+        TRY(k_dirichlet(c, ic, c->gamma, c->gamma_trace + (size_t)it * sg, c->eta_new, fix_eta ? nullptr : c->eta_trace + (size_t)it * 16,
+                        prior_slot(c, it), it - 1, nb_prev, prior_slot(c, it - 1), fuse_s2 ? 1 : 0));
+        if (fix_eta) HIP_TRY(hipMemcpyAsync(prior_slot(c, it) + c->S, held.p + c->S, 4 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        else std::swap(c->eta, c->eta_new);
+        TRY(k_tau_sweep(c, 2, c->gamma, c->eta, c->eta, nullptr, nullptr, 0, &nb_prev, nullptr));
+    }
+    const bool want_rare = n_iter > 0 && c->tau_neartie_mode == -1;             // as the Gibbs loop: what the next call's choice of sweep goes by
+    if (want_rare && !c->h_rare) HIP_TRY(hipHostMalloc((void **)&c->h_rare, sizeof(int), hipHostMallocDefault));
+    if (n_iter > 0)
+        TRY(k_finalize(c, nb_prev, n_iter - 1, 0, prior_slot(c, n_iter - 1), c->gamma_trace + (size_t)(n_iter - 1) * sg,
+                       c->eta_trace + (size_t)(n_iter - 1) * 16, 0, want_rare ? c->h_rare : nullptr));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (want_rare) c->tau_rare_n = *c->h_rare;
+    return DSM_OK;
+}
+
+// The distinct packed tau words of the resident state in ascending order, and the row of each position's word.  overflow: a pooled
+// cell, or the four pooled cells of one (word, sample) together -- the depth dsm_ctx_set_counts bounds --, would pass INT32_MAX.
+struct FixtauWords { std::vector<uint64_t> words; std::vector<int32_t> row; bool overflow = false; };
+
+static int fixtau_words(dsm_ctx *c, FixtauWords *p)
+{
+    const int V = c->V, S = c->S;
+    std::vector<uint64_t> t((size_t)V);
+    HIP_TRY(hipMemcpyAsync(t.data(), c->tau, (size_t)V * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    p->words = t;
+    std::sort(p->words.begin(), p->words.end());
+    p->words.erase(std::unique(p->words.begin(), p->words.end()), p->words.end());
+    p->row.resize((size_t)V);
+    for (int v = 0; v < V; ++v) p->row[v] = (int32_t)(std::lower_bound(p->words.begin(), p->words.end(), t[v]) - p->words.begin());
+    p->overflow = false;
+    if (c->max_depth <= (uint64_t)INT32_MAX) return DSM_OK;        // a sample's reads over ALL positions fit: so does every pooled cell
+    std::vector<int32_t> cnt((size_t)V * S * 4);
+    HIP_TRY(hipMemcpyAsync(cnt.data(), c->cnt_vs, cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<int64_t> dep(p->words.size() * (size_t)S, 0);
+    for (int v = 0; v < V && !p->overflow; ++v)
+        for (int s = 0; s < S; ++s) {
+            const int32_t *x = cnt.data() + ((size_t)v * S + s) * 4;
+            int64_t &d = dep[(size_t)p->row[v] * S + s];
+            d += (int64_t)x[0] + x[1] + x[2] + x[3];
+            if (d > (int64_t)INT32_MAX) { p->overflow = true; break; }
+        }
+    return DSM_OK;
+}
+
+// pooled [W][S][4] on the device: zeroed, then fixtau_pool_kernel
+static int fixtau_pool_counts(dsm_ctx *c, const FixtauWords &p, Scratch<int32_t> &d_pooled)
+{
+    const size_t np = p.words.size() * (size_t)c->S * 4;
+    Scratch<int32_t> d_row;
+    TRY(d_row.alloc((size_t)c->V));
+    TRY(d_pooled.alloc(np));
+    HIP_TRY(hipMemcpyAsync(d_row, p.row.data(), (size_t)c->V * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(d_pooled, 0, np * sizeof(int32_t), c->stream));
+    TRY(k_fixtau_pool(c, d_row, d_pooled));
+    HIP_TRY(hipStreamSynchronize(c->stream));                   // (d_row is released on return)
+    return DSM_OK;
+}
+
+// The scratch chain of the pooled form: a context of W positions -- the pooled counts, the W words -- with the caller's gamma, eta, priors,
+// stream key, iteration counter and mu/E choice.  It is loaded through dsm_ctx_set_counts / dsm_ctx_set_state, so it IS the chain a caller
+// would set up on the pooled table (the test contract), its data constant included.
+static int fixtau_enter(dsm_ctx *c, const FixtauWords &p, dsm_ctx **child_out)
+{
+    const int W = (int)p.words.size(), S = c->S, G = c->G;
+    Scratch<int32_t> d_pooled;
+    TRY(fixtau_pool_counts(c, p, d_pooled));
+    const size_t np = (size_t)W * S * 4;
+    std::vector<int32_t> h32(np);
+    std::vector<double> gamma((size_t)S * G), eta(16);
+    HIP_TRY(hipMemcpyAsync(h32.data(), d_pooled, np * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(gamma.data(), c->gamma, gamma.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(eta.data(), c->eta, 16 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<int64_t> h64(h32.begin(), h32.end());
+    std::vector<int64_t> onehot((size_t)W * G * 4, 0);
+    for (int w = 0; w < W; ++w)
+        for (int g = 0; g < G; ++g) onehot[((size_t)w * G + g) * 4 + ((p.words[w] >> (2 * g)) & 3)] = 1;
+    if (!c->fixtau_child) TRY(dsm_ctx_create(&c->fixtau_child, c->device));
+    dsm_ctx *k = c->fixtau_child;
+    TRY(dsm_ctx_set_counts(k, h64.data(), W, S));
+    TRY(dsm_ctx_set_priors(k, c->alpha, c->delta, c->epsilon));
+    TRY(dsm_ctx_set_state(k, onehot.data(), gamma.data(), eta.data(), G));
+    k->ctr_seed = c->ctr_seed; k->iter_ctr = c->iter_ctr;
+    k->force_stats_spec = c->force_stats_spec; k->tau_neartie_mode = c->tau_neartie_mode; k->tau_screen = c->tau_screen;
+    *child_out = k;
+    return DSM_OK;
+}
+
+extern "C" int dsm_ctx_gibbs_update_fixed_tau(dsm_ctx *c, int n_iter, int fix_eta, int pool)
+{
+    if (n_iter < 0) { dsm_set_error("n_iter < 0"); return DSM_ERR_ARG; }
+    if (pool < -1 || pool > 1) { dsm_set_error("gibbs_update_fixed_tau: pool -1 (auto), 0 or 1"); return DSM_ERR_ARG; }
+    TRY(need(c, true, true));
+    BIND(c);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream_rng));
+    bool pooled = false;
+    FixtauWords p;
+    if (pool != 0) {
+        TRY(fixtau_words(c, &p));
+        if (p.overflow && pool == 1) { dsm_set_error("gibbs_update_fixed_tau: a pooled count would pass 2^31-1 (run with pool = 0 or -1)"); return DSM_ERR_UNSUPPORTED; }
+        // auto: pooling is one pass over the table, less than one iteration's mu/E pass, so any reduction counts as worth it (not measured where it stops paying: DESIGN.md sec. 8c)
+        pooled = !p.overflow && (pool == 1 || (int)p.words.size() < c->V);
+    }
+    if (!pooled) return fixed_tau_loop(c, n_iter, fix_eta != 0);
+    dsm_ctx *k = nullptr;
+    TRY(fixtau_enter(c, p, &k));
+    TRY(fixed_tau_loop(k, n_iter, fix_eta != 0));                              // (returns with the child's stream drained)
+    // back to the caller: gamma, eta, traces, MAP record, iteration counter; its counts and tau were only read
+    const size_t sg = (size_t)c->S * c->G, n = (size_t)n_iter;
+    TRY(alloc_traces(c, n_iter));
+    c->tau_fixed_trace = true;
+    auto d2d = [&](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream) : hipSuccess; };
+    HIP_TRY(d2d(c->tau_trace, c->tau, (size_t)c->V * sizeof(uint64_t)));
+    HIP_TRY(d2d(c->gamma, k->gamma, sg * sizeof(double)));
+    HIP_TRY(d2d(c->eta, k->eta, 16 * sizeof(double)));
+    HIP_TRY(d2d(c->gamma_trace, k->gamma_trace, n * sg * sizeof(double)));
+    HIP_TRY(d2d(c->eta_trace, k->eta_trace, n * 16 * sizeof(double)));
+    HIP_TRY(d2d(c->ll_trace, k->ll_trace, n * sizeof(double)));
+    HIP_TRY(d2d(c->lp_trace, k->lp_trace, n * sizeof(double)));
+    HIP_TRY(d2d(c->nchange_trace, k->nchange_trace, n * sizeof(int)));
+    HIP_TRY(d2d(c->star, k->star, 2 * sizeof(double)));
+    HIP_TRY(d2d(c->gamma_star, k->gamma_star, sg * sizeof(double)));
+    HIP_TRY(d2d(c->eta_star, k->eta_star, 16 * sizeof(double)));
+    HIP_TRY(d2d(c->scalars, k->scalars, 2 * sizeof(double)));
+    // the multinomial coefficients of the caller's table minus the pooled table's: every reported ll / lp is the caller's table's
+    TRY(k_fixtau_add_const(c, n_iter, c->ll_const - k->ll_const));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->iter_ctr = k->iter_ctr;
+    c->tau_rare_n = k->tau_rare_n;
+    return DSM_OK;
+}
+
+// test hook: the pooled table the call above would run on for the resident state -- *W words, pooled [W][S][4] (room for [V][S][4]),
+// words [W] ascending (room for V), row [V].  Any pointer may be null.
+extern "C" int dsm_ctx_debug_fixtau_pool(dsm_ctx *c, int *W, int32_t *pooled, uint64_t *words, int32_t *row)
+{
+    TRY(need(c, true, true));
+    BIND(c);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    FixtauWords p;
+    TRY(fixtau_words(c, &p));
+    if (p.overflow) { dsm_set_error("debug_fixtau_pool: a pooled count would pass 2^31-1"); return DSM_ERR_UNSUPPORTED; }
+    if (W) *W = (int)p.words.size();
+    if (words) memcpy(words, p.words.data(), p.words.size() * sizeof(uint64_t));
+    if (row) memcpy(row, p.row.data(), p.row.size() * sizeof(int32_t));
+    if (pooled) {
+        Scratch<int32_t> d;
+        TRY(fixtau_pool_counts(c, p, d));
+        HIP_TRY(hipMemcpy(pooled, d, p.words.size() * (size_t)c->S * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    return DSM_OK;
+}
+
+// test hook: dsm_ctx_sample_stats on the pooled state of the resident one (the caller's state and counters are untouched)
+extern "C" int dsm_ctx_debug_fixtau_sample_stats(dsm_ctx *c, uint32_t iter, uint64_t *sum_mu, uint64_t *esum)
+{
+    TRY(need(c, true, true));
+    BIND(c);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    FixtauWords p;
+    TRY(fixtau_words(c, &p));
+    if (p.overflow) { dsm_set_error("debug_fixtau_sample_stats: a pooled count would pass 2^31-1"); return DSM_ERR_UNSUPPORTED; }
+    dsm_ctx *k = nullptr;
+    TRY(fixtau_enter(c, p, &k));
+    return dsm_ctx_sample_stats(k, iter, sum_mu, esum);
+}
+
 extern "C" int dsm_release_device_caches(void)
 {
     // what the library keeps per process and device beyond the life of a context: the MT19937 jump tables (2 x 50 MB per device, built by the
@@ -1234,7 +1437,7 @@ extern "C" int dsm_ctx_get_star(dsm_ctx *c, int64_t *tau_star, double *gamma_sta
     HIP_TRY(hipMemcpyAsync(st, c->star, sizeof st, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const int slot = (int)st[1];
-    if (tau_star) TRY(fetch_tau(c, c->tau_trace + (size_t)slot * c->V, tau_star));
+    if (tau_star) TRY(fetch_tau(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)slot * c->V), tau_star));
     if (gamma_star) HIP_TRY(hipMemcpyAsync(gamma_star, c->gamma_star, (size_t)c->S * c->G * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (eta_star) HIP_TRY(hipMemcpyAsync(eta_star, c->eta_star, 16 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1249,6 +1452,11 @@ extern "C" int dsm_ctx_get_tau_sum(dsm_ctx *c, int64_t *tau_sum)
     if (!c->tau_trace || !tau_sum) { dsm_set_error("get_tau_sum: no update has run"); return DSM_ERR_STATE; }
     BIND(c);
     const size_t nt = (size_t)c->V * c->G * 4;
+    if (c->tau_fixed_trace) {                 // every stored iteration holds the tau of slot 0
+        TRY(fetch_tau(c, c->tau_trace, tau_sum));
+        for (size_t i = 0; i < nt; ++i) tau_sum[i] *= c->n_trace;
+        return DSM_OK;
+    }
     Scratch<int64_t> d;
     TRY(d.alloc(nt));
     TRY(k_tau_sum(c, c->tau_trace, c->n_trace, d));
@@ -1262,7 +1470,7 @@ extern "C" int dsm_ctx_get_tau_at(dsm_ctx *c, int it, int64_t *tau)
     TRY(need(c, true, true));
     if (!c->tau_trace || !tau || it < -1 || it >= c->n_trace) { dsm_set_error("get_tau_at: bad iteration"); return DSM_ERR_ARG; }
     BIND(c);
-    return fetch_tau(c, c->tau_trace + (size_t)(it + 1) * c->V, tau);
+    return fetch_tau(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it + 1) * c->V), tau);
 }
 
 // ---------------------------------------------------------------- NMFT

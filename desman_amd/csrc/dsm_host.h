@@ -159,6 +159,9 @@ struct dsm_ctx {
     double *star = nullptr;         // [2]
     double *gamma_star = nullptr;   // [S][G]
     double *eta_star = nullptr;     // [16]
+    // the fixed-tau chain (api.hip: dsm_ctx_gibbs_update_fixed_tau)
+    bool tau_fixed_trace = false;   // the last update call held tau: slot 0 of tau_trace is the tau of every iteration, no other slot is written
+    dsm_ctx *fixtau_child = nullptr;   // the scratch chain of the pooled form (one position per distinct tau word), made on first use
     // a chain sharded over GPUs by positions (dsm_ctx_gibbs_update_sharded): this context holds positions shard_voff .. + V of shard_vtot
     bool shard_on = false;
     int shard_voff = 0, shard_vtot = 0;
@@ -242,6 +245,11 @@ int k_shard_pack(dsm_ctx *c, int nblocks);
 int k_shard_unpack(dsm_ctx *c);
 int k_finalize(dsm_ctx *c, int nblocks, int it, int star_mode, const double *prior, const double *gamma_src,
                const double *eta_src, int slot = 0, int *rare_out = nullptr);
+
+// ---- launchers (kernels_fixtau.hip)
+int k_fixtau_pool(dsm_ctx *c, const int32_t *d_row, int32_t *d_pooled);           // pooled[row[v]][s][b] += counts[v][s][b]
+int k_fixtau_fill_eta(dsm_ctx *c, const double *eta, double *eta_trace, int n);   // n trace rows = one matrix
+int k_fixtau_add_const(dsm_ctx *c, int n, double K);                              // ll / lp of the traces, the MAP record and the last evaluation += K
 
 // ---- launchers (kernels_nmft.hip)
 int k_nmft_freq(dsm_ctx *c);

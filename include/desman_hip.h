@@ -172,6 +172,38 @@ int dsm_ctx_update_tau(dsm_ctx *ctx, int n_iter, const double *gamma_store,
 int dsm_batch_update_tau(dsm_ctx *const *ctxs, int n_ctx, int n_iter, const double *const *gamma_stores,
                          const double *const *eta_stores);
 
+/* HaploSNP_Sampler.update_fixed_tau (HaploSNP_Sampler.py:409-428): n_iter iterations of the chain with the haplotypes HELD -- per
+ * iteration the mu/E pass at (tau, gamma, eta) under the context's own specification (dsm_ctx_stats_spec, dsm_ctx_force_stats_spec), the
+ * gamma and eta draws, and ll / lp of the new state; the entry state is evaluated and recorded first, as by dsm_ctx_gibbs_update.
+ * Results as after dsm_ctx_gibbs_update: gamma / eta / ll / lp traces, the MAP record (dsm_ctx_get_star), the state; nchange is 0 in every
+ * iteration, dsm_ctx_get_tau_at gives the held tau for every iteration and dsm_ctx_get_tau_sum n_iter times it (one row is stored, not
+ * n_iter).  The MT19937 stream is not touched (dsm_ctx_get_mt_state is the same before and after), the stream key stays, the iteration
+ * counter advances by n_iter; a call of 2 n iterations is two calls of n, bit for bit.
+ *   fix_eta != 0: eta is held too.  The E sums and the eta draw are still made (so the gamma draws of iteration 0 are those of
+ *     fix_eta = 0), but the chain's eta, every row of the eta trace and the MAP record's eta are the entry matrix bit for bit, and ll / lp
+ *     are evaluated at it.
+ *   pool: 0 = the chain runs on the table as it is.  1 = on the POOLED table: positions whose packed tau words are equal have the same
+ *     cell probabilities, so their counts are added once per call (a sum of multinomials with one probability vector is the multinomial
+ *     of the summed count) and the chain runs on W <= min(V, 4^G) rows, one per distinct word in ascending order of the word
+ *     (bit 2g.. of the word = base of haplotype g).  Counter-based streams are keyed by the pooled cell indices: the pooled chain is NOT
+ *     the unpooled chain draw for draw; it is, bit for bit, the chain this call with pool = 0 runs on the pooled table with the same
+ *     gamma, eta, priors, stream key and counter -- the same law.  ll and lp (traces, MAP record) are reported for the CALLER's table: the
+ *     multinomial coefficients of the two tables differ by a constant, which is added (fp64; equal to pool = 0 to ~1e-12 relative to the
+ *     summed terms).  The caller's counts and tau are only read.  DSM_ERR_UNSUPPORTED, before anything is launched, if a pooled count --
+ *     a cell, or the four cells of one (word, sample) together, the depth dsm_ctx_set_counts bounds -- would pass 2^31-1.
+ *     -1 = auto: pooled iff W < V and nothing overflows (pooling costs one pass over the table, less than one iteration's mu/E pass;
+ *     where it stops paying has not been measured; at V = 10 000 and 200 iterations the pooled call was the slower one, DESIGN.md
+ *     sec. 8c -- its set-up is paid per call), else as pool = 0.
+ * Degenerate operands: V = 1 and G = 1 run like any other shape (W = 1 at V = 1); a sample without reads draws its gamma row from the
+ * prior Dir(alpha) every iteration and adds 0 to ll.  n_iter = 0 evaluates and records the entry state only.
+ * DSM_ERR_STATE without counts or state, DSM_ERR_ARG for n_iter < 0 or pool outside -1..1.  No batched or sharded form.              */
+int dsm_ctx_gibbs_update_fixed_tau(dsm_ctx *ctx, int n_iter, int fix_eta, int pool);
+/* test hooks of the pooled form, for the resident state (nothing of the context changes): the pooled table itself -- *W distinct words,
+ * pooled [W][S][4] int32 (give room for [V][S][4]), words [W] ascending (room for V), row [V] = the row of each position's word; any
+ * pointer may be NULL -- and one dsm_ctx_sample_stats draw made ON the pooled state.  DSM_ERR_UNSUPPORTED on overflow as above.        */
+int dsm_ctx_debug_fixtau_pool(dsm_ctx *ctx, int *W, int32_t *pooled, uint64_t *words, int32_t *row);
+int dsm_ctx_debug_fixtau_sample_stats(dsm_ctx *ctx, uint32_t iter, uint64_t *sum_mu, uint64_t *esum);
+
 /* results of the last update call.  Any pointer may be NULL.                 */
 int dsm_ctx_get_trace(dsm_ctx *ctx, double *ll, double *lp, int32_t *nchange,
                       double *gamma_store, double *eta_store);
