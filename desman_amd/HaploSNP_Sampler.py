@@ -17,6 +17,7 @@ import numpy as np
 
 from . import _lib
 from . import fixed_tau as _fixed_tau
+from . import relabel as _relabel
 from . import sampletau as _sampletau
 
 
@@ -54,6 +55,8 @@ class HaploSNP_Sampler:
         self._ctx.set_counts(self.variants)
         self._ctx.set_priors(alpha_constant, delta_constant, epsilon)
         self._tau_sum = None
+        self._relabel = None
+        self.relabel_ref = None         # the reference relabelling() matches the stored iterations to ([V,G] digits); None = tau_star
         self._have_trace = False
         self._keyed = False
         self.mt_state = None            # a GSL stream of the sampler's own (update_batch: several chains in one thread);
@@ -214,6 +217,7 @@ class HaploSNP_Sampler:
         for it in range(0, n, 10):
             logging.info('Gibbs Iter %d, no. changed = %d, %s = %f' % (it, tr["nchange"][it], prefix, tr["lp"][it]))
         self._tau_sum = None
+        self._relabel = None
         self._have_trace = True
         self.updateTauIndices()
 
@@ -352,6 +356,7 @@ class HaploSNP_Sampler:
         self.gamma_store = np.zeros((self.max_iter, self.S, self.G))
         self._have_trace = False
         self._tau_sum = None
+        self._relabel = None
         self.updateTauIndices()
 
     # ---- posterior summaries of the last update() (HaploSNP_Sampler.py:463-483,834-839)
@@ -376,6 +381,55 @@ class HaploSNP_Sampler:
 
     def probabilisticTau(self):
         return self._tausum() / float(self.max_iter)
+
+    # ---- the same summaries with every stored iteration's labels matched to a reference first (desman_amd/relabel.py, DESIGN.md sec. 8d)
+    def _trace_ctx(self):
+        if not self._have_trace:
+            raise _lib.DesmanHipError("no update() has run: tau_store is empty")
+        return self._ctx
+
+    def traceSND(self, ref=None, self_=False):
+        """[max_iter, G, Gr] distances of every stored iteration's haplotypes, from the trace on the device: to the haplotypes of
+        ``ref`` ([V,Gr] digits or [V,Gr,4] one-hot; default tau_star), or -- self_ -- to each other within the iteration
+        (calculateSND of every iteration)"""
+        ctx = self._trace_ctx()
+        if self_:
+            return ctx.trace_snd(_lib.SND_SELF)
+        return ctx.trace_snd(_lib.SND_STAR) if ref is None else ctx.trace_snd(_lib.SND_GIVEN, ref=ref)
+
+    def relabelling(self, ref=None):
+        """relabel.relabel_trace of the last update(): per stored iteration the permutation of its labels that brings it closest to
+        ``ref`` (default: ``relabel_ref`` if set, else tau_star), with the costs before and after; kept until the next update()"""
+        ref = self.relabel_ref if ref is None else ref
+        if self._relabel is None or self._relabel[0] is not ref:
+            self._relabel = (ref, _relabel.relabel_trace(self._trace_ctx(), ref))
+        return self._relabel[1]
+
+    def tauMeanRelabelled(self):
+        """tauMean() with iteration t's haplotype g counted as label relabelling()['perm'][t, g]"""
+        return self._ctx.get_tau_sum_perm(self.relabelling()["perm"]) / float(self.max_iter)
+
+    def gammaMeanRelabelled(self):
+        """gammaMean() with the columns of every iteration permuted likewise (eta has no haplotype index: etaMean() stands)"""
+        return _relabel.gamma_mean_relabelled(self.gamma_store[:self.max_iter], self.relabelling()["perm"])
+
+    def sndPosterior(self, level=0.95):
+        """per pair g < h the mean, sd, lo, med, hi of the relabelled within-iteration distance, and the distance in tau_star (map).
+        The pairs carry the labels of the relabelling: with ``relabel_ref`` set those are the reference's, and tau_star itself is
+        matched to the reference like any iteration, so that map speaks of the same pair of strains as the other columns."""
+        perm = self.relabelling()["perm"]
+        snd_map = self.calculateSND(self.tau_star)
+        if self.relabel_ref is not None:
+            ref = _relabel._reference(self, self.relabel_ref)[1]
+            own, _ = _relabel.min_cost_assignment(self.compSND(self.tau_star, self._onehot(ref)))   # tau_star's haplotype g is label own[g]
+            inv = np.argsort(own)
+            snd_map = snd_map[np.ix_(inv, inv)]
+        return _relabel.snd_posterior(self._trace_ctx(), perm, level=level, snd_map=snd_map)
+
+    def haplotypeStability(self):
+        """per haplotype the mean and max over iterations of the fraction of positions that differ from the reference haplotype after
+        relabelling, and the number of iterations in which its label was moved (relabel.haplotype_stability)"""
+        return _relabel.haplotype_stability(self._trace_ctx(), self.relabelling())
 
     @property
     def tau_store(self):

@@ -173,6 +173,42 @@ class Output_Results:
         pd.DataFrame(eta).to_csv(self._path("Eta_mean.csv"))
         logging.info("Eta_mean.csv written")
 
+    # ---- `desman --relabel`: the summaries with every stored iteration's labels matched to a reference (desman_amd/relabel.py)
+    def output_Relabel(self, rel):
+        """Relabel.csv: one row per stored iteration -- the summed distance to the reference under the iteration's own labels and under
+        the best relabelling, whether the two differ in labels, and the relabelling itself (haplotype g -> label, space separated)"""
+        perm = np.asarray(rel["perm"], dtype=np.int64)
+        switched = (perm != np.arange(perm.shape[1])[None, :]).any(axis=1).astype(np.int64)
+        frame = pd.DataFrame({"iter": np.arange(perm.shape[0]), "cost_identity": rel["cost_identity"], "cost_best": rel["cost_best"],
+                              "switched": switched, "perm": [" ".join(str(x) for x in row) for row in perm]})
+        frame.to_csv(self._path("Relabel.csv"), index=False)
+        logging.info("Relabel.csv written: %d of %d stored iterations had switched labels" % (int(switched.sum()), perm.shape[0]))
+
+    def output_Tau_Mean_relabelled(self, tauProb):
+        self._haplotype_table("Tau_Mean_relabelled.csv", np.reshape(tauProb, (self.haplo_SNP.V, self.haplo_SNP.G, 4)),
+                              self.filtered_contig_names, self.filtered_position)
+        logging.info("Tau_Mean_relabelled.csv written")
+
+    def output_Gamma_Mean_relabelled(self, gamma):
+        self._abundance_table("Gamma_Mean_relabelled.csv", gamma)
+
+    def output_SND_posterior(self, post):
+        """SND_posterior.csv: per pair of haplotypes the posterior of their distance (positions that differ) and the MAP state's"""
+        cols = [k for k in ("mean", "sd", "lo", "med", "hi", "map") if k in post]
+        frame = pd.DataFrame({k: post[k] for k in cols})
+        frame.insert(0, "h", post["pairs"][:, 1])
+        frame.insert(0, "g", post["pairs"][:, 0])
+        frame.to_csv(self._path("SND_posterior.csv"), index=False)
+        logging.info("SND_posterior.csv written")
+
+    def output_Haplotype_stability(self, stab):
+        """Haplotype_stability.csv: per haplotype the mean and maximum fraction of positions that differ from the reference haplotype
+        over the relabelled iterations, and in how many iterations its label had moved"""
+        frame = pd.DataFrame({"haplotype": np.arange(len(stab["mean"])), "mean_diff": stab["mean"], "max_diff": stab["max"],
+                              "moved": stab["moved"]})
+        frame.to_csv(self._path("Haplotype_stability.csv"), index=False)
+        logging.info("Haplotype_stability.csv written")
+
     def output_Selected_Variants(self):
         """the selected rows of the input table.  Every chain of a G-sweep writes the same file (the -r selection is drawn from
         a fixed seed, bin/desman:85-86): serialising 50 000 x 385 integers takes longer than the chain's GPU work, so within one

@@ -17,6 +17,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "desman_hip.h")
 
 DSM_OK = 0
 RNG_MT19937, RNG_PHILOX = 0, 1
+SND_STAR, SND_SELF, SND_GIVEN = 0, 1, 2     # DSM_SND_*: the reference of Context.trace_snd
 STATS_AGG = 2        # version of the aggregated mu/E specification that runs by default (oracle/stats_agg.c); 3 = the table exp / log variant
 K_NAMES = ("stats", "dirichlet", "tau", "finalize", "mt", "nmft_a", "nmft_gamma", "nmft_b", "stats2", "stats_big", "stats_pat")
 
@@ -106,6 +107,9 @@ SIGNATURES = {
     "dsm_ctx_get_star": (_i, [_vp, _vp, _vp, _vp, C.POINTER(_d), C.POINTER(_i)]),
     "dsm_ctx_get_tau_sum": (_i, [_vp, _i64p]),
     "dsm_ctx_get_tau_at": (_i, [_vp, _i, _i64p]),
+    "dsm_ctx_trace_snd": (_i, [_vp, _i, _vp, _i, _i, _i, _vp]),
+    "dsm_ctx_get_tau_sum_perm": (_i, [_vp, _vp, _i, _i, _vp]),
+    "dsm_ctx_debug_set_trace": (_i, [_vp, _vp, _i]),
     "dsm_nmft_set": (_i, [_vp, _f64p, _f64p, _i]),
     "dsm_nmft_get": (_i, [_vp, _vp, _vp]),
     "dsm_nmft_factorize": (_i, [_vp, _i, _d, _i, C.POINTER(_i), _vp]),
@@ -743,6 +747,36 @@ class Context:
         out = np.empty((self.V, self.G, 4), dtype=np.int64)
         check(self.lib.dsm_ctx_get_tau_at(self._h, int(it), out))
         return out
+
+    # ---- reductions of the resident tau trace (include/desman_hip.h: dsm_ctx_trace_snd; desman_amd/relabel.py)
+    def trace_snd(self, mode=SND_STAR, ref=None, it0=0, n_it=None):
+        """snd [n_it, G, Gr] int32: in how many positions haplotype g of stored iteration t differs from haplotype h of the reference --
+        SND_STAR: the MAP record's tau; SND_SELF: the iteration itself; SND_GIVEN: ``ref`` ([V,Gr] digits or [V,Gr,4] one-hot)"""
+        n_it = self.n_trace - int(it0) if n_it is None else int(n_it)
+        r, Gr = None, self.G
+        if mode == SND_GIVEN:
+            r = _fit_tau(ref, self.V)
+            Gr = r.shape[1]
+        out = np.zeros((max(n_it, 0), self.G, Gr), dtype=np.int32)
+        check(self.lib.dsm_ctx_trace_snd(self._h, int(mode), _ptr(r), Gr if mode == SND_GIVEN else 0, int(it0), n_it, _ptr(out)))
+        return out
+
+    def get_tau_sum_perm(self, perm, it0=0):
+        """get_tau_sum() over the iterations it0 .. it0 + len(perm) - 1 with iteration t's haplotype g counted as label perm[t, g]"""
+        p = np.ascontiguousarray(perm, dtype=np.uint8)
+        if p.ndim != 2 or p.shape[1] != self.G or not np.array_equal(p, np.asarray(perm)):
+            raise ValueError("get_tau_sum_perm: perm must be [n_it, G=%d] labels 0..G-1" % self.G)
+        out = np.zeros((self.V, self.G, 4), dtype=np.int64)
+        check(self.lib.dsm_ctx_get_tau_sum_perm(self._h, _ptr(p), int(it0), p.shape[0], _ptr(out)))
+        return out
+
+    def debug_set_trace(self, tau_digits):
+        """test hook: installs tau_digits [n, V, G] (digits 0..3) as the tau trace of n iterations; slot 0 = the resident state"""
+        t = np.ascontiguousarray(tau_digits, dtype=np.int64)
+        if t.ndim != 3 or t.shape[1:] != (self.V, self.G):
+            raise ValueError("debug_set_trace: tau_digits must be [n, V=%d, G=%d]" % (self.V, self.G))
+        check(self.lib.dsm_ctx_debug_set_trace(self._h, _ptr(t), t.shape[0]))
+        self.n_trace = t.shape[0]
 
     # ---- NMFT
     def nmft_set(self, tau, gamma):

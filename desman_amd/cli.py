@@ -47,6 +47,16 @@ def build_parser():
     for short, long_, kw in _FLAGS:
         ap.add_argument(short, long_, **kw)
     ap.add_argument('--device', type=int, default=0, help="GPU ordinal (extension)")
+    ap.add_argument('--relabel', action='store_true',
+                    help="also write the posterior summaries with every stored iteration's haplotype labels matched to the MAP "
+                         "haplotypes first (Relabel.csv, Tau_Mean_relabelled.csv, Gamma_Mean_relabelled.csv, SND_posterior.csv, "
+                         "Haplotype_stability.csv) (extension)")
+    ap.add_argument('--relabel-ref', dest='relabel_ref', type=str, metavar='TAU_CSV',
+                    help="with --relabel (implied): match the labels to the haplotypes of this Filtered_Tau_star.csv -- another run on "
+                         "the same positions with the same -g -- instead of this run's own MAP haplotypes; a file that does not fit is refused "
+                         "before the chain starts, but a chain that merges identical haplotypes after burn-in ends up with fewer than "
+                         "-g, can no longer follow the file and stops with that message after the run: give the -g the other run kept "
+                         "(extension)")
     return ap
 
 
@@ -138,6 +148,36 @@ def _report(report, table, flt, chain, requested):
     report.output_Selected_Variants()
 
 
+def _relabel_reference(opts, table, flt):
+    """--relabel-ref: the other run's haplotypes as [V, G] digits, checked against the positions this run is about to fit and against
+    -g; the run stops here, before any chain, if the file does not fit.  None without the option."""
+    if opts.relabel_ref is None:
+        return None
+    from . import relabel
+    if not os.path.isfile(opts.relabel_ref):
+        sys.exit("desman: can't open --relabel-ref file '%s'" % opts.relabel_ref)
+    rows = np.asarray(flt.selected_indices, dtype=np.int64)
+    names = table.index.to_numpy()[rows]
+    positions = table['Position'].to_numpy()[rows]
+    try:
+        return relabel.read_reference(opts.relabel_ref, positions, names, opts.genomes)
+    except ValueError as e:
+        sys.exit("desman: --relabel-ref: %s" % e)
+
+
+def _report_relabel(report, chain, ref):
+    """--relabel: the relabelled summaries of the fitted chain, next to the usual files (which do not change)"""
+    if ref is not None and ref.shape[1] != chain.G:
+        sys.exit("desman: --relabel-ref: the chain kept %d of the %d haplotypes after merging identical ones; the reference has %d"
+                 % (chain.G, ref.shape[1], ref.shape[1]))
+    chain.relabel_ref = ref
+    report.output_Relabel(chain.relabelling())
+    report.output_Tau_Mean_relabelled(chain.tauMeanRelabelled())
+    report.output_Gamma_Mean_relabelled(chain.gammaMeanRelabelled())
+    report.output_SND_posterior(chain.sndPosterior())
+    report.output_Haplotype_stability(chain.haplotypeStability())
+
+
 def _assign_rest(opts, report, table, flt, chain):
     """-r: haplotypes of the positions left out of the fit, with tau-only sweeps driven by the fitted
     chain's gamma / eta traces (bin/desman:181-206)."""
@@ -211,8 +251,11 @@ def main(argv=None):
         sys.exit(-1)
     report = Output_Results(opts.output_dir)
     table, flt, subsample = _load(opts, report)
+    ref = _relabel_reference(opts, table, flt)
     chain = _fit(opts, flt)
     _report(report, table, flt, chain, opts.genomes)
+    if opts.relabel or ref is not None:
+        _report_relabel(report, chain, ref)
     if subsample is not None:
         _assign_rest(opts, report, table, flt, chain)
     sampletau.freeRNG()
@@ -238,7 +281,8 @@ def main_replicates(argv_list, on_chain=None):
         logging.info('sampler seed %d', opts.random_seed)
         rng = RandomState(opts.random_seed)
         nmft = Init_NMFT(flt.snps_filter, opts.genomes, rng, device=opts.device)
-        runs.append(dict(opts=opts, report=report, table=table, flt=flt, subsample=subsample, rng=rng, nmft=nmft))
+        runs.append(dict(opts=opts, report=report, table=table, flt=flt, subsample=subsample, rng=rng, nmft=nmft,
+                         ref=_relabel_reference(opts, table, flt)))
     # the NMF starts: together where the batched kernels apply (one shape, S <= 128, G <= 16), else one by one
     nm = [r["nmft"] for r in runs]
     done = False
@@ -292,6 +336,8 @@ def main_replicates(argv_list, on_chain=None):
     for k, r in enumerate(runs):
         tell(k)
         _report(r["report"], r["table"], r["flt"], r["chain"], r["opts"].genomes)
+        if r["opts"].relabel or r["ref"] is not None:
+            _report_relabel(r["report"], r["chain"], r["ref"])
     # -r: the positions left out of the fit -- batched where the replicates still agree in shape
     rest_runs = [r for r in runs if r["subsample"] is not None]
     idx = {id(r): k for k, r in enumerate(runs)}

@@ -1473,6 +1473,137 @@ extern "C" int dsm_ctx_get_tau_at(dsm_ctx *c, int it, int64_t *tau)
     return fetch_tau(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it + 1) * c->V), tau);
 }
 
+// ---------------------------------------------------------------- reductions of the tau trace (kernels_relabel.hip)
+// digits [rows][G] -> packed words; DSM_ERR_ARG on a digit outside 0..3
+static int pack_digits(const char *who, const int64_t *digits, size_t rows, int G, std::vector<uint64_t> &out)
+{
+    out.assign(rows, 0ull);
+    for (size_t r = 0; r < rows; ++r) {
+        uint64_t t = 0;
+        for (int g = 0; g < G; ++g) {
+            const int64_t d = digits[r * G + g];
+            if (d < 0 || d > 3) { dsm_set_error("%s: digit %lld at row %zu, haplotype %d is not a base 0..3", who, (long long)d, r, g); return DSM_ERR_ARG; }
+            t |= (uint64_t)d << (2 * g);
+        }
+        out[r] = t;
+    }
+    return DSM_OK;
+}
+
+// the checks the two trace reductions share: a trace, and a range inside it
+static int trace_range(dsm_ctx *c, const char *who, int it0, int n_it)
+{
+    TRY(need(c, true, true));
+    if (!c->tau_trace) { dsm_set_error("%s: no update has run", who); return DSM_ERR_STATE; }
+    if (it0 < 0 || n_it < 0 || it0 > c->n_trace || n_it > c->n_trace - it0) {
+        dsm_set_error("%s: iterations %d .. %d + %d outside the trace of %d", who, it0, it0, n_it, c->n_trace);
+        return DSM_ERR_ARG;
+    }
+    return DSM_OK;
+}
+
+extern "C" int dsm_ctx_trace_snd(dsm_ctx *c, int mode, const int64_t *ref_tau, int Gr, int it0, int n_it, int32_t *snd)
+{
+    TRY(trace_range(c, "trace_snd", it0, n_it));
+    if (mode != DSM_SND_STAR && mode != DSM_SND_SELF && mode != DSM_SND_GIVEN) { dsm_set_error("trace_snd: mode %d is none of DSM_SND_STAR / SELF / GIVEN", mode); return DSM_ERR_ARG; }
+    if (mode == DSM_SND_GIVEN) {
+        if (Gr < 1 || Gr > DSM_MAX_G) { dsm_set_error("trace_snd: Gr=%d outside 1..%d", Gr, DSM_MAX_G); return DSM_ERR_ARG; }
+        if (!ref_tau) { dsm_set_error("trace_snd: DSM_SND_GIVEN without a reference"); return DSM_ERR_ARG; }
+    } else {
+        if (Gr != 0 && Gr != c->G) { dsm_set_error("trace_snd: Gr=%d, but this mode's reference has the chain's %d haplotypes (pass 0 or G)", Gr, c->G); return DSM_ERR_ARG; }
+        Gr = c->G;
+    }
+    if (n_it > 0 && !snd) { dsm_set_error("trace_snd: no output buffer"); return DSM_ERR_ARG; }
+    std::vector<uint64_t> packed;
+    if (mode == DSM_SND_GIVEN) TRY(pack_digits("trace_snd", ref_tau, (size_t)c->V, Gr, packed));
+    if (n_it == 0) return DSM_OK;
+    BIND(c);
+    const size_t V = (size_t)c->V, stride = c->tau_fixed_trace ? 0 : V;
+    const uint64_t *trace = c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it0 + 1) * V);
+    const uint64_t *ref = nullptr;
+    Scratch<uint64_t> d_ref;
+    if (mode == DSM_SND_STAR) {
+        double st[2];
+        HIP_TRY(hipMemcpyAsync(st, c->star, sizeof st, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (!(st[1] >= 0.0 && st[1] <= (double)c->n_trace)) { dsm_set_error("trace_snd: the MAP record's slot lies outside the trace of %d", c->n_trace); return DSM_ERR_STATE; }
+        ref = c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(int)st[1] * V);
+    } else if (mode == DSM_SND_GIVEN) {
+        TRY(d_ref.alloc(V));
+        HIP_TRY(hipMemcpyAsync(d_ref, packed.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        ref = d_ref;
+    }
+    const size_t nout = (size_t)n_it * c->G * Gr;
+    Scratch<int> d_out;
+    TRY(d_out.alloc(nout));
+    TRY(k_trace_snd(c, trace, stride, ref, Gr, n_it, d_out));
+    HIP_TRY(hipMemcpyAsync(snd, d_out, nout * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DSM_OK;
+}
+
+extern "C" int dsm_ctx_get_tau_sum_perm(dsm_ctx *c, const uint8_t *perm, int it0, int n_it, int64_t *tau_sum)
+{
+    TRY(trace_range(c, "get_tau_sum_perm", it0, n_it));
+    if (!tau_sum || (n_it > 0 && !perm)) { dsm_set_error("get_tau_sum_perm: null pointer"); return DSM_ERR_ARG; }
+    const int G = c->G;
+    std::vector<uint8_t> inv((size_t)n_it * G);
+    for (int t = 0; t < n_it; ++t) {
+        uint32_t seen = 0;
+        for (int g = 0; g < G; ++g) {
+            const int p = perm[(size_t)t * G + g];
+            if (p >= G || (seen >> p & 1u)) { dsm_set_error("get_tau_sum_perm: row %d of perm is not a permutation of 0..%d", t, G - 1); return DSM_ERR_ARG; }
+            seen |= 1u << p;
+            inv[(size_t)t * G + p] = (uint8_t)g;
+        }
+    }
+    BIND(c);
+    const size_t V = (size_t)c->V, nt = V * G * 4;
+    Scratch<int64_t> d_out;
+    Scratch<uint8_t> d_inv;
+    TRY(d_out.alloc(nt));
+    TRY(d_inv.alloc(inv.size()));
+    if (n_it > 0) HIP_TRY(hipMemcpyAsync(d_inv, inv.data(), inv.size(), hipMemcpyHostToDevice, c->stream));
+    TRY(k_tau_sum_perm(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it0 + 1) * V), c->tau_fixed_trace ? 0 : V, d_inv, n_it, d_out));
+    HIP_TRY(hipMemcpyAsync(tau_sum, d_out, nt * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DSM_OK;
+}
+
+// test hook: a synthetic trace.  Slot 0 = the resident state, slots 1 .. n = the given digits.  A context on which no update has run has
+// no MAP record yet: it gets the resident state as one (slot 0, lp = -inf), so that DSM_SND_STAR has a reference; an existing record stays.
+extern "C" int dsm_ctx_debug_set_trace(dsm_ctx *c, const int64_t *tau_digits, int n)
+{
+    TRY(need(c, true, true));
+    if (n < 0 || (n > 0 && !tau_digits)) { dsm_set_error("debug_set_trace: bad arguments"); return DSM_ERR_ARG; }
+    std::vector<uint64_t> packed;
+    TRY(pack_digits("debug_set_trace", tau_digits, (size_t)n * c->V, c->G, packed));
+    BIND(c);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const bool fresh = !c->tau_trace || n > c->trace_cap;
+    const bool no_star = !c->tau_trace;
+    TRY(alloc_traces(c, n));
+    const size_t V = (size_t)c->V, sg = (size_t)c->S * c->G;
+    if (fresh) {                                      // the other traces of a new allocation read as zero
+        const size_t cap = (size_t)c->trace_cap;
+        HIP_TRY(hipMemsetAsync(c->ll_trace, 0, cap * sizeof(double), c->stream));
+        HIP_TRY(hipMemsetAsync(c->lp_trace, 0, cap * sizeof(double), c->stream));
+        HIP_TRY(hipMemsetAsync(c->nchange_trace, 0, cap * sizeof(int), c->stream));
+        HIP_TRY(hipMemsetAsync(c->gamma_trace, 0, cap * sg * sizeof(double), c->stream));
+        HIP_TRY(hipMemsetAsync(c->eta_trace, 0, cap * 16 * sizeof(double), c->stream));
+    }
+    if (no_star) {
+        const double st[2] = {-INFINITY, 0.0};
+        HIP_TRY(hipMemcpyAsync(c->star, st, sizeof st, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->gamma_star, c->gamma, sg * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->eta_star, c->eta, 16 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(c->tau_trace, c->tau, V * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
+    if (n > 0) HIP_TRY(hipMemcpyAsync(c->tau_trace + V, packed.data(), (size_t)n * V * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DSM_OK;
+}
+
 // ---------------------------------------------------------------- NMFT
 extern "C" int dsm_nmft_set(dsm_ctx *c, const double *tau, const double *gamma, int G)
 {

@@ -251,6 +251,10 @@ int k_fixtau_pool(dsm_ctx *c, const int32_t *d_row, int32_t *d_pooled);         
 int k_fixtau_fill_eta(dsm_ctx *c, const double *eta, double *eta_trace, int n);   // n trace rows = one matrix
 int k_fixtau_add_const(dsm_ctx *c, int n, double K);                              // ll / lp of the traces, the MAP record and the last evaluation += K
 
+// ---- launchers (kernels_relabel.hip): reductions of the tau trace; trace_stride = words between two iterations' rows (0: one row for all)
+int k_trace_snd(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const uint64_t *ref, int Gr, int n_it, int *d_out);   // ref null: each iteration against itself
+int k_tau_sum_perm(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const uint8_t *d_inv, int n, int64_t *d_out);      // inv[t][perm[t][g]] = g
+
 // ---- launchers (kernels_nmft.hip)
 int k_nmft_freq(dsm_ctx *c);
 int k_nmft_clamp(dsm_ctx *c);

@@ -215,6 +215,37 @@ int dsm_ctx_get_tau_sum(dsm_ctx *ctx, int64_t *tau_sum);
 /* tau as stored after iteration `it` of the last update ([V][G][4] int64).   */
 int dsm_ctx_get_tau_at(dsm_ctx *ctx, int it, int64_t *tau);
 
+/* Reductions of the resident tau trace of the last update call, for posterior summaries that survive label switching (DESIGN.md
+ * sec. 8d; desman_amd/relabel.py).  The trace stays on the device: one pass over its packed words (8 B per position and iteration),
+ * integer results, the same bits from run to run.  Iteration `it` is what dsm_ctx_get_tau_at(it) returns; after
+ * dsm_ctx_gibbs_update_fixed_tau every iteration is the held tau.
+ *   dsm_ctx_trace_snd: for the stored iterations it0 .. it0 + n_it - 1 and a reference of Gr haplotypes
+ *       snd[t][g][h] = #{ v : tau_t[v][g] != ref_t[v][h] }                              int32 [n_it][G][Gr]
+ *     mode DSM_SND_STAR   ref = the tau of the MAP record (what dsm_ctx_get_star returns); Gr = G (pass 0 or G), ref_tau ignored
+ *          DSM_SND_SELF   ref_t = tau_t: the pairwise distances within each iteration (calculateSND, HaploSNP_Sampler.py:712-730:
+ *                         symmetric, zero diagonal); Gr = G (pass 0 or G), ref_tau ignored
+ *          DSM_SND_GIVEN  ref = ref_tau [V][Gr] DIGITS 0..3 (the format dsm_fit_gamma takes), 1 <= Gr <= DSM_MAX_G
+ *   dsm_ctx_get_tau_sum_perm: dsm_ctx_get_tau_sum over the same kind of range with the labels of iteration t renamed by row t of perm
+ *     (uint8 [n_it][G], each row a permutation of 0..G-1):  tau_sum[v][perm[t][g]][a] += [tau_t[v][g] = a],  int64 [V][G][4].  With
+ *     identity rows over the whole trace it is dsm_ctx_get_tau_sum.
+ * DSM_ERR_STATE when no update has run (or, DSM_SND_STAR, the MAP record names a slot outside the trace: only after
+ * dsm_ctx_debug_set_trace); DSM_ERR_ARG for a range outside 0 .. the trace's length, a bad mode, Gr outside its range, a digit outside
+ * 0..3, a perm row that is no permutation.  n_it = 0 succeeds and writes nothing to snd (tau_sum: zeros).  The chain state, both RNG
+ * streams, the traces and the MAP record are only read: a chain continues bit for bit after these calls.                          */
+#define DSM_SND_STAR  0
+#define DSM_SND_SELF  1
+#define DSM_SND_GIVEN 2
+int dsm_ctx_trace_snd(dsm_ctx *ctx, int mode, const int64_t *ref_tau /*[V][Gr] digits or NULL*/, int Gr, int it0, int n_it,
+                      int32_t *snd /*[n_it][G][Gr]*/);
+int dsm_ctx_get_tau_sum_perm(dsm_ctx *ctx, const uint8_t *perm /*[n_it][G]*/, int it0, int n_it, int64_t *tau_sum /*[V][G][4]*/);
+/* test hook: installs a synthetic tau trace of n iterations, tau_digits [n][V][G] DIGITS 0..3 (DSM_ERR_ARG otherwise): slot 0 (the
+ * entry state, dsm_ctx_get_tau_at(-1)) = the resident tau, iteration k = tau_digits[k], the trace's length = n, as after
+ * dsm_ctx_gibbs_update (not a fixed-tau trace).  Needs counts and a state (DSM_ERR_STATE).  The state, both RNG streams and the
+ * counters are not touched, nor is the MAP record: DSM_SND_STAR then compares against the slot that record names in the PLANTED
+ * trace.  A context on which no update has run has no record; it is given the resident state as one (slot 0, lp = -inf).  The
+ * ll / lp / nchange / gamma / eta traces keep what they held (zeros where the call had to allocate them).                       */
+int dsm_ctx_debug_set_trace(dsm_ctx *ctx, const int64_t *tau_digits /*[n][V][G]*/, int n);
+
 /* A8-A12: Init_NMFT (desman/Init_NMFT.py).  F is derived from the resident
  * counts (:49-60).  tau [4V][G] row v + a*V, gamma [G][S] as in the reference.
  * Every shape up to S = DSM_MAX_S, G = DSM_MAX_G has a kernel (tests/test_gpu_nmft_forms.py
