@@ -195,6 +195,17 @@ class HaploSNP_Sampler:
         self._release_rng()
         self._collect(prefix='nlp')
 
+    def update_held(self, n_held, fix_eta=False):
+        """max_iter Gibbs iterations with the LAST n_held haplotypes held and the others sampled, on the device
+        (dsm_ctx_gibbs_update_held_tau; the reference has no counterpart).  Fills the stores, the star state and lp as update() does;
+        the GSL stream advances by V (G - n_held) words per iteration.  fix_eta: eta is held as well.  n_held = 0 is update(),
+        n_held = G is update_fixed_tau(pool=0)."""
+        self._push_state()
+        self._bind_rng()
+        self._ctx.gibbs_update_held_tau(self.max_iter, n_held, fix_eta=fix_eta)
+        self._release_rng()
+        self._collect(prefix='nlp')
+
     def _collect(self, prefix, keep_gamma_eta=False):
         tr = self._ctx.get_trace()
         n = self.max_iter

@@ -81,6 +81,8 @@ SIGNATURES = {
     "dsm_ctx_loglik": (_i, [_vp, C.POINTER(_d), C.POINTER(_d)]),
     "dsm_ctx_gibbs_update": (_i, [_vp, _i]),
     "dsm_ctx_gibbs_update_fixed_tau": (_i, [_vp, _i, _i, _i]),
+    "dsm_ctx_sample_tau_held": (_i, [_vp, _i, C.POINTER(_i)]),
+    "dsm_ctx_gibbs_update_held_tau": (_i, [_vp, _i, _i, _i]),
     "dsm_ctx_debug_fixtau_pool": (_i, [_vp, C.POINTER(_i), _vp, _vp, _vp]),
     "dsm_ctx_debug_fixtau_sample_stats": (_i, [_vp, C.c_uint32, _u64p, _u64p]),
     "dsm_ctx_get_counters": (_i, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
@@ -663,6 +665,19 @@ class Context:
         gibbs_update.  fix_eta: eta is held too.  pool: 0 = on the table as it is, 1 = on the counts pooled per distinct tau word,
         -1 = pooled where that makes the table smaller."""
         check(self.lib.dsm_ctx_gibbs_update_fixed_tau(self._h, int(n_iter), 1 if fix_eta else 0, int(pool)))
+        self.n_trace = int(n_iter)
+
+    def sample_tau_held(self, n_held):
+        """one tau sweep over haplotypes 0 .. G - n_held - 1 of the resident state, the last n_held held (include/desman_hip.h:
+        dsm_ctx_sample_tau_held); returns the number of changed (position, haplotype) pairs"""
+        n = _i(0)
+        check(self.lib.dsm_ctx_sample_tau_held(self._h, int(n_held), C.byref(n)))
+        return n.value
+
+    def gibbs_update_held_tau(self, n_iter, n_held, fix_eta=False):
+        """n_iter Gibbs iterations with the last n_held haplotypes held (include/desman_hip.h: dsm_ctx_gibbs_update_held_tau): results
+        as after gibbs_update.  fix_eta: eta is held too.  n_held = 0 is gibbs_update, n_held = G is gibbs_update_fixed_tau(pool=0)."""
+        check(self.lib.dsm_ctx_gibbs_update_held_tau(self._h, int(n_iter), int(n_held), 1 if fix_eta else 0))
         self.n_trace = int(n_iter)
 
     def debug_fixtau_pool(self):

@@ -1,7 +1,7 @@
 """`desman-abund`: abundances of a finished run's haplotypes in samples that were not in the fit.
 
     python -m desman_amd.abund <run_dir> <table.freq> [-o DIR] [--tau FILE] [--only-new] [--presence] [--interval [LEVEL]] [--ctol X]
-                                                      [--fit-eta] [--posterior [N]] [--burn B] [--posterior-seed X]
+                                                      [--fit-eta] [--posterior [N]] [--burn B] [--posterior-seed X] [--novel K]
                                                       [--max-iter N] [--tol X] [--device N]
 
 `desman` drops every sample whose mean depth is not above -m, and a sample sequenced after the fit has no row in ``Gamma_star.csv``
@@ -38,6 +38,24 @@ fitted matrix, and two more files are written:
                              converged, dead_rows (bit a: no haplotype with abundance carries base a, row a is the run's)
     Projected_Eta_posterior.csv   with --posterior: the chain samples the error matrix too, from the fitted one as its start; per
                              true base (row) <b>_mean and <b>_sd of the posterior of eta[row, b]
+
+With --novel K the new samples may also contain strains the run did not find: the run's G haplotypes are held, K free haplotypes are
+placed in front of them and sampled together with the abundances by the partly held chain (dsm_ctx_gibbs_update_held_tau; DESIGN.md
+sec. 8e) -- --posterior N iterations, the first --burn dropped (that option's defaults when it is not given), streams keyed by
+--posterior-seed, eta = the run's (held) or, with --fit-eta, the fitted one as the start (sampled).  The start is not tuned: uniform
+abundance rows over the G + K haplotypes, every free digit drawn uniformly from the bases with a non-zero pooled count at its position
+by numpy's RandomState(--posterior-seed mod 2^32).  The K = 0 chain of --posterior is run on the same table as the baseline.  Written
+next to the usual files, which do not change (--interval and --presence speak of the held-only model):
+
+    Novel_Tau_star.csv         all K + G haplotypes of the MAP state in the format of Filtered_Tau_star.csv, the K free ones first; the
+                               held ones are the input
+    Novel_Gamma_star.csv       the MAP state's abundances; columns novel0 .. novel<K-1>, then the run's haplotypes under their numbers
+    Novel_Gamma_posterior.csv  <label>_mean, _sd, _lo, _med, _hi per sample and haplotype after burn-in (lo / hi as --posterior)
+    Novel_fit.csv              one row for K = 0 and one for K: deviance = -2 mean(ll) after burn-in, lp_star = lp of the MAP record,
+                               iters = iterations kept
+    Novel_haplotypes.csv       per free haplotype: distance = positions in which it differs from the nearest held haplotype, nearest =
+                               that haplotype, mean_abundance / max_abundance over the samples (posterior means).  A free haplotype at
+                               distance 0 from a held one is an over-fit; the file shows that, it does not decide it.
 """
 import argparse
 import os
@@ -50,6 +68,7 @@ from .Output_Results import rchop
 
 POSTERIOR_N, POSTERIOR_BURN, POSTERIOR_SEED = 1000, 200, 0x8C1F3A5D7E9B2468      # fixed_tau.POSTERIOR_SEED
 MAX_ITER, TOL, CTOL = 20000, 1.0e-9, 1.0e-6          # _lib.FIT_MAX_ITER / FIT_TOL / FIT_CTOL (the parser must not need the library)
+NOVEL_MAX_G = 32                                     # held_tau.MAX_G = DSM_MAX_G
 TAU_FILES = ("Collated_Tau_star.csv", "Filtered_Tau_star.csv")
 
 
@@ -73,6 +92,9 @@ def build_parser():
                     help="iterations of --posterior dropped at the start (default %d)" % POSTERIOR_BURN)
     ap.add_argument("--posterior-seed", type=lambda v: int(v, 0), default=POSTERIOR_SEED, metavar="X",
                     help="stream key of the --posterior chain (default 0x%X)" % POSTERIOR_SEED)
+    ap.add_argument("--novel", type=int, default=None, metavar="K",
+                    help="also fit K further haplotypes to the samples with the run's haplotypes held (the partly held chain; length, "
+                         "burn-in and key as --posterior) and write the Novel_* files")
     ap.add_argument("--ctol", type=float, default=CTOL, help="width to which an interval end is found (default %g)" % CTOL)
     ap.add_argument("--max-iter", type=int, default=MAX_ITER, help="EM steps at most (default %d)" % MAX_ITER)
     ap.add_argument("--tol", type=float, default=TOL, help="stop when no abundance moves by this much in a step (default %g)" % TOL)
@@ -219,7 +241,14 @@ def main(argv=None):
         sys.exit("desman-abund: --interval needs a level between 0 and 1")
     if opts.posterior is not None and not (opts.posterior >= 1 and 0 <= opts.burn < opts.posterior):
         sys.exit("desman-abund: --posterior needs N >= 1 iterations and 0 <= --burn < N")
+    n_chain = POSTERIOR_N if opts.posterior is None else opts.posterior
+    if opts.novel is not None and opts.novel < 1:
+        sys.exit("desman-abund: --novel needs K >= 1 free haplotypes")
+    if opts.novel is not None and not 0 <= opts.burn < n_chain:
+        sys.exit("desman-abund: --novel runs %d iterations (--posterior N), --burn must lie in 0 .. N - 1" % n_chain)
     contigs, positions, digits, eta = load_model(opts.run_dir, opts.tau)
+    if opts.novel is not None and digits.shape[1] + opts.novel > NOVEL_MAX_G:
+        sys.exit("desman-abund: --novel %d with the run's %d haplotypes makes more than %d" % (opts.novel, digits.shape[1], NOVEL_MAX_G))
     if not os.path.isfile(opts.freq_file):
         sys.exit("desman-abund: can't open '%s'" % opts.freq_file)
     table = pd.read_csv(opts.freq_file, header=0, index_col=0)
@@ -278,6 +307,14 @@ def main(argv=None):
         if opts.fit_eta:
             write_eta_posterior(opts.output_dir or opts.run_dir, post)
         res["posterior"] = post
+    if opts.novel is not None:
+        from . import fixed_tau, held_tau
+        chain = dict(n_iter=n_chain, burn=opts.burn, fix_eta=not opts.fit_eta, level=0.95 if opts.interval is None else opts.interval,
+                     seed=opts.posterior_seed, device=opts.device)
+        base = res["posterior"] if "posterior" in res else fixed_tau.posterior_gamma(counts, digits, eta, **chain)     # K = 0
+        novel = held_tau.novel_chain(counts, digits, eta, opts.novel, **chain)
+        held_tau.write_novel(opts.output_dir or opts.run_dir, [names[k] for k in keep], contigs, positions, base, novel, opts.novel)
+        res["novel"], res["novel_base"] = novel, base
     return res
 
 

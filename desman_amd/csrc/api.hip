@@ -1298,6 +1298,102 @@ extern "C" int dsm_ctx_gibbs_update_fixed_tau(dsm_ctx *c, int n_iter, int fix_et
     return DSM_OK;
 }
 
+// ---------------------------------------------------------------- the chain with the LAST n_held haplotypes held
+// The MT19937 words of held sweeps: V F per sweep instead of V G.  SweepWords sizes its chunks and addresses its sweeps by
+// c->u_cap, which is set to V F for the lifetime of this object (the buffers were sized for V G: every chunk still fits).
+struct HeldWordsPerSweep {
+    dsm_ctx *c; size_t saved;
+    HeldWordsPerSweep(dsm_ctx *ctx, int n_held) : c(ctx), saved(ctx->u_cap) { c->u_cap = (size_t)c->V * (c->G - n_held); }
+    ~HeldWordsPerSweep() { c->u_cap = saved; }
+};
+
+extern "C" int dsm_ctx_sample_tau_held(dsm_ctx *c, int n_held, int *nchange)
+{
+    TRY(need(c, true, true));
+    if (n_held < 0 || n_held > c->G) { dsm_set_error("sample_tau_held: n_held = %d outside 0..%d", n_held, c->G); return DSM_ERR_ARG; }
+    if (n_held == 0) return dsm_ctx_sample_tau(c, nchange, nullptr);
+    if (n_held == c->G) { c->iter_ctr++; if (nchange) *nchange = 0; return DSM_OK; }      // a sweep over no haplotype
+    BIND(c);
+    HeldWordsPerSweep per(c, n_held);
+    const uint32_t *u = nullptr;
+    SweepWords words(c, 1);
+    HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
+    TRY(words.acquire(0, &u));
+    TRY(k_held_sweep(c, n_held, c->gamma, c->eta, c->iter_ctr++, u));
+    TRY(words.release(0));
+    int n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, c->nchange, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (nchange) *nchange = n;
+    return DSM_OK;
+}
+
+// Per iteration, as gibbs_update with the sweep replaced: the mu/E pass at (tau, gamma, eta), the Dirichlet launch (gamma_new, eta_new,
+// traces, prior terms; it finalizes the previous iteration), the held sweep with (gamma_new, eta_old) -- the operands of gibbs_update's
+// mode-3 call --, the likelihood-only pass at (tau_new, gamma_new, eta_new), which writes the iteration's slot of the tau trace and the
+// ll partials.  fix_eta as in fixed_tau_loop: the sweep and the likelihood then both read the held matrix.
+static int held_tau_loop(dsm_ctx *c, int n_iter, int n_held, bool fix_eta)
+{
+    const int spec = stats_spec(c);
+    const bool agg = spec >= 2;
+    const bool fuse_s2 = agg && c->G < 10;
+    const size_t sg = (size_t)c->S * c->G;
+    HeldWordsPerSweep per(c, n_held);
+    TRY(alloc_traces(c, n_iter));
+    HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
+    HIP_TRY(hipMemsetAsync(c->sum_mu, 0, sg * sizeof(unsigned long long), c->stream));
+    TRY(esum_reset(c));
+    TRY(eval_state(c, c->gamma, c->eta, c->tau_trace, 1));                     // entry state: ll, lp, storeStarState(0); tau -> slot 0
+    TRY(stats_ensure_ntab(c));
+    Scratch<double> held;                                                      // fix_eta: the four prior terms of the held matrix
+    if (fix_eta && n_iter > 0) {
+        TRY(held.alloc((size_t)c->S + 4));
+        TRY(k_prior(c, c->gamma, c->eta, held));
+        TRY(k_fixtau_fill_eta(c, c->eta, c->eta_trace, n_iter));
+    }
+    SweepWords words(c, n_iter);
+    TRY(words.prefetch());
+    int nb_prev = 0;
+    for (int it = 0; it < n_iter; ++it) {
+        const uint32_t ic = c->iter_ctr++;
+        TRY(agg ? k_stats_stage1(c, ic) : k_stats_v1(c, ic));
+        if (agg && !fuse_s2) TRY(k_stats_stage2(c, ic));
+        TRY(k_dirichlet(c, ic, c->gamma, c->gamma_trace + (size_t)it * sg, c->eta_new, fix_eta ? nullptr : c->eta_trace + (size_t)it * 16,
+                        prior_slot(c, it), it - 1, nb_prev, prior_slot(c, it - 1), fuse_s2 ? 1 : 0));
+        const uint32_t *u = nullptr;
+        TRY(words.acquire(it, &u));
+        TRY(k_held_sweep(c, n_held, c->gamma, c->eta, ic, u));
+        TRY(words.release(it));
+        if (fix_eta) HIP_TRY(hipMemcpyAsync(prior_slot(c, it) + c->S, held.p + c->S, 4 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        else std::swap(c->eta, c->eta_new);
+        TRY(k_tau_sweep(c, 2, c->gamma, c->eta, c->eta, c->tau_trace + (size_t)(it + 1) * c->V, nullptr, 0, &nb_prev, nullptr));
+    }
+    const bool want_rare = n_iter > 0 && c->tau_neartie_mode == -1;             // as the Gibbs loop: what the next call's choice of sweep goes by
+    if (want_rare && !c->h_rare) HIP_TRY(hipHostMalloc((void **)&c->h_rare, sizeof(int), hipHostMallocDefault));
+    if (n_iter > 0)
+        TRY(k_finalize(c, nb_prev, n_iter - 1, 0, prior_slot(c, n_iter - 1), c->gamma_trace + (size_t)(n_iter - 1) * sg,
+                       c->eta_trace + (size_t)(n_iter - 1) * 16, 0, want_rare ? c->h_rare : nullptr));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream_rng));
+    if (want_rare) c->tau_rare_n = *c->h_rare;
+    return DSM_OK;
+}
+
+extern "C" int dsm_ctx_gibbs_update_held_tau(dsm_ctx *c, int n_iter, int n_held, int fix_eta)
+{
+    if (n_iter < 0) { dsm_set_error("n_iter < 0"); return DSM_ERR_ARG; }
+    TRY(need(c, true, true));
+    if (n_held < 0 || n_held > c->G) { dsm_set_error("gibbs_update_held_tau: n_held = %d outside 0..%d", n_held, c->G); return DSM_ERR_ARG; }
+    if (n_held == 0) return dsm_ctx_gibbs_update(c, n_iter);
+    if (n_held == c->G) return dsm_ctx_gibbs_update_fixed_tau(c, n_iter, fix_eta, 0);
+    BIND(c);
+    if (c->tau_rng == DSM_RNG_MT19937 && n_iter > 0 && !c->mt_seeded) { dsm_set_error("tau RNG not seeded: call dsm_ctx_seed / dsm_setRNG"); return DSM_ERR_STATE; }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream_rng));
+    return held_tau_loop(c, n_iter, n_held, fix_eta != 0);
+}
+
 // test hook: the pooled table the call above would run on for the resident state -- *W words, pooled [W][S][4] (room for [V][S][4]),
 // words [W] ascending (room for V), row [V].  Any pointer may be null.
 extern "C" int dsm_ctx_debug_fixtau_pool(dsm_ctx *c, int *W, int32_t *pooled, uint64_t *words, int32_t *row)

@@ -241,6 +241,7 @@ int k_tau_sweep(dsm_ctx *c, int mode, const double *gamma, const double *eta_swe
                 const double *eta_ll, uint64_t *trace_slot, double *d_logp, uint32_t iter, int *nblocks,
                 const uint32_t *u_raw, int slot = 0, const TauFinalRider *rider = nullptr);
 int tau_launch_info(dsm_ctx *c, int *launched, int *resident);
+int tau_shape(int S, int *lpv, int *nsl);      // lanes per position and sample slots per lane of the sweep kernels for S samples
 int k_shard_pack(dsm_ctx *c, int nblocks);
 int k_shard_unpack(dsm_ctx *c);
 int k_finalize(dsm_ctx *c, int nblocks, int it, int star_mode, const double *prior, const double *gamma_src,
@@ -250,6 +251,10 @@ int k_finalize(dsm_ctx *c, int nblocks, int it, int star_mode, const double *pri
 int k_fixtau_pool(dsm_ctx *c, const int32_t *d_row, int32_t *d_pooled);           // pooled[row[v]][s][b] += counts[v][s][b]
 int k_fixtau_fill_eta(dsm_ctx *c, const double *eta, double *eta_trace, int n);   // n trace rows = one matrix
 int k_fixtau_add_const(dsm_ctx *c, int n, double K);                              // ll / lp of the traces, the MAP record and the last evaluation += K
+
+// ---- launchers (kernels_heldtau.hip)
+// one sweep over haplotypes 0 .. G - n_held - 1 of the resident tau (0 < n_held < G); u_raw = V (G - n_held) MT19937 words or, Philox, null
+int k_held_sweep(dsm_ctx *c, int n_held, const double *gamma, const double *eta, uint32_t iter, const uint32_t *u_raw);
 
 // ---- launchers (kernels_relabel.hip): reductions of the tau trace; trace_stride = words between two iterations' rows (0: one row for all)
 int k_trace_snd(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const uint64_t *ref, int Gr, int n_it, int *d_out);   // ref null: each iteration against itself

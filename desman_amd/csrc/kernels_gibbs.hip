@@ -1559,7 +1559,7 @@ static void launch_tau(dsm_ctx *c, int mode, const TauParams &p, int grid, size_
 }
 
 // lanes per variant and sample slots per lane of the sweep kernel for a table of S samples
-static int tau_shape(int S, int *lpv, int *nsl)
+int tau_shape(int S, int *lpv, int *nsl)
 {
     int LPV, NSL;
     if (S <= 16) { LPV = 16; NSL = 1; }

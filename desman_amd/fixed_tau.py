@@ -55,7 +55,7 @@ def posterior_gamma(counts, tau, eta, n_iter=1000, burn=200, fix_eta=True, level
     """Posterior of the abundances of the haplotypes ``tau`` ([V,G] digits or [V,G,4] one-hot) in the samples of ``counts`` [V,S,4]
     under gamma_s ~ Dir(alpha), with tau held and eta [4,4] held (fix_eta) or sampled under eta_a ~ Dir(delta) from ``eta`` as the
     start: n_iter iterations of the fixed-tau chain from uniform abundance rows, stream key ``seed``, the first ``burn`` dropped.
-    Returns summarize() of the kept gamma draws ([n_iter - burn, S, G]) plus ll (kept iterations) and -- with fix_eta=False -- eta_mean,
+    Returns summarize() of the kept gamma draws ([n_iter - burn, S, G]) plus ll (kept iterations), lp_star and -- with fix_eta=False -- eta_mean,
     eta_sd [4,4] and eta_draws."""
     from . import _lib
     x = np.ascontiguousarray(counts, dtype=np.int64)
@@ -77,10 +77,12 @@ def posterior_gamma(counts, tau, eta, n_iter=1000, burn=200, fix_eta=True, level
         ctx.seed(1, ctr_seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
         ctx.gibbs_update_fixed_tau(n_iter, fix_eta=fix_eta, pool=pool)
         tr = ctx.get_trace()
+        lp_star = float(ctx.get_star()["lp"])
     finally:
         ctx.close()
     res = summarize(tr["gamma"][burn:], level)
     res["ll"] = tr["ll"][burn:]
+    res["lp_star"] = lp_star                              # lp of the MAP record over the whole chain (the entry state included)
     if not fix_eta:
         e = summarize(tr["eta"][burn:], level)
         res["eta_mean"], res["eta_sd"], res["eta_draws"] = e["mean"], e["sd"], e["draws"]

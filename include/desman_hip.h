@@ -204,6 +204,30 @@ int dsm_ctx_gibbs_update_fixed_tau(dsm_ctx *ctx, int n_iter, int fix_eta, int po
 int dsm_ctx_debug_fixtau_pool(dsm_ctx *ctx, int *W, int32_t *pooled, uint64_t *words, int32_t *row);
 int dsm_ctx_debug_fixtau_sample_stats(dsm_ctx *ctx, uint32_t iter, uint64_t *sum_mu, uint64_t *esum);
 
+/* The chain with the LAST n_held haplotypes held and haplotypes 0 .. F-1, F = G - n_held, sampled: a haplotype known
+ * from an isolate anchors the fit of the rest, or the haplotypes of a finished run are held while further ones are fitted to new samples
+ * (`desman-abund --novel`).  Callers order their haplotypes so that the held ones come last; there is no mask.
+ *   dsm_ctx_sample_tau_held: one sweep over the free haplotypes of the resident state with the resident gamma / eta, the counterpart of
+ *     dsm_ctx_sample_tau: every step is that sweep's step (the rest mixture runs over all other haplotypes, held ones included), in plain
+ *     fp64; the held digits are only read.  *nchange = changed (position, free haplotype) pairs.  The iteration counter advances by one.
+ *     DSM_RNG_MT19937: the sweep consumes exactly V F words of the context's stream, position-major, free haplotype ascending (word
+ *     v F + g decides step (v, g)); DSM_RNG_PHILOX: step (v, g) is keyed as the full sweep keys it, so the free digits are those
+ *     dsm_ctx_sample_tau draws at the same counter.  n_held = 0 is dsm_ctx_sample_tau(ctx, nchange, NULL); n_held = G changes nothing
+ *     but the counter and consumes no word.
+ *   dsm_ctx_gibbs_update_held_tau: n_iter iterations of dsm_ctx_gibbs_update with the sweep replaced by the held sweep -- the mu/E pass
+ *     under the context's own specification, the gamma and eta draws, the held sweep with (new gamma, previous eta), ll / lp of the new
+ *     state; the entry state is evaluated and recorded first.  Results as after dsm_ctx_gibbs_update: all traces (dsm_ctx_get_tau_at,
+ *     dsm_ctx_get_tau_sum and the dsm_ctx_trace_* reductions read one stored tau per iteration), the MAP record, the state.  fix_eta != 0
+ *     holds eta exactly as dsm_ctx_gibbs_update_fixed_tau does: the draw is made, the chain's eta, the trace rows and the MAP record's eta
+ *     stay the entry matrix, and the sweep and ll / lp read it.  The MT19937 stream advances by n_iter V F words; the iteration counter
+ *     by n_iter; a call of 2 n iterations is two calls of n, bit for bit.
+ *     n_held = 0: the call IS dsm_ctx_gibbs_update(ctx, n_iter) (fix_eta is not looked at); n_held = G: it IS
+ *     dsm_ctx_gibbs_update_fixed_tau(ctx, n_iter, fix_eta, 0).
+ * Limits: those of dsm_ctx_gibbs_update for a single chain.  DSM_ERR_ARG for n_iter < 0 or n_held outside 0..G, DSM_ERR_STATE without
+ * counts or state (or, MT19937, without a seeded stream).  No batched or sharded form.                                              */
+int dsm_ctx_sample_tau_held(dsm_ctx *ctx, int n_held, int *nchange);
+int dsm_ctx_gibbs_update_held_tau(dsm_ctx *ctx, int n_iter, int n_held, int fix_eta);
+
 /* results of the last update call.  Any pointer may be NULL.                 */
 int dsm_ctx_get_trace(dsm_ctx *ctx, double *ll, double *lp, int32_t *nchange,
                       double *gamma_store, double *eta_store);
