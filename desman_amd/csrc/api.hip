@@ -577,19 +577,20 @@ extern "C" int dsm_ctx_set_tau_rng(dsm_ctx *c, int mode)
 }
 
 // The MT19937 words of the tau sweeps of one call.  The stream is serial, but a call knows how many sweeps it will run
-// (V*G words each), so the side stream generates them in CHUNKS of several sweeps, one chunk ahead of the reader, into two
+// (`per` words each), so the side stream generates them in CHUNKS of several sweeps, one chunk ahead of the reader, into two
 // slots: one cross-stream event pair per chunk instead of per sweep (each pair costs a bubble of several microseconds
 // between two launches of the main stream).  Chunks start small so that the first sweep is not kept waiting and grow
 // by <= 1.5x, slower than the generator outruns the fastest reader (the 82 us tau-only sweeps of updateTau vs 50 us per fill).
 struct SweepWords {
     dsm_ctx *c;
-    int total, filled = 0, nchunk = 0;
+    int total;
+    size_t per;                                         // words per sweep: c->u_cap = V*G, or V*F of a held sweep (the slots are sized for V*G)
+    int filled = 0, nchunk = 0;
     int first[2] = {0, 0}, len[2] = {0, 0};             // sweeps held by each slot
     int max_len = 1;
-    SweepWords(dsm_ctx *ctx, int n_sweeps) : c(ctx), total(n_sweeps)
+    SweepWords(dsm_ctx *ctx, int n_sweeps, size_t words_per_sweep) : c(ctx), total(n_sweeps), per(words_per_sweep)
     {
-        const size_t per = std::max<size_t>(1, c->u_cap);
-        max_len = (int)std::max<size_t>(1, std::min<size_t>(DSM_U_CHUNK, c->u_chunk_words / per));
+        max_len = (int)std::max<size_t>(1, std::min<size_t>(DSM_U_CHUNK, c->u_chunk_words / std::max<size_t>(1, per)));
     }
     bool active() const { return c->tau_rng == DSM_RNG_MT19937; }
     int fill_next()
@@ -600,7 +601,7 @@ struct SweepWords {
         const int slot = nchunk & 1;
         uint32_t *buf = c->u_raw + (size_t)slot * c->u_chunk_words;
         HIP_TRY(hipStreamWaitEvent(c->stream_rng, c->ev_u_free[slot], 0));   // the last reader of this slot is done
-        TRY(k_mt_fill(c, buf, (size_t)want * c->u_cap, c->stream_rng));
+        TRY(k_mt_fill(c, buf, (size_t)want * per, c->stream_rng));
         HIP_TRY(hipEventRecord(c->ev_u_ready[slot], c->stream_rng));
         first[slot] = filled; len[slot] = want;
         filled += want; ++nchunk;
@@ -626,7 +627,7 @@ struct SweepWords {
             if (filled < total) TRY(fill_next());            // keep one chunk ahead (into the other slot)
             HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_u_ready[slot], 0));
         }
-        *u = c->u_raw + (size_t)slot * c->u_chunk_words + (size_t)(it - first[slot]) * c->u_cap;
+        *u = c->u_raw + (size_t)slot * c->u_chunk_words + (size_t)(it - first[slot]) * per;
         return DSM_OK;
     }
     int release(int it)
@@ -639,18 +640,23 @@ struct SweepWords {
 };
 
 // ---------------------------------------------------------------- single steps
-extern "C" int dsm_ctx_sample_tau(dsm_ctx *c, int *nchange, double *logp_out)
+// One sweep of the resident state with the resident gamma / eta over haplotypes 0 .. G - n_held - 1: the full sweep (n_held = 0, the
+// only one with logp_out) or the held sweep of DESIGN.md sec. 8e, which consumes V F words of the MT19937 stream instead of V G.
+static int sample_tau_once(dsm_ctx *c, int n_held, int *nchange, double *logp_out)
 {
     TRY(need(c, true, true));
+    if (n_held < 0 || n_held > c->G) { dsm_set_error("sample_tau_held: n_held = %d outside 0..%d", n_held, c->G); return DSM_ERR_ARG; }
+    if (n_held == c->G) { c->iter_ctr++; if (nchange) *nchange = 0; return DSM_OK; }      // a sweep over no haplotype
     BIND(c);
     Scratch<double> d_logp;
     const size_t nl = (size_t)c->V * c->G * 4;
     if (logp_out) TRY(d_logp.alloc(nl));
     const uint32_t *u = nullptr;
-    SweepWords words(c, 1);
+    SweepWords words(c, 1, n_held ? (size_t)c->V * (c->G - n_held) : c->u_cap);
     HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
     TRY(words.acquire(0, &u));
-    TRY(k_tau_sweep(c, 1, c->gamma, c->eta, c->eta, nullptr, d_logp, c->iter_ctr++, nullptr, u));
+    TRY(n_held ? k_held_sweep(c, n_held, c->gamma, c->eta, c->iter_ctr++, u)
+               : k_tau_sweep(c, 1, c->gamma, c->eta, c->eta, nullptr, d_logp, c->iter_ctr++, nullptr, u));
     TRY(words.release(0));
     int n = 0;
     HIP_TRY(hipMemcpyAsync(&n, c->nchange, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -660,6 +666,9 @@ extern "C" int dsm_ctx_sample_tau(dsm_ctx *c, int *nchange, double *logp_out)
     if (nchange) *nchange = n;
     return DSM_OK;
 }
+
+extern "C" int dsm_ctx_sample_tau(dsm_ctx *c, int *nchange, double *logp_out) { return sample_tau_once(c, 0, nchange, logp_out); }
+extern "C" int dsm_ctx_sample_tau_held(dsm_ctx *c, int n_held, int *nchange) { return sample_tau_once(c, n_held, nchange, nullptr); }
 
 extern "C" int dsm_ctx_sample_stats(dsm_ctx *c, uint32_t iter, uint64_t *sum_mu, uint64_t *esum)
 {
@@ -872,12 +881,22 @@ static int same_G_and_rng(const dsm_ctx *a, const dsm_ctx *b, int k)
 // the Dirichlet log-prior terms of iteration it (two slots, by parity)
 static double *prior_slot(dsm_ctx *c, int it) { return c->prior + (it & 1) * (DSM_MAX_S + 4); }
 
+// The tau step of a Gibbs iteration: the LAST n_held haplotypes are held.  0 = the full chain (the sweep and the likelihood of the new
+// state are one launch: k_tau_sweep mode 3); 0 < n_held < G = the partly held chain (k_held_sweep, V F words of the
+// MT19937 stream per sweep, then the likelihood-only pass, k_tau_sweep mode 2, which also stores tau); n_held = G = tau fixed
+// (HaploSNP_Sampler.py:409-428, update_fixed_tau; sec. 8c: no sweep, no word generated or consumed, the likelihood-only pass, tau stored
+// once -- dsm_host.h: tau_fixed_trace).  fix_eta (n_held > 0 only): the E sums and the eta draw are still made, but the chain's eta, the
+// trace rows, the prior terms, the sweep and the likelihood all stay at the matrix the call came in with.
+struct TauStep { int n_held = 0; bool fix_eta = false; };
+
 // The Gibbs loop of one chain (unbatched) or of K chains of one shape sharing every launch of the iteration.  A chain ends in the same
 // state either way: the mu/E specification is the chain's own (round 5; the per-read pass of small or shallow tables and of G > 16 is
-// launched chain by chain, everything else is shared).
-static int gibbs_update(dsm_ctx *const *ctxs, int K, bool batched, int n_iter)
+// launched chain by chain, everything else is shared).  Per iteration: the mu/E pass at (tau, gamma, eta), the Dirichlet launch (gamma_new,
+// eta_new, traces, prior terms; it finalizes the previous iteration), the tau step.
+static int gibbs_update(dsm_ctx *const *ctxs, int K, bool batched, int n_iter, TauStep step = TauStep{})
 {
     if (n_iter < 0) { dsm_set_error("n_iter < 0"); return DSM_ERR_ARG; }
+    if (batched && step.n_held) { dsm_set_error("batch: no held haplotypes (the held sweep has no batched form)"); return DSM_ERR_UNSUPPORTED; }
     Chains ch{ctxs, K, batched};
     TRY(ch.open(true, false, [](const dsm_ctx *a, const dsm_ctx *b, int k) -> int {
         TRY(same_G_and_rng(a, b, k));
@@ -887,6 +906,7 @@ static int gibbs_update(dsm_ctx *const *ctxs, int K, bool batched, int n_iter)
         return DSM_ERR_ARG;
     }));
     dsm_ctx *const lead = ch.lead();
+    const bool full = step.n_held == 0, fixed = step.n_held == lead->G, fix_eta = step.fix_eta && !full;
     const int spec = stats_spec(lead);
     // sampleMu (:341): spec v2 = stage 1, then stage 2 inside the Dirichlet launch; spec v1 = the per-read pass
     const bool agg = spec >= 2;
@@ -899,39 +919,59 @@ static int gibbs_update(dsm_ctx *const *ctxs, int K, bool batched, int n_iter)
     std::vector<int> nb_prev(K, 0);
     std::vector<uint32_t> ic(K);
     std::vector<const uint32_t *> u(K, nullptr);
+    Scratch<double> held;                               // fix_eta: the four prior terms of the held matrix
     TRY(ch.each([&](dsm_ctx *c, int) -> int {
         TRY(alloc_traces(c, n_iter));
+        c->tau_fixed_trace = fixed;
         HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
-        // entry state: ll, lp, storeStarState(0)  (HaploSNP_Sampler.py:336-338)
+        if (!full) {
+            HIP_TRY(hipMemsetAsync(c->sum_mu, 0, sg * sizeof(unsigned long long), c->stream));
+            TRY(esum_reset(c));                         // Esum and every partial copy of it (a failed pass may have left counts there)
+        }
+        // entry state: ll, lp, storeStarState(0)  (HaploSNP_Sampler.py:336-338); tau -> slot 0 of the trace
         TRY(eval_state(c, c->gamma, c->eta, c->tau_trace, 1));
         TRY(stats_ensure_ntab(c));
-        if (!batched) TRY(k_tau_neartie_hint(c));       // which instantiation of the sweep this call runs (same draws either way)
-        words.emplace_back(c, n_iter);
+        if (full && !batched) TRY(k_tau_neartie_hint(c));   // which instantiation of the full sweep this call runs (same draws either way)
+        if (fix_eta && n_iter > 0) {
+            TRY(held.alloc((size_t)c->S + 4));
+            TRY(k_prior(c, c->gamma, c->eta, held));
+            TRY(k_fixtau_fill_eta(c, c->eta, c->eta_trace, n_iter));
+        }
+        words.emplace_back(c, fixed ? 0 : n_iter, full ? c->u_cap : (size_t)c->V * (c->G - step.n_held));
         return DSM_OK;
     }));
     TRY(ch.launch([&](dsm_ctx *, int k) { return words[k].prefetch(); }));
     for (int it = 0; it < n_iter; ++it) {
-        // (the abundances move during a burn-in: the choice of the sweep's instantiation is looked at again now and then -- a stream
+        // (the abundances move during a burn-in: the choice of the full sweep's instantiation is looked at again now and then -- a stream
         // synchronisation and a 4-byte read-back every 64 iterations; the draws do not depend on it)
-        if (!batched && it && (it & 63) == 0 && lead->tau_neartie_mode == -1) { TRY(k_tau_rare_count(lead, true)); TRY(k_tau_neartie_hint(lead)); }
+        if (full && !batched && it && (it & 63) == 0 && lead->tau_neartie_mode == -1) { TRY(k_tau_rare_count(lead, true)); TRY(k_tau_neartie_hint(lead)); }
         TRY(ch.launch([&](dsm_ctx *c, int k) { ic[k] = c->iter_ctr++; return agg ? k_stats_stage1(c, ic[k]) : k_stats_v1(c, ic[k]); }));
         if (agg && !fuse_s2) TRY(ch.launch([&](dsm_ctx *c, int k) { return k_stats_stage2(c, ic[k]); }));
         // sampleGamma (:342) + the eta draw (:347: eta depends only on the E sums) + traces; the same
         // launch finalizes iteration it-1 (ll, lp, MAP test :349-353) in one extra workgroup
         TRY(ch.launch([&](dsm_ctx *c, int k) {
-            return k_dirichlet(c, ic[k], c->gamma, c->gamma_trace + (size_t)it * sg, c->eta_new, c->eta_trace + (size_t)it * 16,
+            return k_dirichlet(c, ic[k], c->gamma, c->gamma_trace + (size_t)it * sg, c->eta_new, fix_eta ? nullptr : c->eta_trace + (size_t)it * 16,
                                prior_slot(c, it), it - 1, nb_prev[k], prior_slot(c, it - 1), fuse_s2 ? 1 : 0);
         }));
-        // tau sweep with (gamma_new, eta_old) (:345) + log-likelihood of the new state with eta_new (:349)
-        TRY(ch.launch([&](dsm_ctx *, int k) { return words[k].acquire(it, &u[k]); }));
-        TRY(ch.launch([&](dsm_ctx *c, int k) {
-            return k_tau_sweep(c, 3, c->gamma, c->eta, c->eta_new, c->tau_trace + (size_t)(it + 1) * c->V, nullptr, ic[k], &nb_prev[k], u[k]);
-        }));
-        TRY(ch.each([&](dsm_ctx *c, int k) -> int {
-            TRY(words[k].release(it));
-            std::swap(c->eta, c->eta_new);                               // eta_new becomes the chain's eta
+        // tau sweep with (gamma_new, eta_old) (:345); the full sweep's launch is also the log-likelihood of the new state with eta_new (:349)
+        if (!fixed) {
+            TRY(ch.launch([&](dsm_ctx *, int k) { return words[k].acquire(it, &u[k]); }));
+            TRY(ch.launch([&](dsm_ctx *c, int k) {
+                if (!full) return k_held_sweep(c, step.n_held, c->gamma, c->eta, ic[k], u[k]);
+                return k_tau_sweep(c, 3, c->gamma, c->eta, c->eta_new, c->tau_trace + (size_t)(it + 1) * c->V, nullptr, ic[k], &nb_prev[k], u[k]);
+            }));
+            TRY(ch.each([&](dsm_ctx *, int k) { return words[k].release(it); }));
+        }
+        TRY(ch.each([&](dsm_ctx *c, int) -> int {
+            if (fix_eta) HIP_TRY(hipMemcpyAsync(prior_slot(c, it) + c->S, held.p + c->S, 4 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            else std::swap(c->eta, c->eta_new);                          // eta_new becomes the chain's eta
             return DSM_OK;
         }));
+        // held and fixed: the likelihood-only pass at (tau_new, gamma_new, eta_new); it stores tau_new where tau moves
+        if (!full)
+            TRY(ch.each([&](dsm_ctx *c, int k) {
+                return k_tau_sweep(c, 2, c->gamma, c->eta, c->eta, fixed ? nullptr : c->tau_trace + (size_t)(it + 1) * c->V, nullptr, 0, &nb_prev[k], nullptr);
+            }));
     }
     // the last iteration's finalize launch of a chain run alone also counts the haplotypes that are rare in every sample -- what the next
     // call's choice of sweep instantiation goes by -- straight into the host's pinned word: it rides on this call's own launch and synchronisation
@@ -943,6 +983,7 @@ static int gibbs_update(dsm_ctx *const *ctxs, int K, bool batched, int n_iter)
                               c->eta_trace + (size_t)(n_iter - 1) * 16, 0, want_rare ? c->h_rare : nullptr);
         }));
     HIP_TRY(hipStreamSynchronize(lead->stream));
+    if (!full && !fixed) HIP_TRY(hipStreamSynchronize(lead->stream_rng));
     if (want_rare) lead->tau_rare_n = *lead->h_rare;
     return DSM_OK;
 }
@@ -970,6 +1011,7 @@ int comm_device(const dsm_comm *m);
 
 // the loop of both forms: exchange != null -- the caller's all-reduce, called with the stream drained; comm != null -- RCCL
 // all-reduces enqueued on the chain's stream by the library (no host synchronisation inside the loop)
+// (not run through gibbs_update: its exchanges sit between stage 1 and stage 2 and around every finalize -- hooks there, no code saved)
 static int gibbs_update_sharded(dsm_ctx *c, int n_iter, int v_offset, int v_total, dsm_exchange_fn exchange, void *user, dsm_comm *comm)
 {
     TRY(need(c, true, true));
@@ -1007,25 +1049,24 @@ static int gibbs_update_sharded(dsm_ctx *c, int n_iter, int v_offset, int v_tota
         TRY(esum_reset(c));
     }
     TRY(stats_ensure_ntab(c));
-    double *const P[2] = {c->prior, c->prior + (DSM_MAX_S + 4)};
+    const bool fuse_s2 = c->G < 10;
     int nb_prev = 0;
     for (int it = 0; it < n_iter; ++it) {
         const uint32_t ic = c->iter_ctr++;
-        const bool fuse_s2 = c->G < 10;
         TRY(k_stats_stage1(c, ic));                                   // this shard's cells -> its subset table and Esum
         TRY(k_shard_pack(c, nb_prev));                                // + ll / nchange of the previous sweep
         TRY(swap_vec(c->ntab, c->ntab_len));
         TRY(k_shard_unpack(c));
         if (!fuse_s2) TRY(k_stats_stage2(c, ic));
         TRY(k_dirichlet(c, ic, c->gamma, c->gamma_trace + (size_t)it * sg, c->eta_new, c->eta_trace + (size_t)it * 16,
-                        P[it & 1], it - 1, nb_prev, P[(it - 1) & 1], fuse_s2 ? 1 : 0));
+                        prior_slot(c, it), it - 1, nb_prev, prior_slot(c, it - 1), fuse_s2 ? 1 : 0));
         TRY(k_tau_sweep(c, 3, c->gamma, c->eta, c->eta_new, c->tau_trace + (size_t)(it + 1) * c->V, nullptr, ic, &nb_prev, nullptr));
         std::swap(c->eta, c->eta_new);
     }
     if (n_iter > 0) {
         TRY(k_shard_pack(c, nb_prev));
         TRY(swap_vec(nullptr, 0));
-        TRY(k_finalize(c, nb_prev, n_iter - 1, 0, P[(n_iter - 1) & 1], c->gamma_trace + (size_t)(n_iter - 1) * sg,
+        TRY(k_finalize(c, nb_prev, n_iter - 1, 0, prior_slot(c, n_iter - 1), c->gamma_trace + (size_t)(n_iter - 1) * sg,
                        c->eta_trace + (size_t)(n_iter - 1) * 16));
         TRY(esum_reset(c));
     }
@@ -1098,7 +1139,7 @@ static int update_tau(dsm_ctx *const *ctxs, int K, bool batched, int n_iter, con
     const size_t sg = (size_t)ch.lead()->S * ch.lead()->G;
     std::vector<SweepWords> words;
     words.reserve(K);
-    TRY(ch.each([&](dsm_ctx *c, int) -> int { TRY(alloc_traces(c, n_iter)); words.emplace_back(c, n_iter); return DSM_OK; }));
+    TRY(ch.each([&](dsm_ctx *c, int) -> int { TRY(alloc_traces(c, n_iter)); words.emplace_back(c, n_iter, c->u_cap); return DSM_OK; }));
     TRY(ch.launch([&](dsm_ctx *, int k) { return words[k].prefetch(); }));          // (generating while the inputs go in)
     TRY(ch.each([&](dsm_ctx *c, int k) { return tau_inputs(c, n_iter, gamma_stores[k], eta_stores[k]); }));
     std::vector<int> nb_prev(K, 0);
@@ -1134,50 +1175,6 @@ extern "C" int dsm_batch_update_tau(dsm_ctx *const *ctxs, int K, int n_iter, con
 }
 
 // ---------------------------------------------------------------- the chain with tau held (HaploSNP_Sampler.py:409-428, update_fixed_tau)
-// Per iteration: the mu/E pass at (tau, gamma, eta), the Dirichlet launch (gamma_new, eta_new, traces, prior terms; it finalizes the
-// previous iteration), the likelihood-only pass at (tau, gamma_new, eta_new).  No sweep: no MT19937 word is generated or consumed, tau is
-// stored once (slot 0 of the trace stands for every iteration: dsm_host.h, tau_fixed_trace).  fix_eta: the E sums and the eta draw are
-// still made, but the chain's eta, the trace rows, the prior terms and the likelihood all stay at the matrix the call came in with.
-static int fixed_tau_loop(dsm_ctx *c, int n_iter, bool fix_eta)
-{
-    const int spec = stats_spec(c);
-    const bool agg = spec >= 2;
-    const bool fuse_s2 = agg && c->G < 10;
-    const size_t sg = (size_t)c->S * c->G;
-    TRY(alloc_traces(c, n_iter));
-    c->tau_fixed_trace = true;
-    HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
-    HIP_TRY(hipMemsetAsync(c->sum_mu, 0, sg * sizeof(unsigned long long), c->stream));
-    TRY(esum_reset(c));                                                        // Esum and every partial copy of it (a failed pass may have left counts there)
-    TRY(eval_state(c, c->gamma, c->eta, c->tau_trace, 1));                     // entry state: ll, lp, storeStarState(0); tau -> slot 0
-    TRY(stats_ensure_ntab(c));
-    Scratch<double> held;                                                      // fix_eta: the four prior terms of the held matrix
-    if (fix_eta && n_iter > 0) {
-        TRY(held.alloc((size_t)c->S + 4));
-        TRY(k_prior(c, c->gamma, c->eta, held));
-        TRY(k_fixtau_fill_eta(c, c->eta, c->eta_trace, n_iter));
-    }
-    int nb_prev = 0;
-    for (int it = 0; it < n_iter; ++it) {
-        const uint32_t ic = c->iter_ctr++;
-        TRY(agg ? k_stats_stage1(c, ic) : k_stats_v1(c, ic));
-        if (agg && !fuse_s2) TRY(k_stats_stage2(c, ic));
-        TRY(k_dirichlet(c, ic, c->gamma, c->gamma_trace + (size_t)it * sg, c->eta_new, fix_eta ? nullptr : c->eta_trace + (size_t)it * 16,
-                        prior_slot(c, it), it - 1, nb_prev, prior_slot(c, it - 1), fuse_s2 ? 1 : 0));
-        if (fix_eta) HIP_TRY(hipMemcpyAsync(prior_slot(c, it) + c->S, held.p + c->S, 4 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        else std::swap(c->eta, c->eta_new);
-        TRY(k_tau_sweep(c, 2, c->gamma, c->eta, c->eta, nullptr, nullptr, 0, &nb_prev, nullptr));
-    }
-    const bool want_rare = n_iter > 0 && c->tau_neartie_mode == -1;             // as the Gibbs loop: what the next call's choice of sweep goes by
-    if (want_rare && !c->h_rare) HIP_TRY(hipHostMalloc((void **)&c->h_rare, sizeof(int), hipHostMallocDefault));
-    if (n_iter > 0)
-        TRY(k_finalize(c, nb_prev, n_iter - 1, 0, prior_slot(c, n_iter - 1), c->gamma_trace + (size_t)(n_iter - 1) * sg,
-                       c->eta_trace + (size_t)(n_iter - 1) * 16, 0, want_rare ? c->h_rare : nullptr));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (want_rare) c->tau_rare_n = *c->h_rare;
-    return DSM_OK;
-}
-
 // The distinct packed tau words of the resident state in ascending order, and the row of each position's word.  overflow: a pooled
 // cell, or the four pooled cells of one (word, sample) together -- the depth dsm_ctx_set_counts bounds --, would pass INT32_MAX.
 struct FixtauWords { std::vector<uint64_t> words; std::vector<int32_t> row; bool overflow = false; };
@@ -1269,10 +1266,10 @@ extern "C" int dsm_ctx_gibbs_update_fixed_tau(dsm_ctx *c, int n_iter, int fix_et
         // auto: pooling is one pass over the table, less than one iteration's mu/E pass, so any reduction counts as worth it (not measured where it stops paying: DESIGN.md sec. 8c)
         pooled = !p.overflow && (pool == 1 || (int)p.words.size() < c->V);
     }
-    if (!pooled) return fixed_tau_loop(c, n_iter, fix_eta != 0);
+    if (!pooled) return gibbs_update(&c, 1, false, n_iter, TauStep{c->G, fix_eta != 0});
     dsm_ctx *k = nullptr;
     TRY(fixtau_enter(c, p, &k));
-    TRY(fixed_tau_loop(k, n_iter, fix_eta != 0));                              // (returns with the child's stream drained)
+    TRY(gibbs_update(&k, 1, false, n_iter, TauStep{k->G, fix_eta != 0}));      // (returns with the child's stream drained)
     // back to the caller: gamma, eta, traces, MAP record, iteration counter; its counts and tau were only read
     const size_t sg = (size_t)c->S * c->G, n = (size_t)n_iter;
     TRY(alloc_traces(c, n_iter));
@@ -1299,87 +1296,6 @@ extern "C" int dsm_ctx_gibbs_update_fixed_tau(dsm_ctx *c, int n_iter, int fix_et
 }
 
 // ---------------------------------------------------------------- the chain with the LAST n_held haplotypes held
-// The MT19937 words of held sweeps: V F per sweep instead of V G.  SweepWords sizes its chunks and addresses its sweeps by
-// c->u_cap, which is set to V F for the lifetime of this object (the buffers were sized for V G: every chunk still fits).
-struct HeldWordsPerSweep {
-    dsm_ctx *c; size_t saved;
-    HeldWordsPerSweep(dsm_ctx *ctx, int n_held) : c(ctx), saved(ctx->u_cap) { c->u_cap = (size_t)c->V * (c->G - n_held); }
-    ~HeldWordsPerSweep() { c->u_cap = saved; }
-};
-
-extern "C" int dsm_ctx_sample_tau_held(dsm_ctx *c, int n_held, int *nchange)
-{
-    TRY(need(c, true, true));
-    if (n_held < 0 || n_held > c->G) { dsm_set_error("sample_tau_held: n_held = %d outside 0..%d", n_held, c->G); return DSM_ERR_ARG; }
-    if (n_held == 0) return dsm_ctx_sample_tau(c, nchange, nullptr);
-    if (n_held == c->G) { c->iter_ctr++; if (nchange) *nchange = 0; return DSM_OK; }      // a sweep over no haplotype
-    BIND(c);
-    HeldWordsPerSweep per(c, n_held);
-    const uint32_t *u = nullptr;
-    SweepWords words(c, 1);
-    HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
-    TRY(words.acquire(0, &u));
-    TRY(k_held_sweep(c, n_held, c->gamma, c->eta, c->iter_ctr++, u));
-    TRY(words.release(0));
-    int n = 0;
-    HIP_TRY(hipMemcpyAsync(&n, c->nchange, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (nchange) *nchange = n;
-    return DSM_OK;
-}
-
-// Per iteration, as gibbs_update with the sweep replaced: the mu/E pass at (tau, gamma, eta), the Dirichlet launch (gamma_new, eta_new,
-// traces, prior terms; it finalizes the previous iteration), the held sweep with (gamma_new, eta_old) -- the operands of gibbs_update's
-// mode-3 call --, the likelihood-only pass at (tau_new, gamma_new, eta_new), which writes the iteration's slot of the tau trace and the
-// ll partials.  fix_eta as in fixed_tau_loop: the sweep and the likelihood then both read the held matrix.
-static int held_tau_loop(dsm_ctx *c, int n_iter, int n_held, bool fix_eta)
-{
-    const int spec = stats_spec(c);
-    const bool agg = spec >= 2;
-    const bool fuse_s2 = agg && c->G < 10;
-    const size_t sg = (size_t)c->S * c->G;
-    HeldWordsPerSweep per(c, n_held);
-    TRY(alloc_traces(c, n_iter));
-    HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
-    HIP_TRY(hipMemsetAsync(c->sum_mu, 0, sg * sizeof(unsigned long long), c->stream));
-    TRY(esum_reset(c));
-    TRY(eval_state(c, c->gamma, c->eta, c->tau_trace, 1));                     // entry state: ll, lp, storeStarState(0); tau -> slot 0
-    TRY(stats_ensure_ntab(c));
-    Scratch<double> held;                                                      // fix_eta: the four prior terms of the held matrix
-    if (fix_eta && n_iter > 0) {
-        TRY(held.alloc((size_t)c->S + 4));
-        TRY(k_prior(c, c->gamma, c->eta, held));
-        TRY(k_fixtau_fill_eta(c, c->eta, c->eta_trace, n_iter));
-    }
-    SweepWords words(c, n_iter);
-    TRY(words.prefetch());
-    int nb_prev = 0;
-    for (int it = 0; it < n_iter; ++it) {
-        const uint32_t ic = c->iter_ctr++;
-        TRY(agg ? k_stats_stage1(c, ic) : k_stats_v1(c, ic));
-        if (agg && !fuse_s2) TRY(k_stats_stage2(c, ic));
-        TRY(k_dirichlet(c, ic, c->gamma, c->gamma_trace + (size_t)it * sg, c->eta_new, fix_eta ? nullptr : c->eta_trace + (size_t)it * 16,
-                        prior_slot(c, it), it - 1, nb_prev, prior_slot(c, it - 1), fuse_s2 ? 1 : 0));
-        const uint32_t *u = nullptr;
-        TRY(words.acquire(it, &u));
-        TRY(k_held_sweep(c, n_held, c->gamma, c->eta, ic, u));
-        TRY(words.release(it));
-        if (fix_eta) HIP_TRY(hipMemcpyAsync(prior_slot(c, it) + c->S, held.p + c->S, 4 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        else std::swap(c->eta, c->eta_new);
-        TRY(k_tau_sweep(c, 2, c->gamma, c->eta, c->eta, c->tau_trace + (size_t)(it + 1) * c->V, nullptr, 0, &nb_prev, nullptr));
-    }
-    const bool want_rare = n_iter > 0 && c->tau_neartie_mode == -1;             // as the Gibbs loop: what the next call's choice of sweep goes by
-    if (want_rare && !c->h_rare) HIP_TRY(hipHostMalloc((void **)&c->h_rare, sizeof(int), hipHostMallocDefault));
-    if (n_iter > 0)
-        TRY(k_finalize(c, nb_prev, n_iter - 1, 0, prior_slot(c, n_iter - 1), c->gamma_trace + (size_t)(n_iter - 1) * sg,
-                       c->eta_trace + (size_t)(n_iter - 1) * 16, 0, want_rare ? c->h_rare : nullptr));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream_rng));
-    if (want_rare) c->tau_rare_n = *c->h_rare;
-    return DSM_OK;
-}
-
 extern "C" int dsm_ctx_gibbs_update_held_tau(dsm_ctx *c, int n_iter, int n_held, int fix_eta)
 {
     if (n_iter < 0) { dsm_set_error("n_iter < 0"); return DSM_ERR_ARG; }
@@ -1391,7 +1307,7 @@ extern "C" int dsm_ctx_gibbs_update_held_tau(dsm_ctx *c, int n_iter, int n_held,
     if (c->tau_rng == DSM_RNG_MT19937 && n_iter > 0 && !c->mt_seeded) { dsm_set_error("tau RNG not seeded: call dsm_ctx_seed / dsm_setRNG"); return DSM_ERR_STATE; }
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream_rng));
-    return held_tau_loop(c, n_iter, n_held, fix_eta != 0);
+    return gibbs_update(&c, 1, false, n_iter, TauStep{n_held, fix_eta != 0});
 }
 
 // test hook: the pooled table the call above would run on for the resident state -- *W words, pooled [W][S][4] (room for [V][S][4]),

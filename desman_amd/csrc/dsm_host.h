@@ -121,7 +121,7 @@ struct dsm_ctx {
     uint32_t *mt_jstates = nullptr; // starting arrays of the chunks of a parallel fill (kernels_gibbs.hip: mt_fill_parallel), made on first use
     bool mt_seeded = false;
     uint32_t *u_raw = nullptr;      // [2][u_chunk_words] raw MT19937 words: two slots of several sweeps each
-    size_t u_cap = 0;               // words per sweep = V*G
+    size_t u_cap = 0;               // words per full sweep = V*G; written only by ensure_state_buffers (a held sweep's V*F go to SweepWords as an argument)
     size_t u_chunk_words = 0;
     bool mt_attr_set = false;       // dynamic-LDS limit of the MT19937 kernel raised on this context's device
     uint64_t ctr_seed = 0x243F6A8885A308D3ull;

@@ -251,6 +251,87 @@ def test_two_calls_of_n_are_one_call_of_2n_and_runs_repeat(ctx, fix_eta, rng):
     assert all(np.array_equal(x, y) for x, y in zip(ctx.get_state(), one[5:8])) and np.array_equal(ctx.get_mt_state(), one[12])
 
 
+# ---- 6b. the seams of the one driver: the three forms share gibbs_update, the two single sweeps one body (api.hip) --------------------------
+SEAM_SHAPE = (257, 16, 5)
+
+
+def _seam_case():
+    V, S, G = SEAM_SHAPE
+    return synth_counts(V, S, G, seed=90)[0], random_state(V, S, G, seed=91)
+
+
+@pytest.mark.parametrize("rng", [_lib.RNG_MT19937, _lib.RNG_PHILOX])
+def test_forms_in_sequence_on_one_context_are_the_calls_run_alone(rng):
+    """held (n_held = 2), full, fixed (pool = 0), held (n_held = 4) on one context, 7 / 7 / 3 / 7 iterations (7 sweeps cross the 1-, 2- and
+    3-sweep chunks of SweepWords): after each call everything the context reports equals the same call run alone on a fresh context that was
+    given the state, the MT19937 stream and the counters the first one had before the call -- nothing one form sets (words per sweep,
+    tau_fixed_trace) reaches the next call"""
+    counts, (tau, gamma, eta) = _seam_case()
+    calls = [lambda c: c.gibbs_update_held_tau(7, 2), lambda c: c.gibbs_update(7),
+             lambda c: c.gibbs_update_fixed_tau(3, pool=0), lambda c: c.gibbs_update_held_tau(7, 4)]
+    a = _lib.Context(0)
+    try:
+        _load(a, counts, tau, gamma, eta, rng=rng)
+        for i, call in enumerate(calls):
+            before = a.checkpoint()
+            call(a)
+            b = _lib.Context(0)
+            try:
+                b.set_counts(counts)
+                b.restore(before)
+                b.set_tau_rng(rng)
+                call(b)
+                ea, eb = _everything(a), _everything(b)
+                assert len(ea) == len(eb)
+                for j, (x, y) in enumerate(zip(ea, eb)):
+                    assert np.array_equal(x, y), "call %d, item %d" % (i, j)
+            finally:
+                b.close()
+        assert a.counters() == (CTR_SEED, 24)
+    finally:
+        a.close()
+
+
+@pytest.mark.parametrize("n_held", [0, 2, SEAM_SHAPE[2]])
+def test_zero_iterations_are_gibbs_update_of_zero(ctx, ctx2, n_held):
+    counts, (tau, gamma, eta) = _seam_case()
+    _load(ctx, counts, tau, gamma, eta)
+    _load(ctx2, counts, tau, gamma, eta)
+    ctx.gibbs_update_held_tau(0, n_held)
+    ctx2.gibbs_update(0)
+    assert all(np.array_equal(x, y) for x, y in zip(ctx.get_state(), ctx2.get_state()))
+    assert np.array_equal(ctx.get_mt_state(), ctx2.get_mt_state()) and np.array_equal(ctx.get_mt_state(), _lib.mt_seed_state(MT_SEED))
+    sa, sb = ctx.get_star(), ctx2.get_star()
+    assert sorted(sa) == sorted(sb) and all(np.array_equal(sa[k], sb[k]) for k in sa)
+    assert np.array_equal(sa["tau"], tau) and np.array_equal(sa["gamma"], gamma) and np.array_equal(sa["eta"], eta)
+    assert ctx.counters() == (CTR_SEED, 0) and ctx2.counters() == (CTR_SEED, 0)
+
+
+def test_single_sweeps_in_sequence_are_the_oracle_composition(ctx):
+    """sample_tau_held(2), sample_tau(), sample_tau_held(2) on one seeded context: V (3 + 5 + 3) words of one GSL stream, in that order"""
+    V, S, G = SEAM_SHAPE
+    counts, (tau, gamma, eta) = _seam_case()
+    _load(ctx, counts, tau, gamma, eta)
+    mt = cbind.MT19937(MT_SEED)
+    got = []
+    n = ctx.sample_tau_held(2)
+    got.append((ctx.get_state()[0], n))
+    n = ctx.sample_tau()
+    got.append((ctx.get_state()[0], n))
+    n = ctx.sample_tau_held(2)
+    got.append((ctx.get_state()[0], n))
+    t1, n1 = H.held_sweep(tau, gamma, eta, counts, mt.uniform(V * 3), 2)
+    t2 = t1.copy()
+    n2 = cbind.sample_tau_u(t2, gamma, eta, np.ascontiguousarray(counts, dtype=np.int64), mt.uniform(V * 5))
+    t3, n3 = H.held_sweep(t2, gamma, eta, counts, mt.uniform(V * 3), 2)
+    want = [(t1, n1), (t2, n2), (t3, n3)]
+    for i, ((tg, ng), (tw, nw)) in enumerate(zip(got, want)):
+        assert np.array_equal(tg, tw) and ng == nw, "sweep %d" % i
+    after = cbind.MT19937(MT_SEED)
+    after.raw(V * (3 + 5 + 3))
+    assert np.array_equal(ctx.debug_mt_fill(5), after.raw(5)) and ctx.counters() == (CTR_SEED, 3)
+
+
 def test_error_codes():
     counts, _, _ = synth_counts(20, 3, 2, seed=1)
     c = _lib.Context(0)
