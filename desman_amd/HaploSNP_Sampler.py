@@ -17,6 +17,7 @@ import numpy as np
 
 from . import _lib
 from . import fixed_tau as _fixed_tau
+from . import diagnose as _diagnose
 from . import relabel as _relabel
 from . import sampletau as _sampletau
 
@@ -56,6 +57,7 @@ class HaploSNP_Sampler:
         self._ctx.set_priors(alpha_constant, delta_constant, epsilon)
         self._tau_sum = None
         self._relabel = None
+        self._diag = None
         self.relabel_ref = None         # the reference relabelling() matches the stored iterations to ([V,G] digits); None = tau_star
         self._have_trace = False
         self._keyed = False
@@ -229,6 +231,7 @@ class HaploSNP_Sampler:
             logging.info('Gibbs Iter %d, no. changed = %d, %s = %f' % (it, tr["nchange"][it], prefix, tr["lp"][it]))
         self._tau_sum = None
         self._relabel = None
+        self._diag = None
         self._have_trace = True
         self.updateTauIndices()
 
@@ -368,6 +371,7 @@ class HaploSNP_Sampler:
         self._have_trace = False
         self._tau_sum = None
         self._relabel = None
+        self._diag = None
         self.updateTauIndices()
 
     # ---- posterior summaries of the last update() (HaploSNP_Sampler.py:463-483,834-839)
@@ -441,6 +445,52 @@ class HaploSNP_Sampler:
         """per haplotype the mean and max over iterations of the fraction of positions that differ from the reference haplotype after
         relabelling, and the number of iterations in which its label was moved (relabel.haplotype_stability)"""
         return _relabel.haplotype_stability(self._trace_ctx(), self.relabelling())
+
+    # ---- convergence diagnostics of the last update() from the resident trace (desman_amd/diagnose.py, DESIGN.md sec. 8f)
+    def _diag_perm(self):
+        """the relabelling the diagnostics are made under: relabelling()['perm'] when relabel_ref is set or a relabelling has been
+        computed, else None (the labels as stored)"""
+        return self.relabelling()["perm"] if self.relabel_ref is not None or self._relabel is not None else None
+
+    def _diagnosed(self, what, batch_len, make):
+        """``make(L, perm)`` kept per (what, L, relabelling) until the next update, as relabelling() is"""
+        L = _diagnose.default_batch_len(self.max_iter) if batch_len is None else int(batch_len)
+        perm = self._diag_perm()
+        key = (what, L)
+        if self._diag is None or self._diag[0] is not perm:
+            self._diag = (perm, {})
+        if key not in self._diag[1]:
+            self._diag[1][key] = make(L, perm)
+        return self._diag[1][key]
+
+    def _tau_diag(self, batch_len):
+        def make(L, perm):
+            stats = self._trace_ctx().trace_batch_stats(L, perm=perm)
+            return _diagnose.tau_diagnostics(stats), stats["flips"]
+        return self._diagnosed("tau", batch_len, make)
+
+    def tauMCSE(self, batch_len=None):
+        """[V, G, 4]: the Monte Carlo standard error of tauMean() (of tauMeanRelabelled() under a relabelling) by batch means over the
+        last N = B L stored iterations, L = batch_len (default floor(sqrt(max_iter)))"""
+        return self._tau_diag(batch_len)[0]["mcse"]
+
+    def tauDiagnostics(self, batch_len=None):
+        """per (position, haplotype): ess_min over the bases with 0 < p < 1, rhat_max (split R-hat) over the bases, flips (iterations
+        at which the base changed), base (the most frequent one) and its p (diagnose.cell_summary)"""
+        d, flips = self._tau_diag(batch_len)
+        return _diagnose.cell_summary(d, flips)
+
+    def scalarDiagnostics(self, batch_len=None):
+        """mean, sd, mcse, ess, split_rhat of lp, ll and every gamma[s][g] (gamma under the relabelling in force), in that order:
+        dict of names (lp, ll, gamma_<s>_<g>) and one array per column"""
+        def make(L, perm):
+            n = self.max_iter
+            g = _diagnose.relabel_gamma(self.gamma_store[:n], perm)
+            series = np.concatenate([self.lp_store[:n, None], self.ll_store[:n, None], g.reshape(n, -1)], axis=1)
+            d = _diagnose.scalar_diagnostics(series, L)
+            d["names"] = ["lp", "ll"] + ["gamma_%d_%d" % (s, h) for s in range(g.shape[1]) for h in range(g.shape[2])]
+            return d
+        return self._diagnosed("scalars", batch_len, make)
 
     @property
     def tau_store(self):

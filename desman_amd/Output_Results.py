@@ -209,6 +209,39 @@ class Output_Results:
         frame.to_csv(self._path("Haplotype_stability.csv"), index=False)
         logging.info("Haplotype_stability.csv written")
 
+    # ---- `desman --diagnose`: convergence diagnostics of the stored iterations (desman_amd/diagnose.py)
+    def output_Tau_MCSE(self, mcse):
+        """Tau_MCSE.csv: the layout of Tau_Mean.csv, every cell the Monte Carlo standard error of that file's cell"""
+        self._haplotype_table("Tau_MCSE.csv", np.reshape(mcse, (self.haplo_SNP.V, self.haplo_SNP.G, 4)),
+                              self.filtered_contig_names, self.filtered_position)
+        logging.info("Tau_MCSE.csv written")
+
+    def output_Tau_diag(self, cells):
+        """Tau_diag.csv: Contig, Position, then per haplotype g the columns ess_min_g, rhat_max_g, flips_g (HaploSNP_Sampler.tauDiagnostics),
+        and one log line with the share of (position, haplotype) cells below diagnose.ESS_LOW or above diagnose.RHAT_HIGH"""
+        from . import diagnose
+        G = cells["ess_min"].shape[1]
+        cols = {"Position": self.filtered_position}
+        for g in range(G):
+            cols["ess_min_%d" % g] = cells["ess_min"][:, g]
+            cols["rhat_max_%d" % g] = cells["rhat_max"][:, g]
+            cols["flips_%d" % g] = cells["flips"][:, g]
+        frame = pd.DataFrame(cols, index=self.filtered_contig_names)
+        frame.index.name = "Contig"
+        frame.to_csv(self._path("Tau_diag.csv"))
+        logging.info("Tau_diag.csv written: %.2f %% of %d (position, haplotype) cells have ess_min < %g or rhat_max > %g"
+                     % (100.0 * diagnose.flagged_share(cells), cells["ess_min"].size, diagnose.ESS_LOW, diagnose.RHAT_HIGH))
+
+    def output_Diag_scalars(self, diag):
+        """Diag_scalars.csv: one row per scalar -- lp, ll, gamma_<sample>_<g> -- with mean, sd, mcse, ess, split_rhat"""
+        names, samples = list(diag["names"]), self._kept_sample_names()
+        G = (len(names) - 2) // max(len(samples), 1)
+        names[2:] = ["gamma_%s_%d" % (s, g) for s in samples for g in range(G)]
+        frame = pd.DataFrame({k: diag[k] for k in ("mean", "sd", "mcse", "ess", "split_rhat")}, index=names)
+        frame.index.name = "scalar"
+        frame.to_csv(self._path("Diag_scalars.csv"))
+        logging.info("Diag_scalars.csv written")
+
     def output_Selected_Variants(self):
         """the selected rows of the input table.  Every chain of a G-sweep writes the same file (the -r selection is drawn from
         a fixed seed, bin/desman:85-86): serialising 50 000 x 385 integers takes longer than the chain's GPU work, so within one

@@ -112,6 +112,8 @@ SIGNATURES = {
     "dsm_ctx_trace_snd": (_i, [_vp, _i, _vp, _i, _i, _i, _vp]),
     "dsm_ctx_get_tau_sum_perm": (_i, [_vp, _vp, _i, _i, _vp]),
     "dsm_ctx_debug_set_trace": (_i, [_vp, _vp, _i]),
+    "dsm_ctx_trace_batch_stats": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "dsm_diag_debug_set_parts": (_i, [_i]),
     "dsm_nmft_set": (_i, [_vp, _f64p, _f64p, _i]),
     "dsm_nmft_get": (_i, [_vp, _vp, _vp]),
     "dsm_nmft_factorize": (_i, [_vp, _i, _d, _i, C.POINTER(_i), _vp]),
@@ -270,6 +272,12 @@ def assign_tau(counts, gamma, eta, seed=None, device=0):
 def assign_debug_set_chunk(positions=0):
     """test hook: positions per launch of assign_tau / Context.assign_tau (0 = the default bound); results do not depend on it"""
     check(load().dsm_assign_debug_set_chunk(int(positions)))
+
+
+def diag_debug_set_parts(parts=0):
+    """test hook: the parts Context.trace_batch_stats splits its batches into across workgroups (0 = the library's own choice);
+    results do not depend on it"""
+    check(load().dsm_diag_debug_set_parts(int(parts)))
 
 
 FIT_MAX_ITER, FIT_TOL = 20000, 1.0e-9     # defaults of fit_gamma: plain EM is slow near the boundary (DESIGN.md sec. 8b)
@@ -783,6 +791,27 @@ class Context:
             raise ValueError("get_tau_sum_perm: perm must be [n_it, G=%d] labels 0..G-1" % self.G)
         out = np.zeros((self.V, self.G, 4), dtype=np.int64)
         check(self.lib.dsm_ctx_get_tau_sum_perm(self._h, _ptr(p), int(it0), p.shape[0], _ptr(out)))
+        return out
+
+    def trace_batch_stats(self, batch_len, perm=None, it0=0, n_it=None, want=("sum", "first", "bsq", "flips")):
+        """Batch sums of the tau trace for convergence diagnostics (include/desman_hip.h: dsm_ctx_trace_batch_stats;
+        desman_amd/diagnose.py): with L = batch_len, B = 2 (n_it // (2 L)) and N = B L, over the LAST N of the iterations
+        it0 .. it0 + n_it - 1 under the labels of ``perm`` ([n_it, G], rows counted from it0; None = identity) a dict of
+        sum, first, bsq [V, G, 4] int64 and flips [V, G] int32 (those named in ``want``; the others are not fetched), B, N and L"""
+        n_it = self.n_trace - int(it0) if n_it is None else int(n_it)
+        L = int(batch_len)
+        p = None
+        if perm is not None:
+            p = np.ascontiguousarray(perm, dtype=np.uint8)
+            if p.ndim != 2 or p.shape != (max(n_it, 0), self.G) or not np.array_equal(p, np.asarray(perm)):
+                raise ValueError("trace_batch_stats: perm must be [n_it=%d, G=%d] labels 0..G-1" % (n_it, self.G))
+        out = {k: np.zeros((self.V, self.G, 4), dtype=np.int64) for k in ("sum", "first", "bsq") if k in want}
+        if "flips" in want:
+            out["flips"] = np.zeros((self.V, self.G), dtype=np.int32)
+        check(self.lib.dsm_ctx_trace_batch_stats(self._h, _ptr(p), int(it0), n_it, L, _ptr(out.get("sum")), _ptr(out.get("first")),
+                                                 _ptr(out.get("bsq")), _ptr(out.get("flips"))))
+        B = 2 * (n_it // (2 * L))
+        out.update(B=B, N=B * L, L=L)
         return out
 
     def debug_set_trace(self, tau_digits):

@@ -57,6 +57,12 @@ def build_parser():
                          "before the chain starts, but a chain that merges identical haplotypes after burn-in ends up with fewer than "
                          "-g, can no longer follow the file and stops with that message after the run: give the -g the other run kept "
                          "(extension)")
+    ap.add_argument('--diagnose', nargs='?', const=True, default=None, type=int, metavar='L',
+                    help="also write convergence diagnostics of the stored iterations: Tau_MCSE.csv (Monte Carlo standard error of "
+                         "Tau_Mean.csv by batch means), Tau_diag.csv (per position and haplotype: smallest effective sample size, "
+                         "largest split R-hat, number of base changes) and Diag_scalars.csv (lp, ll, every gamma entry); L = batch "
+                         "length (default floor(sqrt(iterations))), at least 2 L iterations are needed; with --relabel / --relabel-ref "
+                         "the diagnostics are those of the relabelled trace (extension)")
     return ap
 
 
@@ -178,6 +184,29 @@ def _report_relabel(report, chain, ref):
     report.output_Haplotype_stability(chain.haplotypeStability())
 
 
+def _diagnose_batch_len(opts):
+    """--diagnose: the batch length L, checked against the iterations a chain will store; the run stops here, before any chain, if
+    there are fewer than 2 L of them.  None without the option."""
+    if opts.diagnose is None:
+        return None
+    from . import diagnose
+    n = 250 if opts.no_iter is None else opts.no_iter            # the sampler's own default
+    L = diagnose.default_batch_len(n) if opts.diagnose is True else opts.diagnose
+    if L < 1:
+        sys.exit("desman: --diagnose: the batch length must be at least 1; got %d" % L)
+    if n < 2 * L:
+        sys.exit("desman: --diagnose: %d stored iterations (-i) are fewer than two batches of %d" % (n, L))
+    return L
+
+
+def _report_diagnose(report, chain, L):
+    """--diagnose: the convergence diagnostics of the fitted chain, next to the usual files (which do not change); under the
+    relabelling of --relabel / --relabel-ref where one was made"""
+    report.output_Tau_MCSE(chain.tauMCSE(L))
+    report.output_Tau_diag(chain.tauDiagnostics(L))
+    report.output_Diag_scalars(chain.scalarDiagnostics(L))
+
+
 def _assign_rest(opts, report, table, flt, chain):
     """-r: haplotypes of the positions left out of the fit, with tau-only sweeps driven by the fitted
     chain's gamma / eta traces (bin/desman:181-206)."""
@@ -249,6 +278,7 @@ def main(argv=None):
     if opts.genomes < 0:
         logging.error('the haplotype number must be positive, got %d' % opts.genomes)
         sys.exit(-1)
+    diag_len = _diagnose_batch_len(opts)
     report = Output_Results(opts.output_dir)
     table, flt, subsample = _load(opts, report)
     ref = _relabel_reference(opts, table, flt)
@@ -256,6 +286,8 @@ def main(argv=None):
     _report(report, table, flt, chain, opts.genomes)
     if opts.relabel or ref is not None:
         _report_relabel(report, chain, ref)
+    if diag_len is not None:
+        _report_diagnose(report, chain, diag_len)
     if subsample is not None:
         _assign_rest(opts, report, table, flt, chain)
     sampletau.freeRNG()
@@ -276,13 +308,14 @@ def main_replicates(argv_list, on_chain=None):
         opts = build_parser().parse_args(argv)
         if opts.assign_file is not None:
             sys.exit('desman: -a/--assign_file is not supported (dead in the reference: bin/desman:213-214)')
+        diag_len = _diagnose_batch_len(opts)
         report = Output_Results(opts.output_dir)
         table, flt, subsample = _load(opts, report)
         logging.info('sampler seed %d', opts.random_seed)
         rng = RandomState(opts.random_seed)
         nmft = Init_NMFT(flt.snps_filter, opts.genomes, rng, device=opts.device)
         runs.append(dict(opts=opts, report=report, table=table, flt=flt, subsample=subsample, rng=rng, nmft=nmft,
-                         ref=_relabel_reference(opts, table, flt)))
+                         ref=_relabel_reference(opts, table, flt), diag_len=diag_len))
     # the NMF starts: together where the batched kernels apply (one shape, S <= 128, G <= 16), else one by one
     nm = [r["nmft"] for r in runs]
     done = False
@@ -338,6 +371,8 @@ def main_replicates(argv_list, on_chain=None):
         _report(r["report"], r["table"], r["flt"], r["chain"], r["opts"].genomes)
         if r["opts"].relabel or r["ref"] is not None:
             _report_relabel(r["report"], r["chain"], r["ref"])
+        if r["diag_len"] is not None:
+            _report_diagnose(r["report"], r["chain"], r["diag_len"])
     # -r: the positions left out of the fit -- batched where the replicates still agree in shape
     rest_runs = [r for r in runs if r["subsample"] is not None]
     idx = {id(r): k for k, r in enumerate(runs)}

@@ -1514,6 +1514,22 @@ static int trace_range(dsm_ctx *c, const char *who, int it0, int n_it)
     return DSM_OK;
 }
 
+// inv[t][perm[t][g]] = g for n_it rows of perm (null: identity rows); DSM_ERR_ARG on a row that is no permutation of 0..G-1
+static int perm_inverse(const char *who, const uint8_t *perm, int n_it, int G, std::vector<uint8_t> &inv)
+{
+    inv.resize((size_t)n_it * G);
+    for (int t = 0; t < n_it; ++t) {
+        uint32_t seen = 0;
+        for (int g = 0; g < G; ++g) {
+            const int p = perm ? perm[(size_t)t * G + g] : g;
+            if (p >= G || (seen >> p & 1u)) { dsm_set_error("%s: row %d of perm is not a permutation of 0..%d", who, t, G - 1); return DSM_ERR_ARG; }
+            seen |= 1u << p;
+            inv[(size_t)t * G + p] = (uint8_t)g;
+        }
+    }
+    return DSM_OK;
+}
+
 extern "C" int dsm_ctx_trace_snd(dsm_ctx *c, int mode, const int64_t *ref_tau, int Gr, int it0, int n_it, int32_t *snd)
 {
     TRY(trace_range(c, "trace_snd", it0, n_it));
@@ -1559,16 +1575,8 @@ extern "C" int dsm_ctx_get_tau_sum_perm(dsm_ctx *c, const uint8_t *perm, int it0
     TRY(trace_range(c, "get_tau_sum_perm", it0, n_it));
     if (!tau_sum || (n_it > 0 && !perm)) { dsm_set_error("get_tau_sum_perm: null pointer"); return DSM_ERR_ARG; }
     const int G = c->G;
-    std::vector<uint8_t> inv((size_t)n_it * G);
-    for (int t = 0; t < n_it; ++t) {
-        uint32_t seen = 0;
-        for (int g = 0; g < G; ++g) {
-            const int p = perm[(size_t)t * G + g];
-            if (p >= G || (seen >> p & 1u)) { dsm_set_error("get_tau_sum_perm: row %d of perm is not a permutation of 0..%d", t, G - 1); return DSM_ERR_ARG; }
-            seen |= 1u << p;
-            inv[(size_t)t * G + p] = (uint8_t)g;
-        }
-    }
+    std::vector<uint8_t> inv;
+    TRY(perm_inverse("get_tau_sum_perm", perm, n_it, G, inv));
     BIND(c);
     const size_t V = (size_t)c->V, nt = V * G * 4;
     Scratch<int64_t> d_out;
@@ -1578,6 +1586,40 @@ extern "C" int dsm_ctx_get_tau_sum_perm(dsm_ctx *c, const uint8_t *perm, int it0
     if (n_it > 0) HIP_TRY(hipMemcpyAsync(d_inv, inv.data(), inv.size(), hipMemcpyHostToDevice, c->stream));
     TRY(k_tau_sum_perm(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it0 + 1) * V), c->tau_fixed_trace ? 0 : V, d_inv, n_it, d_out));
     HIP_TRY(hipMemcpyAsync(tau_sum, d_out, nt * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DSM_OK;
+}
+
+// batch sums of the trace for convergence diagnostics (kernels_diag.hip): the last B L of the n_it iterations
+extern "C" int dsm_ctx_trace_batch_stats(dsm_ctx *c, const uint8_t *perm, int it0, int n_it, int batch_len, int64_t *sum, int64_t *first,
+                                         int64_t *bsq, int32_t *flips)
+{
+    TRY(trace_range(c, "trace_batch_stats", it0, n_it));
+    if (batch_len < 1) { dsm_set_error("trace_batch_stats: batch_len=%d, at least 1 is needed", batch_len); return DSM_ERR_ARG; }
+    if (n_it > 0 && n_it / 2 < batch_len) {
+        dsm_set_error("trace_batch_stats: %d iterations are fewer than two batches of %d", n_it, batch_len);
+        return DSM_ERR_ARG;
+    }
+    const int G = c->G, L = batch_len, B = n_it > 0 ? 2 * (n_it / (2 * L)) : 0, skip = n_it - B * L;       // (n_it > 0: 2 L <= n_it)
+    std::vector<uint8_t> inv;
+    TRY(perm_inverse("trace_batch_stats", perm, n_it, G, inv));
+    BIND(c);
+    const size_t V = (size_t)c->V, nt = V * G * 4, used = (size_t)B * L * G;
+    Scratch<int64_t> d_sum, d_first, d_bsq;
+    Scratch<int32_t> d_flips;
+    Scratch<uint8_t> d_inv;
+    TRY(d_sum.alloc(nt));
+    TRY(d_first.alloc(nt));
+    TRY(d_bsq.alloc(nt));
+    TRY(d_flips.alloc(V * G));
+    TRY(d_inv.alloc(used));
+    if (used > 0) HIP_TRY(hipMemcpyAsync(d_inv, inv.data() + (size_t)skip * G, used, hipMemcpyHostToDevice, c->stream));
+    TRY(k_trace_batch_stats(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it0 + 1 + skip) * V), c->tau_fixed_trace ? 0 : V, d_inv, B,
+                            L, d_sum, d_first, d_bsq, d_flips));
+    if (sum) HIP_TRY(hipMemcpyAsync(sum, d_sum, nt * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    if (first) HIP_TRY(hipMemcpyAsync(first, d_first, nt * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    if (bsq) HIP_TRY(hipMemcpyAsync(bsq, d_bsq, nt * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    if (flips) HIP_TRY(hipMemcpyAsync(flips, d_flips, V * G * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;
 }

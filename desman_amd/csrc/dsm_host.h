@@ -260,6 +260,10 @@ int k_held_sweep(dsm_ctx *c, int n_held, const double *gamma, const double *eta,
 int k_trace_snd(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const uint64_t *ref, int Gr, int n_it, int *d_out);   // ref null: each iteration against itself
 int k_tau_sum_perm(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const uint8_t *d_inv, int n, int64_t *d_out);      // inv[t][perm[t][g]] = g
 
+// ---- launcher (kernels_diag.hip): batch sums of the tau trace; B batches of L iterations, B even, d_inv [B * L][G], trace_stride as above
+int k_trace_batch_stats(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const uint8_t *d_inv, int B, int L, int64_t *d_sum,
+                        int64_t *d_first, int64_t *d_bsq, int32_t *d_flips);
+
 // ---- launchers (kernels_nmft.hip)
 int k_nmft_freq(dsm_ctx *c);
 int k_nmft_clamp(dsm_ctx *c);

@@ -270,6 +270,29 @@ int dsm_ctx_get_tau_sum_perm(dsm_ctx *ctx, const uint8_t *perm /*[n_it][G]*/, in
  * ll / lp / nchange / gamma / eta traces keep what they held (zeros where the call had to allocate them).                       */
 int dsm_ctx_debug_set_trace(dsm_ctx *ctx, const int64_t *tau_digits /*[n][V][G]*/, int n);
 
+/* Batch sums of the resident tau trace for convergence diagnostics (batch-means MCSE and ESS, split R-hat; DESIGN.md sec. 8f;
+ * desman_amd/diagnose.py): one more reduction of the kind above, exact integers, the same bits for any grid.  With L = batch_len,
+ * B = 2 * floor(n_it / (2 L)) batches (always even: two halves of equal length) and N = B L, only the LAST N of the iterations
+ * it0 .. it0 + n_it - 1 are used; the first n_it - N are skipped.  Iteration numbering is that of dsm_ctx_get_tau_at; row t of perm
+ * (uint8 [n_it][G], counted from it0 -- the rows of skipped iterations are passed and validated too; NULL = identity rows) renames
+ * iteration t's labels as in dsm_ctx_get_tau_sum_perm.  Write x_t[v][l][a] = [the haplotype carrying label l in iteration t has base
+ * a at v]:
+ *     sum   [V][G][4] int64   sum of x_t over the N used iterations (= dsm_ctx_get_tau_sum_perm over exactly those)
+ *     first [V][G][4] int64   the same over the first B / 2 batches
+ *     bsq   [V][G][4] int64   sum over the batches b of (sum_{t in b} x_t)^2
+ *     flips [V][G]    int32   the used iterations t, not counting the first, at which label l's base at v differs from its base at
+ *                             t - 1, each iteration read under its own perm row
+ * Any output pointer may be NULL.  DSM_ERR_STATE when no update has run; DSM_ERR_ARG for a range outside the trace, batch_len < 1,
+ * 0 < n_it < 2 batch_len, a perm row that is no permutation.  n_it = 0 succeeds and writes zeros.  After
+ * dsm_ctx_gibbs_update_fixed_tau every iteration is the held tau.  The chain is only read, as by the calls above.  Limits as there:
+ * one context, 1 <= G <= DSM_MAX_G.                                                                                              */
+int dsm_ctx_trace_batch_stats(dsm_ctx *ctx, const uint8_t *perm /*[n_it][G] or NULL*/, int it0, int n_it, int batch_len,
+                              int64_t *sum /*[V][G][4]*/, int64_t *first /*[V][G][4]*/, int64_t *bsq /*[V][G][4]*/,
+                              int32_t *flips /*[V][G]*/);
+/* test hook: the number of parts the call above splits its batches into across workgroups (0 = the library's own choice, the
+ * default; more parts than batches: one batch each) */
+int dsm_diag_debug_set_parts(int parts);
+
 /* A8-A12: Init_NMFT (desman/Init_NMFT.py).  F is derived from the resident
  * counts (:49-60).  tau [4V][G] row v + a*V, gamma [G][S] as in the reference.
  * Every shape up to S = DSM_MAX_S, G = DSM_MAX_G has a kernel (tests/test_gpu_nmft_forms.py
