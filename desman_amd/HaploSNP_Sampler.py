@@ -17,6 +17,7 @@ import numpy as np
 
 from . import _lib
 from . import fixed_tau as _fixed_tau
+from . import check as _check
 from . import diagnose as _diagnose
 from . import relabel as _relabel
 from . import sampletau as _sampletau
@@ -58,6 +59,7 @@ class HaploSNP_Sampler:
         self._tau_sum = None
         self._relabel = None
         self._diag = None
+        self._fit = None
         self.relabel_ref = None         # the reference relabelling() matches the stored iterations to ([V,G] digits); None = tau_star
         self._have_trace = False
         self._keyed = False
@@ -232,6 +234,7 @@ class HaploSNP_Sampler:
         self._tau_sum = None
         self._relabel = None
         self._diag = None
+        self._fit = None
         self._have_trace = True
         self.updateTauIndices()
 
@@ -372,6 +375,7 @@ class HaploSNP_Sampler:
         self._tau_sum = None
         self._relabel = None
         self._diag = None
+        self._fit = None
         self.updateTauIndices()
 
     # ---- posterior summaries of the last update() (HaploSNP_Sampler.py:463-483,834-839)
@@ -491,6 +495,18 @@ class HaploSNP_Sampler:
             d["names"] = ["lp", "ll"] + ["gamma_%d_%d" % (s, h) for s in range(g.shape[1]) for h in range(g.shape[2])]
             return d
         return self._diagnosed("scalars", batch_len, make)
+
+    # ---- posterior predictive fit of the last update() from the resident traces (desman_amd/check.py)
+    def fitCheck(self, cells=False):
+        """(per-sample table, per-position table) -- with ``cells`` also the [V, S] posterior mean of Pearson's X per cell -- of the
+        stored iterations: each table a dict of cells, X2, expected, variance, deviance and z (check.fit_scores).  Invariant to the
+        haplotype labels, so no relabelling applies; kept until the next update."""
+        if self._fit is None or (cells and "cell" not in self._fit):
+            want = ("sample", "position", "cell") if cells else ("sample", "position")
+            sums = self._trace_ctx().trace_fit_stats(0, self.max_iter, want=want)
+            self._fit = _check.fit_scores(sums, self.max_iter, self.variants)
+        f = self._fit
+        return (f["sample"], f["position"], f["cell"]) if cells else (f["sample"], f["position"])
 
     @property
     def tau_store(self):

@@ -242,6 +242,32 @@ class Output_Results:
         frame.to_csv(self._path("Diag_scalars.csv"))
         logging.info("Diag_scalars.csv written")
 
+    # ---- `desman --check`: posterior predictive fit per sample and per position (desman_amd/check.py)
+    _FIT_COLUMNS = (("cells", "cells"), ("X2", "X2"), ("expected", "expected"), ("z", "z"), ("deviance", "deviance"))
+
+    def output_Fit(self, samples, positions):
+        """Fit_samples.csv: sample, cells, X2, expected, z, deviance; Fit_positions.csv: Contig, Position, then the same columns (keyed
+        as Tau_Mean.csv keys its rows); and one log line with the number of samples and positions whose z exceeds check.Z_HIGH"""
+        from . import check
+        frame = pd.DataFrame({col: samples[key] for col, key in self._FIT_COLUMNS}, index=self._kept_sample_names())
+        frame.index.name = "sample"
+        frame.to_csv(self._path("Fit_samples.csv"))
+        cols = {"Position": self.filtered_position}
+        cols.update({col: positions[key] for col, key in self._FIT_COLUMNS})
+        frame = pd.DataFrame(cols, index=self.filtered_contig_names)
+        frame.index.name = "Contig"
+        frame.to_csv(self._path("Fit_positions.csv"))
+        logging.info("Fit_samples.csv / Fit_positions.csv written: %d of %d samples and %d of %d positions have z > %g"
+                     % (check.flagged(samples), len(samples["z"]), check.flagged(positions), len(positions["z"]), check.Z_HIGH))
+
+    def output_Fit_cells(self, cell):
+        """Fit_cells.csv: V x S, the posterior mean of Pearson's X per cell; rows keyed as Tau_Mean.csv's, one column per sample"""
+        frame = pd.DataFrame(np.asarray(cell), index=self.filtered_contig_names, columns=self._kept_sample_names())
+        frame.insert(0, "Position", self.filtered_position)
+        frame.index.name = "Contig"
+        frame.to_csv(self._path("Fit_cells.csv"))
+        logging.info("Fit_cells.csv written")
+
     def output_Selected_Variants(self):
         """the selected rows of the input table.  Every chain of a G-sweep writes the same file (the -r selection is drawn from
         a fixed seed, bin/desman:85-86): serialising 50 000 x 385 integers takes longer than the chain's GPU work, so within one

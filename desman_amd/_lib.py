@@ -114,6 +114,10 @@ SIGNATURES = {
     "dsm_ctx_debug_set_trace": (_i, [_vp, _vp, _i]),
     "dsm_ctx_trace_batch_stats": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "dsm_diag_debug_set_parts": (_i, [_i]),
+    "dsm_ctx_trace_fit_stats": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "dsm_fit_debug_set_parts": (_i, [_i]),
+    "dsm_fit_debug_path": (_i, [_vp, _i, C.POINTER(_i)]),
+    "dsm_ctx_debug_set_param_trace": (_i, [_vp, _vp, _vp, _i]),
     "dsm_nmft_set": (_i, [_vp, _f64p, _f64p, _i]),
     "dsm_nmft_get": (_i, [_vp, _vp, _vp]),
     "dsm_nmft_factorize": (_i, [_vp, _i, _d, _i, C.POINTER(_i), _vp]),
@@ -278,6 +282,12 @@ def diag_debug_set_parts(parts=0):
     """test hook: the parts Context.trace_batch_stats splits its batches into across workgroups (0 = the library's own choice);
     results do not depend on it"""
     check(load().dsm_diag_debug_set_parts(int(parts)))
+
+
+def fit_debug_set_parts(parts=0):
+    """test hook: the parts Context.trace_fit_stats splits its iterations into across workgroups (0 = the library's own choice); the
+    results agree to rounding between part counts and are the same bits for one part count"""
+    check(load().dsm_fit_debug_set_parts(int(parts)))
 
 
 FIT_MAX_ITER, FIT_TOL = 20000, 1.0e-9     # defaults of fit_gamma: plain EM is slow near the boundary (DESIGN.md sec. 8b)
@@ -813,6 +823,38 @@ class Context:
         B = 2 * (n_it // (2 * L))
         out.update(B=B, N=B * L, L=L)
         return out
+
+    def trace_fit_stats(self, it0=0, n_it=None, want=("sample", "position", "cell")):
+        """Posterior predictive fit sums over the stored iterations it0 .. it0 + n_it - 1 (include/desman_hip.h:
+        dsm_ctx_trace_fit_stats; desman_amd/check.py): a dict of sample [S, 4] and position [V, 4] -- the sums of (X, D, E, W) over the
+        iterations and the other index -- and cell [V, S], the sum of X over the iterations; only those named in ``want`` are
+        allocated and fetched.  n_it is in the dict."""
+        n_it = self.n_trace - int(it0) if n_it is None else int(n_it)
+        shapes = dict(sample=(self.S, 4), position=(self.V, 4), cell=(self.V, self.S))
+        bad = [k for k in want if k not in shapes]
+        if bad:
+            raise ValueError("trace_fit_stats: unknown output %r (sample, position, cell)" % bad[0])
+        out = {k: np.zeros(shapes[k]) for k in shapes if k in want}
+        check(self.lib.dsm_ctx_trace_fit_stats(self._h, int(it0), n_it, _ptr(out.get("sample")), _ptr(out.get("position")),
+                                               _ptr(out.get("cell"))))
+        out["n_it"] = n_it
+        return out
+
+    def fit_debug_path(self, n_it=None):
+        """test hook: what trace_fit_stats over n_it iterations (default: the whole trace) would launch: dict of nsl (the kernel's
+        instantiation: sample slots per lane), lpv (lanes per position), gc (haplotypes per staged chunk of gamma), tiles and parts"""
+        out = (_i * 5)()
+        check(self.lib.dsm_fit_debug_path(self._h, int(self.n_trace if n_it is None else n_it), out))
+        return dict(zip(("nsl", "lpv", "gc", "tiles", "parts"), (int(x) for x in out)))
+
+    def debug_set_param_trace(self, gamma, eta):
+        """test hook: installs gamma [n, S, G] and eta [n, 4, 4] as the first n rows of the gamma and eta traces (after
+        debug_set_trace or an update)"""
+        g = np.ascontiguousarray(gamma, dtype=np.float64)
+        e = np.ascontiguousarray(eta, dtype=np.float64)
+        if g.ndim != 3 or g.shape[1:] != (self.S, self.G) or e.shape != (g.shape[0], 4, 4):
+            raise ValueError("debug_set_param_trace: gamma must be [n, S=%d, G=%d] and eta [n, 4, 4]" % (self.S, self.G))
+        check(self.lib.dsm_ctx_debug_set_param_trace(self._h, _ptr(g), _ptr(e), g.shape[0]))
 
     def debug_set_trace(self, tau_digits):
         """test hook: installs tau_digits [n, V, G] (digits 0..3) as the tau trace of n iterations; slot 0 = the resident state"""

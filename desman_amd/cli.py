@@ -63,6 +63,13 @@ def build_parser():
                          "largest split R-hat, number of base changes) and Diag_scalars.csv (lp, ll, every gamma entry); L = batch "
                          "length (default floor(sqrt(iterations))), at least 2 L iterations are needed; with --relabel / --relabel-ref "
                          "the diagnostics are those of the relabelled trace (extension)")
+    ap.add_argument('--check', action='store_true',
+                    help="also write the posterior predictive fit of the stored iterations: Fit_samples.csv and Fit_positions.csv "
+                         "(per sample / per position: non-empty cells, posterior mean of Pearson's X2, its expectation under the "
+                         "model, the standardised discrepancy z and the deviance); a large z marks a sample or a position the "
+                         "haplotypes do not explain; z is a conservative score, not a p-value (extension)")
+    ap.add_argument('--check-cells', dest='check_cells', action='store_true',
+                    help="with --check: also write Fit_cells.csv, positions x samples, the posterior mean X2 of every cell (extension)")
     return ap
 
 
@@ -207,6 +214,23 @@ def _report_diagnose(report, chain, L):
     report.output_Diag_scalars(chain.scalarDiagnostics(L))
 
 
+def _check_options(opts):
+    """--check / --check-cells: refused here, before any chain, where they cannot be served"""
+    if opts.check_cells and not opts.check:
+        sys.exit("desman: --check-cells needs --check")
+    if opts.check and opts.no_iter is not None and opts.no_iter < 1:
+        sys.exit("desman: --check: %d stored iterations (-i): at least 1 is needed" % opts.no_iter)
+
+
+def _report_check(report, chain, cells):
+    """--check: the fit of the chain per sample and per position (--check-cells: per cell too), next to the usual files (which do not
+    change); the statistic does not depend on the haplotype labels, so --relabel changes nothing here"""
+    fit = chain.fitCheck(cells=cells)
+    report.output_Fit(fit[0], fit[1])
+    if cells:
+        report.output_Fit_cells(fit[2])
+
+
 def _assign_rest(opts, report, table, flt, chain):
     """-r: haplotypes of the positions left out of the fit, with tau-only sweeps driven by the fitted
     chain's gamma / eta traces (bin/desman:181-206)."""
@@ -279,6 +303,7 @@ def main(argv=None):
         logging.error('the haplotype number must be positive, got %d' % opts.genomes)
         sys.exit(-1)
     diag_len = _diagnose_batch_len(opts)
+    _check_options(opts)
     report = Output_Results(opts.output_dir)
     table, flt, subsample = _load(opts, report)
     ref = _relabel_reference(opts, table, flt)
@@ -288,6 +313,8 @@ def main(argv=None):
         _report_relabel(report, chain, ref)
     if diag_len is not None:
         _report_diagnose(report, chain, diag_len)
+    if opts.check:
+        _report_check(report, chain, opts.check_cells)
     if subsample is not None:
         _assign_rest(opts, report, table, flt, chain)
     sampletau.freeRNG()
@@ -309,6 +336,7 @@ def main_replicates(argv_list, on_chain=None):
         if opts.assign_file is not None:
             sys.exit('desman: -a/--assign_file is not supported (dead in the reference: bin/desman:213-214)')
         diag_len = _diagnose_batch_len(opts)
+        _check_options(opts)
         report = Output_Results(opts.output_dir)
         table, flt, subsample = _load(opts, report)
         logging.info('sampler seed %d', opts.random_seed)
@@ -373,6 +401,8 @@ def main_replicates(argv_list, on_chain=None):
             _report_relabel(r["report"], r["chain"], r["ref"])
         if r["diag_len"] is not None:
             _report_diagnose(r["report"], r["chain"], r["diag_len"])
+        if r["opts"].check:
+            _report_check(r["report"], r["chain"], r["opts"].check_cells)
     # -r: the positions left out of the fit -- batched where the replicates still agree in shape
     rest_runs = [r for r in runs if r["subsample"] is not None]
     idx = {id(r): k for k, r in enumerate(runs)}

@@ -1624,6 +1624,70 @@ extern "C" int dsm_ctx_trace_batch_stats(dsm_ctx *c, const uint8_t *perm, int it
     return DSM_OK;
 }
 
+// posterior predictive fit per sample, position and cell over stored iterations (kernels_fit.hip): everything is read
+// where it lies -- the counts, the tau, gamma and eta traces -- and nothing of the chain is written
+extern "C" int dsm_ctx_trace_fit_stats(dsm_ctx *c, int it0, int n_it, double *sample, double *position, double *cell)
+{
+    TRY(trace_range(c, "trace_fit_stats", it0, n_it));
+    const size_t V = (size_t)c->V, S = (size_t)c->S, sg = S * c->G;
+    if (n_it == 0) {
+        if (sample) std::fill(sample, sample + S * 4, 0.0);
+        if (position) std::fill(position, position + V * 4, 0.0);
+        if (cell) std::fill(cell, cell + V * S, 0.0);
+        return DSM_OK;
+    }
+    FitPlan pl;
+    TRY(fit_plan(c, n_it, &pl));
+    BIND(c);
+    Scratch<double> d_sample, d_position, d_cell, samp_part, pos_part, cell_part;
+    TRY(d_sample.alloc(S * 4));
+    TRY(d_position.alloc(V * 4));
+    TRY(samp_part.alloc((size_t)pl.parts * pl.tiles * S * 4));
+    TRY(pos_part.alloc((size_t)pl.parts * V * 4));
+    if (cell) {
+        TRY(d_cell.alloc(V * S));
+        TRY(cell_part.alloc((size_t)pl.parts * V * S));
+    }
+    TRY(k_trace_fit_stats(c, pl, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it0 + 1) * V), c->tau_fixed_trace ? 0 : V,
+                          c->gamma_trace + (size_t)it0 * sg, c->eta_trace + (size_t)it0 * 16, n_it, samp_part, pos_part, cell_part, d_sample,
+                          d_position, cell ? d_cell.p : nullptr));
+    if (sample) HIP_TRY(hipMemcpyAsync(sample, d_sample, S * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (position) HIP_TRY(hipMemcpyAsync(position, d_position, V * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (cell) HIP_TRY(hipMemcpyAsync(cell, d_cell, V * S * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DSM_OK;
+}
+
+// test hook: which instantiation of the fit kernel, and which grid, a call over n_it iterations would launch (nothing is launched)
+extern "C" int dsm_fit_debug_path(dsm_ctx *c, int n_it, int out[5])
+{
+    TRY(need(c, true, true));
+    if (!out || n_it < 1) { dsm_set_error("fit_debug_path: bad arguments"); return DSM_ERR_ARG; }
+    FitPlan pl;
+    TRY(fit_plan(c, n_it, &pl));
+    out[0] = pl.nsl; out[1] = pl.lpv; out[2] = pl.gc; out[3] = pl.tiles; out[4] = pl.parts;
+    return DSM_OK;
+}
+
+// test hook: the first n rows of the gamma and eta traces (the companion of dsm_ctx_debug_set_trace, called after it)
+extern "C" int dsm_ctx_debug_set_param_trace(dsm_ctx *c, const double *gamma, const double *eta, int n)
+{
+    TRY(need(c, true, true));
+    const int have = c->tau_trace ? c->n_trace : 0;
+    if (n < 0 || n > have || (n > 0 && (!gamma || !eta))) {
+        dsm_set_error("debug_set_param_trace: n=%d outside the trace of %d, or a null pointer", n, have);
+        return DSM_ERR_ARG;
+    }
+    BIND(c);
+    const size_t sg = (size_t)c->S * c->G;
+    if (n > 0) {
+        HIP_TRY(hipMemcpyAsync(c->gamma_trace, gamma, (size_t)n * sg * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(c->eta_trace, eta, (size_t)n * 16 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DSM_OK;
+}
+
 // test hook: a synthetic trace.  Slot 0 = the resident state, slots 1 .. n = the given digits.  A context on which no update has run has
 // no MAP record yet: it gets the resident state as one (slot 0, lp = -inf), so that DSM_SND_STAR has a reference; an existing record stays.
 extern "C" int dsm_ctx_debug_set_trace(dsm_ctx *c, const int64_t *tau_digits, int n)

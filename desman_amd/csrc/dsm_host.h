@@ -264,6 +264,13 @@ int k_tau_sum_perm(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const
 int k_trace_batch_stats(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const uint8_t *d_inv, int B, int L, int64_t *d_sum,
                         int64_t *d_first, int64_t *d_bsq, int32_t *d_flips);
 
+// ---- launcher (kernels_fit.hip): posterior predictive fit sums over n_it stored iterations; trace_stride as above
+struct FitPlan { int nsl, lpv, gc, tiles, parts; };   // sample slots per lane, lanes per position, haplotypes per staged gamma chunk, workgroups per part, parts
+int fit_plan(const dsm_ctx *c, int n_it, FitPlan *pl);
+int k_trace_fit_stats(dsm_ctx *c, const FitPlan &pl, const uint64_t *trace, size_t trace_stride, const double *gamma, const double *eta,
+                      int n_it, double *d_samp_part, double *d_pos_part, double *d_cell_part, double *d_sample, double *d_position,
+                      double *d_cell);
+
 // ---- launchers (kernels_nmft.hip)
 int k_nmft_freq(dsm_ctx *c);
 int k_nmft_clamp(dsm_ctx *c);

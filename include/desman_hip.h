@@ -293,6 +293,37 @@ int dsm_ctx_trace_batch_stats(dsm_ctx *ctx, const uint8_t *perm /*[n_it][G] or N
  * default; more parts than batches: one batch each) */
 int dsm_diag_debug_set_parts(int parts);
 
+/* Posterior predictive fit of the chain per sample, per position and per cell (desman_amd/check.py): one device pass
+ * over the resident counts and the tau, gamma and eta traces of the iterations it0 .. it0 + n_it - 1 (numbered as by
+ * dsm_ctx_get_tau_at).  For a stored iteration t and a cell (v, s) with counts n_b, N = sum_b n_b > 0 (an empty cell adds nothing
+ * anywhere), p_b = sum_g gamma_t[s][g] eta_t[tau_t[v][g]][b] -- the likelihood's own probabilities -- and k = #{b : p_b > 0}:
+ *     X = sum_{b: p_b > 0} (n_b - N p_b)^2 / (N p_b)       Pearson's discrepancy
+ *     D = 2 sum_{b: n_b > 0} n_b ln(n_b / (N p_b))          the deviance against the saturated model
+ *     E = k - 1                                             the exact mean of X under multinomial(N, p)
+ *     W = 2 (k - 1) + (sum_{b: p_b > 0} 1 / p_b - k^2 - 2 k + 2) / N      its exact variance
+ * A base with p_b = 0 < n_b makes X and D of its cell +inf; one with p_b = 0 = n_b adds 0; nothing is ever NaN.  Outputs, sums over the
+ * iterations (the caller divides by n_it):
+ *     sample   [S][4] double   sum over t and v of (X, D, E, W)
+ *     position [V][4] double   sum over t and s of (X, D, E, W)
+ *     cell     [V][S] double   sum over t of X
+ * Any output pointer may be NULL (cell = NULL also saves its device buffers).  Plain fp64 sums in a fixed order, no floating-point
+ * atomics: two calls with the same split of the iteration range give the same bits; another split moves the last bits.  n_it = 0
+ * succeeds and writes zeros.  DSM_ERR_STATE when no update has run, DSM_ERR_ARG for a range outside the trace.  After
+ * dsm_ctx_gibbs_update_fixed_tau every iteration is the held tau.  The chain, both RNG streams, the traces and the MAP record are only
+ * read.  Limits: one context, 1 <= G <= DSM_MAX_G, S <= DSM_MAX_S.                                                                 */
+int dsm_ctx_trace_fit_stats(dsm_ctx *ctx, int it0, int n_it, double *sample /*[S][4]*/, double *position /*[V][4]*/,
+                            double *cell /*[V][S]*/);
+/* test hook: the number of parts the call above splits its iterations into across workgroups (0 = the library's own choice, the
+ * default; never more parts than iterations) */
+int dsm_fit_debug_set_parts(int parts);
+/* test hook: what a dsm_ctx_trace_fit_stats call over n_it >= 1 iterations would launch on this context's table: out = {sample slots
+ * per lane (the kernel's instantiation: 1, 2, 4 or 8), lanes per position, haplotypes per staged chunk of gamma, workgroups per part,
+ * parts}.  Nothing is launched.  Needs counts and a state.                                                                          */
+int dsm_fit_debug_path(dsm_ctx *ctx, int n_it, int out[5]);
+/* test hook, the companion of dsm_ctx_debug_set_trace: overwrites the first n rows of the gamma and eta traces.  DSM_ERR_ARG when n
+ * exceeds the trace's length (0 before any update or dsm_ctx_debug_set_trace).                                                      */
+int dsm_ctx_debug_set_param_trace(dsm_ctx *ctx, const double *gamma /*[n][S][G]*/, const double *eta /*[n][16]*/, int n);
+
 /* A8-A12: Init_NMFT (desman/Init_NMFT.py).  F is derived from the resident
  * counts (:49-60).  tau [4V][G] row v + a*V, gamma [G][S] as in the reference.
  * Every shape up to S = DSM_MAX_S, G = DSM_MAX_G has a kernel (tests/test_gpu_nmft_forms.py
