@@ -68,6 +68,8 @@ SIGNATURES = {
     "dsm_ctx_sweep_stats": (_i, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _i]),
     "dsm_ctx_set_tau_screen": (_i, [_vp, _i]),
     "dsm_ctx_set_tau_neartie": (_i, [_vp, _i]),
+    "dsm_ctx_set_big_launch": (_i, [_vp, _i]),
+    "dsm_ctx_debug_big_lists": (_i, [_vp, _vp, _vp]),
     "dsm_ctx_set_nmft_fused": (_i, [_vp, _i]),
     "dsm_ctx_set_nmft_persist": (_i, [_vp, _i]),
     "dsm_ctx_tau_launch_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
@@ -611,6 +613,17 @@ class Context:
         """which instantiation of the Gibbs loop's tau sweep runs: -1 = the one with the near-tie screen when the chain holds a haplotype
         that is rare in every sample (decided at the start of each gibbs_update call), 0 = never, 1 = always; same draws either way"""
         check(self.lib.dsm_ctx_set_tau_neartie(self._h, int(mode)))
+
+    def set_big_launch(self, mode=-1):
+        """the launch of stats_big_kernel after stage 1 of the aggregated mu/E pass, where it is a choice (full chain, G < 10, spec 2 / 3):
+        -1 = while stage 1 was last seen handing items over, 0 = never (the Dirichlet launch draws them), 1 = always; same draws either way"""
+        check(self.lib.dsm_ctx_set_big_launch(self._h, int(mode)))
+
+    def debug_big_lists(self):
+        """(non-zero words among the deferred lists' counters -- 0 between passes --, the device's running count of lists found non-empty)"""
+        a, b = _i(0), C.c_uint32(0)
+        check(self.lib.dsm_ctx_debug_big_lists(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def set_tau_screen(self, on):
         """A/B switch: False = every step of the tau sweep in fp64 (same draws except in ~1e-13 near-ties)"""

@@ -265,6 +265,7 @@ extern "C" int dsm_ctx_set_counts(dsm_ctx *c, const int64_t *variants, int V, in
     c->V = V; c->S = S;
     c->have_state = false;
     c->G = 0;                       // V/S changed: every state-sized buffer is re-made by set_state
+    c->big_hot = true;
     TRY(dev_alloc(&c->cnt_vs, n * 4));
     TRY(dev_alloc(&c->nitems, (size_t)S));
     TRY(dev_alloc(&c->tau, (size_t)V));
@@ -415,6 +416,7 @@ extern "C" int dsm_ctx_set_state(dsm_ctx *c, const int64_t *tau, const double *g
     TRY(k_pack_tau(c, d_t, c->tau, c->V, G));
     HIP_TRY(hipMemcpyAsync(c->gamma, gamma, (size_t)c->S * G * sizeof(double), hipMemcpyHostToDevice, c->stream));
     c->tau_rare_n = tau_rare_from_host(gamma, c->S, G);
+    c->big_hot = true;              // a new state: nothing is known about what stage 1 will hand over
     HIP_TRY(hipMemcpyAsync(c->eta, eta, 16 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->have_state = true;
@@ -427,6 +429,7 @@ extern "C" int dsm_ctx_set_gamma_eta(dsm_ctx *c, const double *gamma, const doub
     BIND(c);
     if (gamma) HIP_TRY(hipMemcpyAsync(c->gamma, gamma, (size_t)c->S * c->G * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (gamma) c->tau_rare_n = tau_rare_from_host(gamma, c->S, c->G);
+    c->big_hot = true;
     if (eta) HIP_TRY(hipMemcpyAsync(c->eta, eta, 16 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;
@@ -678,7 +681,8 @@ extern "C" int dsm_ctx_sample_stats(dsm_ctx *c, uint32_t iter, uint64_t *sum_mu,
     HIP_TRY(hipMemsetAsync(c->sum_mu, 0, sg * sizeof(unsigned long long), c->stream));
     TRY(stats_ensure_ntab(c));
     TRY(esum_reset(c));
-    TRY(k_stats(c, iter));
+    // (the launch of stats_big_kernel left out where the context says so: stage 2 then draws the deferred items, the same sums)
+    TRY(k_stats(c, iter, !(stats_big_optional(c) && !stats_big_wanted(c))));
     TRY(k_esum_fold(c));
     if (sum_mu) HIP_TRY(hipMemcpyAsync(sum_mu, c->sum_mu, sg * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (esum) HIP_TRY(hipMemcpyAsync(esum, c->esum, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
@@ -716,7 +720,8 @@ extern "C" int dsm_ctx_debug_stage1(dsm_ctx *c, uint32_t iter, uint32_t *ntab, u
     if (esum) HIP_TRY(hipMemcpyAsync(esum, c->esum, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemsetAsync(c->ntab, 0, t.size() * sizeof(uint32_t), c->stream));
     TRY(esum_reset(c));
-    HIP_TRY(hipMemsetAsync(c->big_count, 0, DSM_BIG_NT * DSM_BIG_NL * DSM_BIG_STRIDE * sizeof(uint32_t), c->stream));     // no stage 2 follows to reset it
+    HIP_TRY(hipMemsetAsync(c->big_count, 0, DSM_BIG_NT * DSM_BIG_NL * DSM_BIG_STRIDE * sizeof(uint32_t), c->stream));     // (the running count of non-empty lists with them)
+    c->big_seen = 0; c->big_hot = true;
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (ntab)
         for (size_t h = 0; h < NH; ++h)
@@ -912,6 +917,14 @@ static int gibbs_update(dsm_ctx *const *ctxs, int K, bool batched, int n_iter, T
     const bool agg = spec >= 2;
     const bool fuse_s2 = agg && lead->G < 10;           // many subsets per sample: stage 2 as its own 1024-thread launch
     const size_t sg = (size_t)lead->S * lead->G;
+    // The launch of stats_big_kernel after stage 1 is a choice for the full chain whose Dirichlet launch runs stage 2 (it then draws what
+    // the deferred lists hold itself).  Chains with G >= 10, specification 1 or 4, sharded chains and the held and fixed-tau chains keep
+    // the launch unconditionally (kernels_stats.hip: stats_big_optional).  The choice is one of speed only; a batch launches if any
+    // of its chains would.
+    const bool big_opt = full && fuse_s2 && stats_big_optional(lead);
+    auto big_wanted = [&]() { bool w = !big_opt; for (int k = 0; k < K; ++k) w = w || stats_big_wanted(ctxs[k]); return w; };
+    bool launch_big = big_wanted();
+    const bool big_auto = big_opt && !batched && stats_big_mode(lead) == -1;       // (not forced: the next look can change the choice)
     // the MT19937 words of the sweeps are generated on the side stream, chunks of sweeps ahead (never beyond the last sweep
     // of the call: the stream position must equal the reference's)
     std::vector<SweepWords> words;
@@ -944,8 +957,12 @@ static int gibbs_update(dsm_ctx *const *ctxs, int K, bool batched, int n_iter, T
     for (int it = 0; it < n_iter; ++it) {
         // (the abundances move during a burn-in: the choice of the full sweep's instantiation is looked at again now and then -- a stream
         // synchronisation and a 4-byte read-back every 64 iterations; the draws do not depend on it)
-        if (full && !batched && it && (it & 63) == 0 && lead->tau_neartie_mode == -1) { TRY(k_tau_rare_count(lead, true)); TRY(k_tau_neartie_hint(lead)); }
-        TRY(ch.launch([&](dsm_ctx *c, int k) { ic[k] = c->iter_ctr++; return agg ? k_stats_stage1(c, ic[k]) : k_stats_v1(c, ic[k]); }));
+        // (the same look tells whether stage 1 still hands items over: a settled chain drops the launch of stats_big_kernel, at most 64 iterations late)
+        if (full && !batched && it && (it & 63) == 0 && (lead->tau_neartie_mode == -1 || big_auto)) {
+            TRY(k_tau_rare_count(lead, true)); TRY(k_tau_neartie_hint(lead));
+            launch_big = big_wanted();
+        }
+        TRY(ch.launch([&](dsm_ctx *c, int k) { ic[k] = c->iter_ctr++; return agg ? k_stats_stage1(c, ic[k], launch_big) : k_stats_v1(c, ic[k]); }));
         if (agg && !fuse_s2) TRY(ch.launch([&](dsm_ctx *c, int k) { return k_stats_stage2(c, ic[k]); }));
         // sampleGamma (:342) + the eta draw (:347: eta depends only on the E sums) + traces; the same
         // launch finalizes iteration it-1 (ll, lp, MAP test :349-353) in one extra workgroup
@@ -976,15 +993,21 @@ static int gibbs_update(dsm_ctx *const *ctxs, int K, bool batched, int n_iter, T
     // the last iteration's finalize launch of a chain run alone also counts the haplotypes that are rare in every sample -- what the next
     // call's choice of sweep instantiation goes by -- straight into the host's pinned word: it rides on this call's own launch and synchronisation
     const bool want_rare = !batched && n_iter > 0 && lead->tau_neartie_mode == -1;
-    if (want_rare && !lead->h_rare) HIP_TRY(hipHostMalloc((void **)&lead->h_rare, sizeof(int), hipHostMallocDefault));
+    // ... and, for every chain whose launch of stats_big_kernel is a choice, the device's count of deferred lists found non-empty
+    const bool want_big = big_opt && n_iter > 0;
+    TRY(ch.each([&](dsm_ctx *c, int) -> int {
+        if ((want_rare || want_big) && !c->h_rare) HIP_TRY(hipHostMalloc((void **)&c->h_rare, 2 * sizeof(int), hipHostMallocDefault));
+        return DSM_OK;
+    }));
     if (n_iter > 0)
         TRY(ch.each([&](dsm_ctx *c, int k) {
             return k_finalize(c, nb_prev[k], n_iter - 1, 0, prior_slot(c, n_iter - 1), c->gamma_trace + (size_t)(n_iter - 1) * sg,
-                              c->eta_trace + (size_t)(n_iter - 1) * 16, 0, want_rare ? c->h_rare : nullptr);
+                              c->eta_trace + (size_t)(n_iter - 1) * 16, 0, want_rare ? c->h_rare : nullptr, want_big ? c->h_rare + 1 : nullptr);
         }));
     HIP_TRY(hipStreamSynchronize(lead->stream));
     if (!full && !fixed) HIP_TRY(hipStreamSynchronize(lead->stream_rng));
     if (want_rare) lead->tau_rare_n = *lead->h_rare;
+    if (want_big) TRY(ch.each([&](dsm_ctx *c, int) -> int { stats_big_take(c, (uint32_t)c->h_rare[1]); return DSM_OK; }));
     return DSM_OK;
 }
 
@@ -1399,6 +1422,36 @@ extern "C" int dsm_ctx_set_tau_neartie(dsm_ctx *c, int mode)
 {
     if (!c || mode < -1 || mode > 1) { dsm_set_error("set_tau_neartie: -1 (by the abundances), 0 or 1"); return DSM_ERR_ARG; }
     c->tau_neartie_mode = mode;
+    return DSM_OK;
+}
+
+// Whether a Gibbs iteration launches stats_big_kernel between stage 1 and the Dirichlet launch, where that is a choice (kernels_stats.hip:
+// stats_big_optional): -1 = while stage 1 was last seen handing items over, 0 = never (the Dirichlet launch draws them), 1 = always.
+// Same draws bit for bit.
+extern "C" int dsm_ctx_set_big_launch(dsm_ctx *c, int mode)
+{
+    if (!c || mode < -1 || mode > 1) { dsm_set_error("set_big_launch: -1 (while the deferred lists are in use), 0 or 1"); return DSM_ERR_ARG; }
+    c->big_launch_mode = mode;
+    return DSM_OK;
+}
+
+// test hook: how many of the deferred lists' counters are non-zero now (0 between passes), and the running count of lists found non-empty
+extern "C" int dsm_ctx_debug_big_lists(dsm_ctx *c, int *nonzero, uint32_t *seen)
+{
+    if (!c) { dsm_set_error("debug_big_lists: null context"); return DSM_ERR_ARG; }
+    if (nonzero) *nonzero = 0;
+    if (seen) *seen = 0;
+    if (!c->big_count) return DSM_OK;
+    BIND(c);
+    std::vector<uint32_t> w(DSM_BIG_NT * DSM_BIG_NL * DSM_BIG_STRIDE);
+    HIP_TRY(hipMemcpyAsync(w.data(), c->big_count, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int nz = 0;
+    for (int i = 0; i < DSM_BIG_NT * DSM_BIG_NL; ++i) nz += w[(size_t)i * DSM_BIG_STRIDE] != 0u;
+    nz += w[DSM_BIG_W_ARRIVE] != 0u;                      // (the arrival word and the tickets are zero between launches too)
+    for (int i = 0; i < DSM_BIG_NT * DSM_BIG_NL; ++i) nz += w[(size_t)i * DSM_BIG_STRIDE + DSM_BIG_W_TICKET] != 0u;
+    if (nonzero) *nonzero = nz;
+    if (seen) *seen = w[DSM_BIG_W_SEEN];
     return DSM_OK;
 }
 

@@ -12,7 +12,11 @@
 #define DSM_BIG_NL 64        // sub-lists of deferred stage-1 items (kernels_stats.hip), one counter each ...
 #define DSM_BIG_STRIDE 16    // ... 64 B apart
 #define DSM_BIG_NT 3         // ... for each kind of deferred item (BTRS / long search / search + two more binomials)
-#define DSM_U_CHUNK 8        // MT19937 words are generated in chunks of up to this many sweeps (api.hip: SweepWords)
+// the spare words of the counters' lines hold what the consumers of the lists share:
+#define DSM_BIG_W_ARRIVE 1   // [1] arrivals at the end of the inline list phase (dsm_stage2.h); zero between launches
+#define DSM_BIG_W_SEEN 2     // [2] lists found non-empty so far, a running count: the host reads it to choose whether to launch stats_big_kernel
+#define DSM_BIG_W_TICKET 3   // [list * DSM_BIG_STRIDE + 3] workgroups of stats_big_kernel done with the list; zero between launches
+#define DSM_U_CHUNK 8       // MT19937 words are generated in chunks of up to this many sweeps (api.hip: SweepWords)
 
 #define DSM_STATS_AGG 2      // the version of the aggregated mu/E specification that runs by default (oracle/stats_agg.c); version 3 (table
                              // exp / log instead of the squaring loop) is selectable: measured 2 us slower in stage 1 at config 3
@@ -141,7 +145,13 @@ struct dsm_ctx {
     bool tau_neartie_on = false;    // this call runs the sweep's instantiation with the near-tie screen (kernels_gibbs.hip: k_tau_neartie_hint)
     int tau_rare_n = 0;             // haplotypes at or below DSM_NT_RARE in every sample, as last known: from the host's gamma (set_state /
                                     // set_gamma_eta), from the device's at the end of a Gibbs call and every 64 iterations inside one
-    int *h_rare = nullptr;          // pinned word the count is read back into (no synchronisation of its own at the end of a call)
+    int *h_rare = nullptr;          // pinned words [2] the count is read back into (no synchronisation of its own at the end of a call); [1]: big_seen below
+    // The launch of stats_big_kernel between stage 1 and the Dirichlet launch (kernels_stats.hip: k_stats_stage1).  A matter of speed only:
+    // where it is left out, the Dirichlet launch finds the deferred lists non-empty and draws the items itself, the same draws.
+    int big_launch_mode = -1;       // dsm_ctx_set_big_launch: -1 = while the lists were last seen non-empty (big_hot), 0 = never, 1 = always
+    bool big_hot = true;            // the lists were non-empty when last looked at -- or nothing is known yet (new state, new table, new lists)
+    uint32_t big_seen = 0;          // the device's running count of lists found non-empty (big_count[DSM_BIG_W_SEEN]) as last read: at the end of
+                                    // a Gibbs call and every 64 iterations inside one, where h_rare is read
     double *prior_all = nullptr;    // [n_iter][S + 4] priors of the stored states of updateTau
     double *prior = nullptr;        // [2][DSM_MAX_S + 4] per-row Dirichlet log-prior terms, by iteration parity
     double *scalars = nullptr;      // [8] misc device scalars
@@ -225,8 +235,14 @@ static inline int stats_draw_version(int spec) { return spec == 4 ? 2 : spec; } 
 int k_tau_neartie_hint(dsm_ctx *c);
 int k_tau_rare_count(dsm_ctx *c, bool wait);         // enqueue the count of rare haplotypes of the resident gamma -> *h_rare (wait: and take it)
 int tau_rare_from_host(const double *gamma, int S, int G);
-int k_stats(dsm_ctx *c, uint32_t iter);
-int k_stats_stage1(dsm_ctx *c, uint32_t iter);
+// launch_big = false: stage 1 without the launch of stats_big_kernel -- only where the launch that runs stage 2 draws the lists' items
+// itself (stats_big_optional)
+int k_stats(dsm_ctx *c, uint32_t iter, bool launch_big = true);
+int k_stats_stage1(dsm_ctx *c, uint32_t iter, bool launch_big = true);
+bool stats_big_optional(const dsm_ctx *c);  // the chain's stage 2 can draw deferred items (aggregated specification 2 / 3, G < 10, not sharded by positions)
+int stats_big_mode(const dsm_ctx *c);       // big_launch_mode, or DESMAN_HIP_BIG_LAUNCH where the context has none of its own
+bool stats_big_wanted(const dsm_ctx *c);  // the host's choice for a chain where the launch is optional (big_launch_mode, DESMAN_HIP_BIG_LAUNCH, big_hot)
+void stats_big_take(dsm_ctx *c, uint32_t seen);      // a fresh reading of the device's count of non-empty lists -> big_hot
 int k_stats_stage2(dsm_ctx *c, uint32_t iter);
 int k_binom_test(dsm_ctx *c, int kind, uint32_t n, const double *w, uint64_t seed, int nsamp, uint32_t *d_out, int spec);
 int k_esum_fold(dsm_ctx *c);             // kernels_stats.hip: the copies of Esum stage 1 adds to -> Esum
@@ -245,7 +261,7 @@ int tau_shape(int S, int *lpv, int *nsl);      // lanes per position and sample 
 int k_shard_pack(dsm_ctx *c, int nblocks);
 int k_shard_unpack(dsm_ctx *c);
 int k_finalize(dsm_ctx *c, int nblocks, int it, int star_mode, const double *prior, const double *gamma_src,
-               const double *eta_src, int slot = 0, int *rare_out = nullptr);
+               const double *eta_src, int slot = 0, int *rare_out = nullptr, int *big_out = nullptr);
 
 // ---- launchers (kernels_fixtau.hip)
 int k_fixtau_pool(dsm_ctx *c, const int32_t *d_row, int32_t *d_pooled);           // pooled[row[v]][s][b] += counts[v][s][b]

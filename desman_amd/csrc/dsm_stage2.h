@@ -9,6 +9,7 @@
 // Shared by stats_stage2_kernel (kernels_stats.hip) and dirichlet_kernel (kernels_gibbs.hip, fused form).
 #pragma once
 #include "dsm_binom.h"
+#include "dsm_big_item.h"
 #include "log_table.h"
 
 #define S2_MAX_NODES 32
@@ -31,12 +32,96 @@ struct Stage2Params {
     int S, G;
     uint32_t k0, k1, iter;
     uint32_t hmul, swz;             // row of (subset H, sample s) in ntab: (H * hmul + (s >> 4) * swz) mod 2^G (dsm_host.h: DSM_NTAB_HMUL / _SWZ)
-    uint32_t *big_count;            // work-list counter of stage 1: consumed by now, reset here for the next pass (or null)
+    uint32_t *big_count;            // work-list counters of stage 1 (or null)
+    // The deferred items of stage 1 (big_list non-null: G < 10, one workgroup per sample).  stats_big_kernel leaves every list it consumed
+    // empty; where the host left that launch out, the counters are still up and the workgroups of this launch draw the items themselves
+    // (s2_inline_items below).  The host's choice is a matter of speed only: either way every item is drawn exactly once.
+    // (only what the rest of the block does not hold already: the chains of a batch share one argument segment)
+    const unsigned long long *big_list;
+    const int32_t *cnt_vs;          // [V][S][4]
+    const uint64_t *tau;            // [V]
+    const double *eta;              // [4][4] the matrix stage 1 ran with
+    uint32_t big_seg;               // entries per list
+    int V;
     int nsplit;                     // workgroups that share a sample's root level (stand-alone kernel, G >= 11), else 1
     uint32_t *scratch, *ticket;     // [S][S2_TAB_ENTRIES] level-1 tables handed over, [S] arrival counters; zero between passes
 };                                  // the plan of the halving tree (a function of G) travels beside it: one per launch
 
 S2Plan make_stage2_plan(int G);     // kernels_stats.hip
+struct dsm_ctx;
+void stats_s2_lists(const dsm_ctx *c, Stage2Params *p);     // kernels_stats.hip: the deferred-list fields above
+// ... and what differs between the launches that run stage 2 (an argument of its own)
+struct S2Lists {
+    unsigned long long *esum;       // [16] the items' E sums are added here (device-scope atomics)
+    int n_arrive;                   // workgroups of the launch that read the counters: whoever arrives last closes the lists
+};
+
+#define S2_NLIST (DSM_BIG_NT * DSM_BIG_NL)
+// every thread of the first three wavefronts loads one list counter (early: the load flies while the tables are staged) ...
+__device__ __forceinline__ uint32_t s2_list_count(const Stage2Params &p)
+{
+    return (p.big_list && threadIdx.x < S2_NLIST) ? p.big_count[threadIdx.x * DSM_BIG_STRIDE] : 0u;
+}
+// ... and posts, ahead of a barrier the caller has anyway, whether its wavefront saw a non-empty list; after that barrier s2_lists_any()
+// is the same for every thread of the workgroup -- and of the launch: the counters change only once every workgroup has read them
+__device__ __forceinline__ void s2_lists_post(uint32_t *wflag, uint32_t my_cnt)
+{
+    const bool nz = __builtin_amdgcn_ballot_w64(my_cnt != 0u) != 0ull;
+    if ((threadIdx.x & 63) == 0 && threadIdx.x < 256) wflag[threadIdx.x >> 6] = nz ? 1u : 0u;
+}
+__device__ __forceinline__ bool s2_lists_any(const uint32_t *wflag) { return (wflag[0] | wflag[1] | wflag[2]) != 0u; }
+// one arrival per workgroup that found the lists non-empty; true in the workgroup that arrives last (all threads; ends with a barrier and
+// a device-scope fence).  The caller's own device-scope adds must have been fenced before.
+__device__ __forceinline__ bool s2_lists_arrive(const Stage2Params &p, int n_arrive, int *last_flag)
+{
+    if (threadIdx.x == 0) *last_flag = (atomicAdd(p.big_count + DSM_BIG_W_ARRIVE, 1u) == (uint32_t)(n_arrive - 1)) ? 1 : 0;
+    __syncthreads();
+    const bool last = *last_flag != 0;
+    __threadfence();
+    return last;
+}
+// the last arriver: every list has been consumed (each sample's workgroup drew its own items), so the counters go back to zero
+__device__ __forceinline__ void s2_lists_close(const Stage2Params &p)
+{
+    if (threadIdx.x < S2_NLIST) p.big_count[threadIdx.x * DSM_BIG_STRIDE] = 0u;
+    if (threadIdx.x == 0) { p.big_count[DSM_BIG_W_ARRIVE] = 0u; atomicAdd(p.big_count + DSM_BIG_W_SEEN, 1u); }
+}
+// The inline list phase of sample s's workgroup (all threads; the samplers' tables are staged).  It draws the items of ITS sample from
+// every non-empty list -- a list holds items of any sample, so it filters by the item's sample; the adds go to row s of the subset table
+// and to Esum -- then fences, arrives, and returns whether it arrived last.  No workgroup waits for another.
+template <int SPEC>
+__device__ __forceinline__ bool s2_inline_items(const Stage2Params &p, const S2Lists &ls, int s, uint32_t my_cnt, const double *rcp, const double2 *ltab)
+{
+    BigItemParams big;              // (never a chain sharded by positions, never the pooled counts of specification 4: those keep stats_big_kernel)
+    big.cnt_vs = p.cnt_vs; big.tau = p.tau; big.gamma = p.gamma; big.pat_x = nullptr; big.ntab = p.ntab; big.rep = p.rep; big.ld = p.ld;
+    big.S = p.S; big.G = p.G; big.v_off = 0; big.V_tot = p.V; big.k0 = p.k0; big.k1 = p.k1; big.iter = p.iter; big.hmul = p.hmul; big.swz = p.swz;
+    __shared__ uint32_t cnt[S2_NLIST];
+    __shared__ unsigned long long eacc[16];
+    __shared__ double es[16];
+    __shared__ int last_flag;
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    if (tid < S2_NLIST) cnt[tid] = my_cnt;
+    if (tid < 16) { eacc[tid] = 0ull; es[tid] = p.eta[tid]; }
+    __syncthreads();
+    for (int sub = 0; sub < S2_NLIST; ++sub) {
+        const uint32_t nb = cnt[sub];
+        if (!nb) continue;
+        const unsigned long long *list = p.big_list + (size_t)sub * p.big_seg;
+        for (uint32_t i = tid; i < nb; i += nthr) {
+            const unsigned long long item = list[i];
+            if (big_item_sample(big, item) != s) continue;
+            uint32_t n[4];
+            const int b = big_item_draw<SPEC>(big, item, (unsigned)sub, es, rcp, ltab, n);
+#pragma unroll
+            for (int a = 0; a < 4; ++a) if (n[a]) atomicAdd(&eacc[b * 4 + a], (unsigned long long)n[a]);
+        }
+    }
+    __syncthreads();
+    if (tid < 16 && eacc[tid]) atomicAdd(&ls.esum[tid], eacc[tid]);
+    __threadfence();                    // this thread's adds to the table and to Esum are performed ...
+    __syncthreads();                    // ... every thread's are
+    return s2_lists_arrive(p, ls.n_arrive, &last_flag);      // (its closing fence: what stage 2 loads below is loaded afresh)
+}
 
 #define S2_SMEM_BYTES (DSM_LOG_TAB_N * 16 + DSM_EXP_TAB_N * 8 + DSM_RCP_TAB_N * 8 + 32 * 8 + S2_TAB_ENTRIES * 4 + 32 * 4 + 5 * S2_MAX_NODES * 4)
 
@@ -48,9 +133,12 @@ __device__ unsigned long long s2_clk[1024 * 8];
 #endif
 // leaf counts end in LDS (returned pointer, [G] u32, valid after the function's final barrier); to_global also adds
 // them to p.sum_mu[s][.]
+// last_out (or null): set where this workgroup arrived last at the end of an inline list phase
 template <int SPEC>
-__device__ __forceinline__ const uint32_t *stage2_sample(const Stage2Params &p, const S2Plan &pl, int s, char *smem, bool to_global, int part = 0)
+__device__ __forceinline__ const uint32_t *stage2_sample(const Stage2Params &p, const S2Plan &pl, int s, char *smem, bool to_global, int part = 0,
+                                                         const S2Lists &ls = S2Lists{nullptr, 0}, bool *last_out = nullptr)
 {
+    __shared__ uint32_t lists_wflag[4];
     const int G = p.G, tid = threadIdx.x, nthr = blockDim.x;      // 256 (fused form) or 1024 (many subsets)
     double2 *ltab = reinterpret_cast<double2 *>(smem);                         // [256] log table, then [64] exp table
     double *etab = reinterpret_cast<double *>(ltab + DSM_LOG_TAB_N);
@@ -75,7 +163,9 @@ __device__ __forceinline__ const uint32_t *stage2_sample(const Stage2Params &p, 
             pre_ok = true;
         }
     }
-    if (s == 0 && part == 0 && tid < DSM_BIG_NT * DSM_BIG_NL && p.big_count) p.big_count[tid * DSM_BIG_STRIDE] = 0u;
+    const uint32_t my_cnt = s2_list_count(p);
+    // (without the lists -- stage 2 of G >= 10, which always follows stats_big_kernel -- the counters are cleared here as they always were)
+    if (!p.big_list && s == 0 && part == 0 && tid < DSM_BIG_NT * DSM_BIG_NL && p.big_count) p.big_count[tid * DSM_BIG_STRIDE] = 0u;
     if (tid < DSM_LOG_TAB_N) ltab[tid] = reinterpret_cast<const double2 *>(p.log_tab)[tid];
     if (tid < DSM_EXP_TAB_N) etab[tid] = p.log_tab[2 * DSM_LOG_TAB_N + tid];
     for (int k = tid; k < DSM_RCP_TAB_N; k += nthr) rcp[k] = k ? 1.0 / (double)k : 0.0;
@@ -85,7 +175,14 @@ __device__ __forceinline__ const uint32_t *stage2_sample(const Stage2Params &p, 
         n_child[tid] = pl.child[tid];
     }
     for (int i = tid; i < S2_TAB_ENTRIES; i += nthr) tab[i] = 0u;
+    if (p.big_list) s2_lists_post(lists_wflag, my_cnt);
     __syncthreads();
+    if (p.big_list && s2_lists_any(lists_wflag)) {
+        const bool last = s2_inline_items<SPEC>(p, ls, s, my_cnt, rcp, ltab);
+        if (last) s2_lists_close(p);
+        if (last_out) *last_out = last;
+        pre_ok = false;                 // the count loaded ahead is from before this sample's items were added
+    }
     S2_CLK(s, 1);
 
     // Round 6: a node's count goes straight into leaf[] where its child is a single haplotype, so the tree's last level -- leaves only: a pass

@@ -537,9 +537,15 @@ struct FinalParams {
     uint32_t *screen_ctl;         // [0] sweeps still to run without the screening pass
     uint32_t *blk_order;          // [nblocks] out (or null): the order the next sweep of this parity runs its blocks in -- those first that
                                   // left a step to the fp64 code in the finalized one (tau_body: `order`)
-    int *rare_out; int G;         // stand-alone launch at the end of a Gibbs call (or null): how many haplotypes of the finalized state are rare in
+};
+// what rides on the stand-alone launch at the end of a Gibbs call (its own argument: FinalParams travels in every chain's block of the
+// batched Dirichlet and sweep launches, whose argument segments are nearly full)
+struct FinalRide {
+    int *rare_out; int G;         // (or null) how many haplotypes of the finalized state are rare in
                                   // every sample (gamma_rare_kernel's count), written straight to the host's pinned word -- what the NEXT call's
                                   // choice of sweep instantiation goes by; as its own launch + copy + clear it was 15 us of every call
+    const uint32_t *big_seen; int *big_out;   // (or null) the running count of deferred lists found non-empty -> the host's pinned word; what the
+                                  // NEXT call's choice of launching stats_big_kernel goes by (kernels_stats.hip: stats_big_take)
 };
 
 __device__ void finalize_body(const FinalParams &p, double *red, double *redp, int *flag, int tid, int nthr)
@@ -625,23 +631,24 @@ __device__ void finalize_body(const FinalParams &p, double *red, double *redp, i
 
 // NB the reduction tree depends on the workgroup size, so one chain must always finalize with the same
 // size to stay bitwise reproducible: both users below run it with 256 threads.
-__global__ __launch_bounds__(256) void finalize_kernel(FinalParams p)
+__global__ __launch_bounds__(256) void finalize_kernel(FinalParams p, FinalRide r)
 {
     __shared__ double red[256], redp[256];
     __shared__ int flag;
     finalize_body(p, red, redp, &flag, threadIdx.x, 256);
-    if (p.rare_out) {                                     // (gamma_rare_kernel's count on the finalized state's abundances)
+    if (r.rare_out) {                                     // (gamma_rare_kernel's count on the finalized state's abundances)
         __syncthreads();
         if (threadIdx.x == 0) flag = 0;
         __syncthreads();
-        for (int g = threadIdx.x; g < p.G; g += 256) {
+        for (int g = threadIdx.x; g < r.G; g += 256) {
             double m = 0.0;
-            for (int s = 0; s < p.S; ++s) m = fmax(m, p.gamma_src[(size_t)s * p.G + g]);
+            for (int s = 0; s < p.S; ++s) m = fmax(m, p.gamma_src[(size_t)s * r.G + g]);
             if ((float)m <= (float)DSM_NT_RARE) atomicAdd(&flag, 1);
         }
         __syncthreads();
-        if (threadIdx.x == 0) *p.rare_out = flag;
+        if (threadIdx.x == 0) *r.rare_out = flag;
     }
+    if (r.big_out && threadIdx.x == 0) *r.big_out = (int)*r.big_seen;
 }
 
 // =====================================================================
@@ -698,15 +705,64 @@ struct DirParams {
     Stage2Params s2;
 };
 
+// the draw of one row by one wavefront (lane g draws variate g from shape prior + cnt), normalisation, prior term, outputs
+__device__ __forceinline__ void dirichlet_draw_row(const DirParams &q, int row, int lane, unsigned long long cnt)
+{
+    const int S = q.S, G = q.G;
+    const bool is_gamma = row < S;
+    const int n = is_gamma ? G : 4;
+    double y = 0.0;
+    if (lane < n) {
+        const uint32_t vid = is_gamma ? (uint32_t)(row * G + lane) : (uint32_t)(S * G + (row - S) * 4 + lane);      // variate id: the spec's flat index
+        const double shape = (is_gamma ? q.alpha : q.delta) + (double)cnt;
+        y = gamma_variate(shape, vid, q.iter, q.k0, q.k1);
+    }
+    // row normalisation, lane-parallel (inactive lanes carry 0)
+    double x = y / group_allreduce_sum<64>(y);
+    if (is_gamma) {
+        if (lane < n && x < q.epsilon) x = q.epsilon;                   // HaploSNP_Sampler.py:271
+        x = x / group_allreduce_sum<64>(lane < n ? x : 0.0);            // :272-273
+    }
+    const double a1 = is_gamma ? q.alpha : q.delta;
+    const double lsum = group_allreduce_sum<64>(lane < n ? (a1 - 1.0) * log(x) : 0.0);
+    if (lane == 0) q.rowprior[row] = (is_gamma ? q.lgc_gamma : q.lgc_eta) + lsum;
+    if (lane < n) {
+        if (is_gamma) { q.gamma_out[row * G + lane] = x; if (q.gamma_trace) q.gamma_trace[row * G + lane] = x; }
+        else { q.eta_out[(row - S) * 4 + lane] = x; if (q.eta_trace) q.eta_trace[(row - S) * 4 + lane] = x; }
+    }
+}
+
+// The eta rows where the deferred items of stage 1 were drawn inside this launch (dsm_stage2.h: s2_inline_items): Esum is complete only
+// when the last workgroup has arrived, so that workgroup -- a gamma row's or an eta row's, whichever came last -- folds the copies of
+// Esum and draws all four rows, one per wavefront (the four eta workgroups have returned).  All 256 threads; its own LDS, a gamma row's
+// stage-2 tables stay as they are.  Every add to Esum was fenced before its workgroup arrived; the sums are read at the memory side.
+__device__ __forceinline__ void dirichlet_eta_tail(const DirParams &q)
+{
+    static_assert(DSM_ESUM_PARTS * 4 == 256, "one thread per (copy, observed base)");
+    __shared__ unsigned long long te[16];
+    const int tid = threadIdx.x;
+    if (tid < 16) te[tid] = 0ull;
+    __syncthreads();
+    {
+        const int ob = tid & 3, k = tid >> 2;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const unsigned long long v = atomicExch(&q.esum[16 + k * 16 + ob * 4 + a], 0ull);
+            if (v) atomicAdd(&te[ob * 4 + a], v);
+        }
+    }
+    __syncthreads();
+    if (tid < 16) te[tid] += q.zero_after ? atomicExch(&q.esum[tid], 0ull) : atomicAdd(&q.esum[tid], 0ull);
+    __syncthreads();
+    const int a = tid >> 6, lane = tid & 63;
+    dirichlet_draw_row(q, q.S + a, lane, lane < 4 ? te[lane * 4 + a] : 0ull);
+}
+
 __device__ __forceinline__ void dirichlet_body(const DirParams &q, const S2Plan &plan)
 {
     unsigned long long *__restrict__ sum_mu = q.sum_mu, *__restrict__ esum = q.esum;
     const int S = q.S, G = q.G;
-    const double alpha = q.alpha, delta = q.delta, epsilon = q.epsilon, lgc_gamma = q.lgc_gamma, lgc_eta = q.lgc_eta;
-    const uint32_t k0 = q.k0, k1 = q.k1, iter = q.iter;
     const int zero_after = q.zero_after;
-    double *__restrict__ gamma_out = q.gamma_out, *__restrict__ gamma_trace = q.gamma_trace;
-    double *__restrict__ eta_out = q.eta_out, *__restrict__ eta_trace = q.eta_trace, *__restrict__ rowprior = q.rowprior;
     const int do_fin = q.do_fin, do_s2 = q.do_s2;
     const FinalParams &fin = q.fin;
     const Stage2Params &s2 = q.s2;
@@ -720,15 +776,32 @@ __device__ __forceinline__ void dirichlet_body(const DirParams &q, const S2Plan 
     const int row = blockIdx.x;
     const bool is_gamma = row < S;
     const uint32_t *leaf = nullptr;
-    if (do_s2 && is_gamma)                                                          // workgroup-uniform branches; both end with a barrier
-        leaf = do_s2 >= 3 ? stage2_sample<3>(s2, plan, row, smem_d, false) : stage2_sample<2>(s2, plan, row, smem_d, false);
+    if (do_s2 && is_gamma) {                                                        // workgroup-uniform branches; both end with a barrier
+        bool last = false;
+        const S2Lists ls = {q.esum, S + 4};             // the gamma rows and the four eta rows read the deferred lists' counters
+        leaf = do_s2 >= 3 ? stage2_sample<3>(s2, plan, row, smem_d, false, 0, ls, &last) : stage2_sample<2>(s2, plan, row, smem_d, false, 0, ls, &last);
+        if (last) dirichlet_eta_tail(q);              // (only where this launch drew deferred items and this workgroup arrived last)
+    }
     if (!is_gamma) {
         // Esum = the context's [4][4] + the DSM_ESUM_PARTS copies the wavefronts of stage 1 added to (kernels_stats.hip: stats_agg_body,
         // round 6): this row needs Esum[., a] -- four counters of every copy, one per thread -- and leaves the copies zero for the next pass
         static_assert(DSM_ESUM_PARTS * 4 == 256, "one thread per (copy, observed base)");
         unsigned long long *ef = reinterpret_cast<unsigned long long *>(smem_d);
+        // the deferred lists of stage 1 first: empty (stats_big_kernel ran, or there was nothing to hand over) -> as always.  Otherwise
+        // the gamma rows are drawing the items now and Esum is not complete yet: this workgroup arrives and leaves; whoever arrives last
+        // draws the four eta rows (dirichlet_eta_tail).  Every workgroup of the launch sees the same counters.
+        const uint32_t my_cnt = do_s2 ? s2_list_count(s2) : 0u;
+        uint32_t *wflag = reinterpret_cast<uint32_t *>(ef + 4);
+        int *last_flag = reinterpret_cast<int *>(wflag + 4);
         if (threadIdx.x < 4) ef[threadIdx.x] = 0ull;
+        s2_lists_post(wflag, my_cnt);
         __syncthreads();
+        if (do_s2 && s2.big_list && s2_lists_any(wflag)) {
+            if (!s2_lists_arrive(s2, S + 4, last_flag)) return;
+            s2_lists_close(s2);
+            dirichlet_eta_tail(q);
+            return;
+        }
         const int ob = threadIdx.x & 3, k = threadIdx.x >> 2;
         unsigned long long *pp = esum + 16 + k * 16 + ob * 4 + (row - S);
         const unsigned long long v = *pp;
@@ -739,29 +812,13 @@ __device__ __forceinline__ void dirichlet_body(const DirParams &q, const S2Plan 
     if (threadIdx.x >= 64) return;                       // the draw needs one wavefront (no workgroup barriers below)
     const int lane = threadIdx.x;
     const int n = is_gamma ? G : 4;
-    const int SG = S * G;
-    double y = 0.0;
+    unsigned long long cnt = 0ull;
     if (lane < n) {
-        double shape;
-        uint32_t vid;                                   // variate id: the spec's flat index
-        if (is_gamma) { vid = (uint32_t)(row * G + lane); shape = alpha + (double)(sum_mu[vid] + (leaf ? (unsigned long long)leaf[lane] : 0ull)); }
-        else { const int a = row - S; vid = (uint32_t)(SG + a * 4 + lane); shape = delta + (double)(esum[lane * 4 + a] + reinterpret_cast<const unsigned long long *>(smem_d)[lane]); }
-        y = gamma_variate(shape, vid, iter, k0, k1);
+        if (is_gamma) cnt = sum_mu[row * G + lane] + (leaf ? (unsigned long long)leaf[lane] : 0ull);
+        else cnt = esum[lane * 4 + (row - S)] + reinterpret_cast<const unsigned long long *>(smem_d)[lane];
         if (zero_after) { if (is_gamma) sum_mu[row * G + lane] = 0ull; else esum[lane * 4 + (row - S)] = 0ull; }
     }
-    // row normalisation, lane-parallel (inactive lanes carry 0)
-    double x = y / group_allreduce_sum<64>(y);
-    if (is_gamma) {
-        if (lane < n && x < epsilon) x = epsilon;                       // HaploSNP_Sampler.py:271
-        x = x / group_allreduce_sum<64>(lane < n ? x : 0.0);            // :272-273
-    }
-    const double a1 = is_gamma ? alpha : delta;
-    const double lsum = group_allreduce_sum<64>(lane < n ? (a1 - 1.0) * log(x) : 0.0);
-    if (lane == 0) rowprior[row] = (is_gamma ? lgc_gamma : lgc_eta) + lsum;
-    if (lane < n) {
-        if (is_gamma) { gamma_out[row * G + lane] = x; if (gamma_trace) gamma_trace[row * G + lane] = x; }
-        else { eta_out[(row - S) * 4 + lane] = x; if (eta_trace) eta_trace[(row - S) * 4 + lane] = x; }
-    }
+    dirichlet_draw_row(q, row, lane, cnt);
     S2_CLK(row, 7);
 }
 #ifdef DSM_AB_SWITCHES
@@ -1395,7 +1452,6 @@ static FinalParams make_final(dsm_ctx *c, int nblocks, int it, int star_mode, co
     p.step_cnt = c->step_cnt + (size_t)slot * 2 * DSM_MAX_GRID; p.sweep_stats = c->sweep_stats; p.screen_ctl = c->screen_ctl + slot;
     static const bool order_on = !(getenv("DESMAN_HIP_TAU_ORDER") && atoi(getenv("DESMAN_HIP_TAU_ORDER")) == 0);      // A/B switch
     p.blk_order = nullptr;
-    p.rare_out = nullptr; p.G = c->G;
     // (a launch whose workgroups are all resident at once has no tail to move the long steps out of: the order is left alone and the finalize
     // step stays short -- at config 2 it rides in a 8 us Dirichlet launch)
     if (order_on && c->blk_order && nblocks > 0 && nblocks <= DSM_MAX_GRID) {
@@ -1429,6 +1485,7 @@ int k_dirichlet(dsm_ctx *c, uint32_t iter, double *gamma_out, double *gamma_trac
         s2.ntab = c->ntab; s2.rep = c->ntab_rep; s2.ld = c->ntab_ld; s2.gamma = c->gamma; s2.sum_mu = c->sum_mu; s2.log_tab = c->log_tab;
         s2.S = c->S; s2.G = c->G; s2.k0 = k0; s2.k1 = k1; s2.iter = iter; s2.hmul = DSM_NTAB_HMUL; s2.swz = DSM_NTAB_SWZ;
         s2.big_count = c->big_count;
+        stats_s2_lists(c, &s2);
     }
     DirParams q;
     q.sum_mu = c->sum_mu; q.esum = c->esum; q.S = c->S; q.G = c->G;
@@ -1532,12 +1589,16 @@ int tau_rare_from_host(const double *gamma, int S, int G)
 // (end of a Gibbs call), or with one of its own (wait: every 64 iterations inside a call)
 int k_tau_rare_count(dsm_ctx *c, bool wait)
 {
-    if (!c->h_rare) HIP_TRY(hipHostMalloc((void **)&c->h_rare, sizeof(int), hipHostMallocDefault));
+    if (!c->h_rare) HIP_TRY(hipHostMalloc((void **)&c->h_rare, 2 * sizeof(int), hipHostMallocDefault));
     hipLaunchKernelGGL(gamma_rare_kernel, dim3(1), dim3(256), 0, c->stream, c->gamma, c->S, c->G, c->nchange + 1);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(c->h_rare, c->nchange + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemsetAsync(c->nchange + 1, 0, sizeof(int), c->stream));
+    // the same synchronisation also tells whether stage 1 has handed items over since the last look (dsm_host.h: big_hot)
+    const bool big = wait && c->big_count != nullptr;
+    if (big) HIP_TRY(hipMemcpyAsync(c->h_rare + 1, c->big_count + DSM_BIG_W_SEEN, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     if (wait) { HIP_TRY(hipStreamSynchronize(c->stream)); c->tau_rare_n = *c->h_rare; }
+    if (big) stats_big_take(c, (uint32_t)c->h_rare[1]);
     return DSM_OK;
 }
 
@@ -1693,12 +1754,13 @@ int k_shard_unpack(dsm_ctx *c)
 }
 
 int k_finalize(dsm_ctx *c, int nblocks, int it, int star_mode, const double *prior, const double *gamma_src,
-               const double *eta_src, int slot, int *rare_out)
+               const double *eta_src, int slot, int *rare_out, int *big_out)
 {
     KTimer tm(c, DSM_K_FINAL);
     FinalParams p = make_final(c, nblocks, it, star_mode, prior, gamma_src, eta_src, slot);
-    p.rare_out = rare_out;
-    hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, c->stream, p);
+    FinalRide r = {rare_out, c->G, nullptr, nullptr};
+    if (big_out && c->big_count) { r.big_seen = c->big_count + DSM_BIG_W_SEEN; r.big_out = big_out; }
+    hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, c->stream, p, r);
     HIP_TRY(hipGetLastError());
     return DSM_OK;
 }

@@ -20,6 +20,7 @@
 //   stats v1 (per-read draws, kernels_gibbs.hip: stats_kernel) remains for G > 16 / tables above 64 MB.
 #include "dsm_binom.h"
 #include "dsm_host.h"
+#include "dsm_big_item.h"
 #include "log_table.h"
 
 #include <string.h>
@@ -452,43 +453,15 @@ __device__ __forceinline__ void stats_big_body(const StatsAggParams &p)
 #pragma unroll
     for (int i = 0; i < 16; ++i) eacc[i * 256 + tid] = 0u;
     __syncthreads();
-    const int S = p.S, G = p.G;
+    BigItemParams bp;
+    bp.cnt_vs = p.cnt_vs; bp.tau = p.tau; bp.gamma = p.gamma; bp.pat_x = p.pat_x; bp.ntab = p.ntab; bp.rep = p.rep; bp.ld = p.ld;
+    bp.S = p.S; bp.G = p.G; bp.v_off = p.v_off; bp.V_tot = p.V_tot; bp.k0 = p.k0; bp.k1 = p.k1; bp.iter = p.iter; bp.hmul = p.hmul; bp.swz = p.swz;
     for (uint32_t i = bi * 256u + tid; i < nbig; i += nb * 256u) {
-        const unsigned long long item = list[i];
-        const uint32_t cell = (uint32_t)(item >> 2);
-        const int b = (int)(item & 3ull);
-        const int s = (int)(cell / (uint32_t)p.V_tot), v = (int)(cell - (uint32_t)s * (uint32_t)p.V_tot) - p.v_off;
-        const uint64_t t = p.tau[v];
-        uint32_t xb;
-        if (p.pat_x) { uint32_t *xw = p.pat_x + ((size_t)v * 4 + b) * S + s; xb = *xw; *xw = 0u; }     // spec 4: consumed here (see stats_agg_body)
-        else xb = (uint32_t)p.cnt_vs[((size_t)v * S + s) * 4 + b];
-        uint32_t H[4] = {0, 0, 0, 0};
-        double Gam[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int g = 0; g < G; ++g) {
-            const int a = (int)((t >> (2 * g)) & 3);
-            const double x = p.gamma[(size_t)s * G + g];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) if (a == k) { H[k] |= 1u << g; Gam[k] = Gam[k] + x; }
-        }
-        double W[4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a) W[a] = es[a * 4 + b] * Gam[a];
-        const double Wt = ((W[0] + W[1]) + W[2]) + W[3];
-        if (!(Wt > 0.0)) {
-#pragma unroll
-            for (int a = 0; a < 4; ++a) W[a] = Gam[a];
-        }
-        uint32_t n[4], cbase[4];
-        philox4x32_10(cell, 0u, p.iter, DSM_STREAM_STA1, p.k0, p.k1, cbase);
-        Xo128 rng = item_seed<SPEC>(cbase, (uint32_t)b, p.k0, p.k1);
-        bool defer = false;
-        mult4<true, SPEC>(rng, xb, W, n, rcp, ltab, defer);
+        uint32_t n[4];
+        const int b = big_item_draw<SPEC>(bp, list[i], blockIdx.x, es, rcp, ltab, n);
         uint32_t *erow = eacc + (b * 4) * 256 + tid;
 #pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            erow[a * 256] += n[a];
-            if (n[a]) atomicAdd(p.ntab + (size_t)(blockIdx.x % (unsigned)p.rep) * (((size_t)1 << G) * (size_t)p.ld) + (size_t)((H[a] * p.hmul + ((uint32_t)s >> 4) * p.swz) & ((1u << G) - 1u)) * (size_t)p.ld + s, n[a]);
-        }
+        for (int a = 0; a < 4; ++a) erow[a * 256] += n[a];
     }
     {
         uint32_t e[16];
@@ -500,6 +473,14 @@ __device__ __forceinline__ void stats_big_body(const StatsAggParams &p)
     }
     __syncthreads();
     if (tid < 16 && acc[tid]) atomicAdd(&p.esum[tid], acc[tid]);
+    // a consumed list is left empty: the last of the list's workgroups to get here (every one that had items read the counter before it
+    // drew its ticket) clears the counter and notes that the pass handed items over.  The launch that runs stage 2 finds all counters zero
+    // and goes its usual way; where this launch was left out it finds the items and draws them itself (dsm_stage2.h: s2_inline_items).
+    if (tid == 0) {
+        const uint32_t nwg = min(nb, (nbig + 255u) / 256u);
+        uint32_t *cw = p.big_count + sub * DSM_BIG_STRIDE;
+        if (atomicAdd(cw + DSM_BIG_W_TICKET, 1u) == nwg - 1u) { cw[DSM_BIG_W_TICKET] = 0u; cw[0] = 0u; atomicAdd(p.big_count + DSM_BIG_W_SEEN, 1u); }
+    }
 }
 
 // the copies of Esum stage 1 adds to (stats_agg_body's last lines) -> Esum, copies zero again.  The Gibbs loop never launches this: the
@@ -530,18 +511,18 @@ __global__ __launch_bounds__(256) void stats_big_kernel_b(BatchArgs<StatsAggPara
 
 #include "dsm_stage2.h"
 
-struct Stage2Batch { Stage2Params p[DSM_MAX_BATCH]; S2Plan plan; };
+struct Stage2Batch { Stage2Params p[DSM_MAX_BATCH]; S2Lists ls[DSM_MAX_BATCH]; S2Plan plan; };
 template <int SPEC>
-__global__ __launch_bounds__(1024) void stats_stage2_kernel(Stage2Params p, S2Plan plan)
+__global__ __launch_bounds__(1024) void stats_stage2_kernel(Stage2Params p, S2Plan plan, S2Lists ls)
 {
     __shared__ __attribute__((aligned(16))) char smem2[S2_SMEM_BYTES];
-    stage2_sample<SPEC>(p, plan, (int)blockIdx.x / p.nsplit, smem2, true, (int)blockIdx.x % p.nsplit);
+    stage2_sample<SPEC>(p, plan, (int)blockIdx.x / p.nsplit, smem2, true, (int)blockIdx.x % p.nsplit, ls);
 }
 template <int SPEC>
 __global__ __launch_bounds__(1024) void stats_stage2_kernel_b(Stage2Batch b)
 {
     __shared__ __attribute__((aligned(16))) char smem2[S2_SMEM_BYTES];
-    stage2_sample<SPEC>(b.p[blockIdx.y], b.plan, blockIdx.x, smem2, true);
+    stage2_sample<SPEC>(b.p[blockIdx.y], b.plan, blockIdx.x, smem2, true, 0, b.ls[blockIdx.y]);
 }
 
 // test hook: variate i of a sampler from the stream Philox({i, 0, 0, 'TEST'})  (oracle: orc_binom_test / orc_mult4_test)
@@ -709,9 +690,47 @@ static int ensure_big_list(dsm_ctx *c, size_t seg)
     hipError_t e = hipMalloc((void **)&c->big_list, need * sizeof(unsigned long long));
     if (e != hipSuccess) { dsm_set_error("hipMalloc(%zu B) failed: %s", need * 8, hipGetErrorString(e)); return DSM_ERR_NOMEM; }
     c->big_cap = need;
-    // the counters are zero between passes: stage 2 (its consumer-side successor) resets them
+    // the counters are zero between passes: whoever consumes a list leaves it empty (stats_big_body; dsm_stage2.h: s2_lists_close)
     HIP_TRY(hipMemsetAsync(c->big_count, 0, DSM_BIG_NT * DSM_BIG_NL * DSM_BIG_STRIDE * sizeof(uint32_t), c->stream));
+    c->big_seen = 0; c->big_hot = true;              // (the running count went with them)
     return DSM_OK;
+}
+
+// Where the launch of stats_big_kernel is a choice.  Chains with G >= 10 (stage 2 as its own 1024-thread launch), the per-read pass
+// (specification 1), stage 1 over tau words (4), chains sharded by positions (the tables are exchanged between the two stages) and the
+// held and fixed-tau chains (api.hip: gibbs_update) keep the launch unconditionally.
+bool stats_big_optional(const dsm_ctx *c)
+{
+    const int spec = stats_spec(c);
+    return (spec == 2 || spec == 3) && c->G < 10 && !c->shard_on;
+}
+int stats_big_mode(const dsm_ctx *c)
+{
+    int mode = c->big_launch_mode;
+    if (mode == -1) {                       // DESMAN_HIP_BIG_LAUNCH=0|1: the choice for every context that has none of its own
+        const char *e = getenv("DESMAN_HIP_BIG_LAUNCH");
+        if (e && (e[0] == '0' || e[0] == '1') && e[1] == 0) mode = e[0] - '0';
+    }
+    return mode;
+}
+bool stats_big_wanted(const dsm_ctx *c)
+{
+    const int mode = stats_big_mode(c);
+    return mode == -1 ? c->big_hot : mode == 1;
+}
+void stats_big_take(dsm_ctx *c, uint32_t seen)
+{
+    c->big_hot = seen != c->big_seen;
+    c->big_seen = seen;
+}
+// what the launch that runs stage 2 needs to draw deferred items itself -- where it can: one workgroup per sample (G < 10), the counts
+// themselves (not the pooled ones of specification 4), positions not sharded
+void stats_s2_lists(const dsm_ctx *c, Stage2Params *p)
+{
+    p->big_list = nullptr; p->cnt_vs = nullptr; p->tau = nullptr; p->eta = nullptr; p->big_seg = 0; p->V = c->V;
+    const size_t seg = c->big_cap / (DSM_BIG_NT * DSM_BIG_NL);
+    if (!stats_big_optional(c) || !c->big_list || !c->big_count || seg > 0xFFFFFFFFull) return;
+    p->big_list = c->big_list; p->big_seg = (uint32_t)seg; p->cnt_vs = c->cnt_vs; p->tau = c->tau; p->eta = c->eta;
 }
 
 // spec 4: the word table (4^G entries, all ones = "no pass has written here") and the aggregated counts (zero between passes)
@@ -742,7 +761,7 @@ static int ensure_pat(dsm_ctx *c)
     return DSM_OK;
 }
 
-int k_stats_stage1(dsm_ctx *c, uint32_t iter)
+int k_stats_stage1(dsm_ctx *c, uint32_t iter, bool launch_big)
 {
     int r = ensure_ntab(c);
     if (r != DSM_OK) return r;
@@ -862,7 +881,8 @@ int k_stats_stage1(dsm_ctx *c, uint32_t iter)
             const dim3 g(grid, g_batch.K);
             void *args[] = {(void *)&acc};
             HIP_TRY(hipLaunchKernel(fn_b, g, dim3(256), args, sh, c->stream));
-            if (spec >= 3) hipLaunchKernelGGL(stats_big_kernel_b<3>, dim3(big_grid, g_batch.K), dim3(256), 0, c->stream, acc);
+            if (!launch_big) { }                        // (the caller's choice for the whole batch; see below)
+            else if (spec >= 3) hipLaunchKernelGGL(stats_big_kernel_b<3>, dim3(big_grid, g_batch.K), dim3(256), 0, c->stream, acc);
             else hipLaunchKernelGGL(stats_big_kernel_b<2>, dim3(big_grid, g_batch.K), dim3(256), 0, c->stream, acc);
         }
         HIP_TRY(hipGetLastError());
@@ -873,6 +893,9 @@ int k_stats_stage1(dsm_ctx *c, uint32_t iter)
         void *args[] = {(void *)&p};
         HIP_TRY(hipLaunchKernel(fn, dim3(grid), dim3(256), args, sh, c->stream));
     }
+    // Left out (launch_big = false, only where stats_big_optional): the lists stay as stage 1 left them, and the launch that runs stage 2
+    // draws whatever they hold.  An empty launch is a dependent launch boundary of 5.5-6.7 us whatever its grid (profiles/r06_big_wgs.txt).
+    if (!launch_big) return DSM_OK;
     KTimer tm(c, DSM_K_STATSBIG);
     // the deferred items (none once the chain has converged on data of ordinary depth: the launch then returns at once);
     // up to 16 workgroups per list = 4096 items of a list per round (a list one item longer than a round doubles the launch:
@@ -918,6 +941,8 @@ int k_stats_stage2(dsm_ctx *c, uint32_t iter)
     p.S = c->S; p.G = c->G; p.hmul = DSM_NTAB_HMUL; p.swz = DSM_NTAB_SWZ;
     p.k0 = (uint32_t)c->ctr_seed; p.k1 = (uint32_t)(c->ctr_seed >> 32); p.iter = iter;
     p.big_count = c->big_count;
+    stats_s2_lists(c, &p);
+    const S2Lists ls = {c->esum, c->S};                      // (G < 10: one workgroup per sample, each reads the deferred lists' counters)
     // 2^G subsets per sample at the root: 256 threads up to G = 9, 1024 above
     const int nthr = c->G >= 10 ? 1024 : 256;
     const bool v3 = stats_draw_version(stats_spec(c)) >= 3;          // (spec 4 draws with version 2's samplers)
@@ -936,11 +961,11 @@ int k_stats_stage2(dsm_ctx *c, uint32_t iter)
         p.scratch = c->s2_scratch; p.ticket = c->s2_scratch + (size_t)DSM_MAX_S * S2_TAB_ENTRIES;
     }
     if (g_batch.K == 0) {
-        if (v3) hipLaunchKernelGGL(stats_stage2_kernel<3>, dim3(c->S * p.nsplit), dim3(nthr), 0, c->stream, p, make_stage2_plan(c->G));
-        else hipLaunchKernelGGL(stats_stage2_kernel<2>, dim3(c->S * p.nsplit), dim3(nthr), 0, c->stream, p, make_stage2_plan(c->G));
+        if (v3) hipLaunchKernelGGL(stats_stage2_kernel<3>, dim3(c->S * p.nsplit), dim3(nthr), 0, c->stream, p, make_stage2_plan(c->G), ls);
+        else hipLaunchKernelGGL(stats_stage2_kernel<2>, dim3(c->S * p.nsplit), dim3(nthr), 0, c->stream, p, make_stage2_plan(c->G), ls);
     } else {
         static thread_local Stage2Batch acc;
-        acc.p[g_batch.k] = p;
+        acc.p[g_batch.k] = p; acc.ls[g_batch.k] = ls;
         if (g_batch.k == g_batch.K - 1) {
             acc.plan = make_stage2_plan(c->G);
             if (v3) hipLaunchKernelGGL(stats_stage2_kernel_b<3>, dim3(c->S, g_batch.K), dim3(nthr), 0, c->stream, acc);
@@ -952,10 +977,10 @@ int k_stats_stage2(dsm_ctx *c, uint32_t iter)
 }
 
 // A2 for the resident state: the aggregated pass (spec DSM_STATS_AGG = 2, or 3 when forced) where it applies, else the per-read pass (spec 1)
-int k_stats(dsm_ctx *c, uint32_t iter)
+int k_stats(dsm_ctx *c, uint32_t iter, bool launch_big)
 {
     if (stats_spec(c) >= 2) {
-        int r = k_stats_stage1(c, iter);
+        int r = k_stats_stage1(c, iter, launch_big);
         if (r != DSM_OK) return r;
         return k_stats_stage2(c, iter);
     }

@@ -624,6 +624,16 @@ int dsm_ctx_set_tau_screen(dsm_ctx *ctx, int on);
    chain's abundances hold such a haplotype (as set by dsm_ctx_set_state / left by the previous call, and looked at every 64 iterations); 0 = never; 1 = always.  The draws are those of the fp64 code
    either way (tests/test_gpu_parity.py); not used for batches and sharded chains. */
 int dsm_ctx_set_tau_neartie(dsm_ctx *ctx, int mode);
+/* stage 1 of the aggregated mu/E pass hands a few items (deep cells, burn-in states, chains that fit badly) to lists; a launch of its
+   own (stats_big_kernel) draws them, and where it was left out the launch that runs stage 2 does, the same draws bit for bit.  For
+   the full chain with G < 10 under specification 2 / 3, not sharded, the launch is a choice: mode -1 (default) = launched while the
+   lists were last seen non-empty (looked at when a Gibbs call ends and every 64 iterations inside one; the first call after
+   dsm_ctx_set_state / dsm_ctx_set_counts launches), 0 = never, 1 = always.  DESMAN_HIP_BIG_LAUNCH=0|1 chooses for every context
+   that has no mode of its own.  Everywhere else the launch is unconditional. */
+int dsm_ctx_set_big_launch(dsm_ctx *ctx, int mode);
+/* test hook: how many words of the deferred lists' counters are non-zero now (0 between passes), and the device's running count of
+   lists found non-empty */
+int dsm_ctx_debug_big_lists(dsm_ctx *ctx, int *nonzero, uint32_t *seen);
 /* workgroups one tau sweep of the resident shape launches, and how many of them the device holds at once (occupancy of the
    kernel x compute units): launched / resident = rounds of the launch, the partly filled last one being its tail */
 int dsm_ctx_tau_launch_info(dsm_ctx *ctx, int *launched, int *resident);
