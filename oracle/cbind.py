@@ -72,6 +72,9 @@ def lib():
         L.orc_stats_agg.argtypes = [_u8p, _f64p, _f64p, _i64p, C.c_int, C.c_int, C.c_int,
                                     C.c_uint64, C.c_uint32, _u64p, _u64p, C.c_void_p, C.c_int]
         L.orc_stats_agg.restype = C.c_int
+        L.orc_stats_kinds.argtypes = [_u8p, _f64p, _f64p, _i64p, C.c_int, C.c_int, C.c_int,
+                                      C.c_uint64, C.c_uint32, np.ctypeslib.ndpointer(np.int8, flags="C_CONTIGUOUS"), C.c_int]
+        L.orc_stats_kinds.restype = C.c_int
         L.orc_binom_test.argtypes = [C.c_int, C.c_uint32, C.c_double, C.c_double, C.c_uint64, C.c_int, _u32p, C.c_int]
         L.orc_mult4_test.argtypes = [C.c_uint32, _f64p, C.c_uint64, C.c_int, _u32p, C.c_int]
         L.orc_tlog.argtypes = [C.c_double]
@@ -272,6 +275,19 @@ def stats_agg(tau_idx, gamma, eta, variants, seed, it, want_ntab=False, spec=STA
     if rc != 0:
         raise ValueError("orc_stats_agg: G outside 1..16 or spec not 2 / 3")
     return (mu, E, nt) if want_ntab else (mu, E)
+
+
+def stats_kinds(tau_idx, gamma, eta, variants, seed, it, spec=STATS_AGG):
+    """int8 [V,S,4]: for every (position, sample, observed base) item of the pass stats_agg(..., seed, it, spec=spec) makes, the kind
+    under which the product's lean stage 1 hands it over (oracle/stats_agg.c: item_kind -- 0 rejection sampler, 1 long search,
+    2 search + two more binomials, the kind that depends on the draw) or -1 where stage 1 draws it itself.  spec 2 or 3."""
+    V, S, _ = variants.shape
+    G = tau_idx.shape[1]
+    kinds = np.empty((V, S, 4), dtype=np.int8)
+    rc = lib().orc_stats_kinds(tau_idx, np.ascontiguousarray(gamma), np.ascontiguousarray(eta), variants, V, G, S, int(seed), int(it), kinds, int(spec))
+    if rc != 0:
+        raise ValueError("orc_stats_kinds: G outside 1..16 or spec not 2 / 3")
+    return kinds
 
 
 def binom_test(kind, n, wa, wb, seed, nsamp, spec=STATS_AGG):

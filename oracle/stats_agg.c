@@ -396,6 +396,66 @@ int orc_stats_agg(const uint8_t *tau_idx, const double *gamma, const double *eta
     return 0;
 }
 
+/* Who draws an item, not what is drawn: the product's lean stage-1 kernel draws an item itself while the rarer outcome of its first
+ * binomial has a mean <= LEAN_CAP (DSM_LEAN_CAP) and that binomial leaves <= XS reads of the other bases; every other item it hands
+ * over to a consumer that runs mult4 above from the item's own stream.  The kind it hands an item over under (dsm_binom.h: s1_item,
+ * mult4<false>): 0 = the first binomial takes BTRS, 1 = a search with a mean in (LEAN_CAP, BINV_MEAN_CAP], 2 = the search was made
+ * and found more than XS reads of the other bases (two more binomials follow) -- the one kind that depends on the draw; -1 = drawn
+ * by stage 1 itself (or no reads).  Same operands and order as mult4 / binom. */
+#define LEAN_CAP 64.0
+
+static int item_kind(xo_t *rng, uint32_t x, const double W[4], int spec)
+{
+    if (x == 0) return -1;
+    int am = 0;
+    for (int a = 1; a < 4; a++) if (W[a] > W[am]) am = a;
+    int o[3], j = 0;
+    for (int a = 0; a < 4; a++) if (a != am) o[j++] = a;
+    const double ws = (W[o[0]] + W[o[1]]) + W[o[2]], wm = W[am];
+    if (!(ws > 0.0)) return -1;                                  /* binom: no read of another base */
+    uint32_t m = x;                                              /* binom: !(wm > 0) -> every read */
+    if (wm > 0.0) {
+        const double wsm = ws > wm ? wm : ws, wl = ws > wm ? ws : wm;
+        const double T = wsm + wl;
+        if ((double)x * wsm > LEAN_CAP * T) return (double)x * wsm > BINV_MEAN_CAP * T ? 0 : 1;
+        m = binom(rng, x, ws, wm, LEAN_CAP, spec);               /* (the same test inside: the search) */
+    }
+    return m > XS ? 2 : -1;
+}
+
+/* kinds [V][S][4] (position, sample, observed base) <- item_kind of every item of the pass orc_stats_agg(..., seed, iter, spec) makes:
+ * the same cells, weights and item streams as stage1 above.  Returns 0, or -1 if G / spec is out of range. */
+int orc_stats_kinds(const uint8_t *tau_idx, const double *gamma, const double *eta, const int64_t *variants,
+                    int V, int G, int S, uint64_t seed, uint32_t iter, int8_t *kinds, int spec)
+{
+    if (G < 1 || G > 16 || spec < 2 || spec > 3) return -1;
+    const uint32_t key[2] = { (uint32_t)seed, (uint32_t)(seed >> 32) };
+    for (int v = 0; v < V; v++) {
+        const uint8_t *tv = tau_idx + (size_t)v * G;
+        for (int s = 0; s < S; s++) {
+            const int64_t *x = variants + ((size_t)v * S + s) * 4;
+            const uint32_t cell = (uint32_t)((uint64_t)s * (uint64_t)V + (uint64_t)v);
+            uint32_t cctr[4] = { cell, 0u, iter, STREAM_STA1 }, cbase[4];
+            orc_philox4x32_10(cctr, key, cbase);
+            double Gam[4] = { 0.0, 0.0, 0.0, 0.0 };
+            for (int g = 0; g < G; g++) Gam[tv[g]] = Gam[tv[g]] + gamma[(size_t)s * G + g];
+            for (int b = 0; b < 4; b++) {
+                int8_t *out = kinds + ((size_t)v * S + s) * 4 + b;
+                *out = -1;
+                if (x[b] <= 0) continue;
+                double W[4];
+                for (int a = 0; a < 4; a++) W[a] = eta[a * 4 + b] * Gam[a];
+                const double Wt = ((W[0] + W[1]) + W[2]) + W[3];
+                if (!(Wt > 0.0)) for (int a = 0; a < 4; a++) W[a] = Gam[a];
+                xo_t rng;
+                item_seed(&rng, cbase, (uint32_t)b, key, spec);
+                *out = (int8_t)item_kind(&rng, (uint32_t)x[b], W, spec);
+            }
+        }
+    }
+    return 0;
+}
+
 /* test hooks: nsamp variates of one sampler, variate i from the stream Philox({i, 0, 0, 'TEST'}, seed) */
 void orc_binom_test(int kind, uint32_t n, double wa, double wb, uint64_t seed, int nsamp, uint32_t *out, int spec)
 {

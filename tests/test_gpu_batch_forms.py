@@ -35,13 +35,12 @@ from oracle import cbind
 
 import test_gpu_philox as tph
 from test_gpu_batch import _chain, _snapshot, _same
+from _deferred import first_rule, ntab_rep as _ntab_rep
 
 pytestmark = pytest.mark.gpu
 
 MT, PHILOX = _lib.RNG_MT19937, _lib.RNG_PHILOX
 MAX_BATCH = 8                   # DSM_MAX_BATCH
-LEAN_CAP = 64.0                 # DSM_LEAN_CAP: stage 1 defers an item whose rarer outcome has a mean above this
-BINV_MEAN_CAP = 128.0           # DSM_BINV_MEAN_CAP: ... onto the list of kind 0 (rejection sampler) above this, kind 1 (long search) below
 
 
 # ---------------------------------------------------------------- the dispatch rules, restated (test data, not kernel code)
@@ -69,17 +68,6 @@ def _agg_lpv(S):
         if -(-S // lpv) * lpv < -(-S // best) * best:
             best = lpv
     return best
-
-
-def _ntab_rep(V, S, G):
-    """kernels_stats.hip: stats_ntab_rep -- copies of the subset table"""
-    if 3.0 * V / (1 << G) <= 128.0:
-        return 1
-    lines = ((1 << G) * S * 4 + 63) // 64
-    rep = 2
-    while lines * rep < 384 and rep < 64 and 2 * rep * (1 << G) * S * 4 <= (64 << 20):
-        rep *= 2
-    return rep
 
 
 def _spec_run(asked, G):
@@ -371,24 +359,8 @@ def test_several_stage1_passes_per_wavefront(spec):
 
 
 def _deferred(counts, state, pooled=False):
-    """Lower bound on the items stage 1 defers from `state`, by the rule of dsm_binom.h (mult4 / s1_item): the item (cell, observed base b)
-    with count x and weights W[a] = eta[a, b] Gamma_a splits off the reads not of the heaviest base by one binomial, and is deferred
-    when x w > DSM_LEAN_CAP, w = the smaller side's share of the weight (kind 0 above DSM_BINV_MEAN_CAP, else kind 1; items that go
-    through and then find more than DSM_XS such reads are deferred too and not counted here).  pooled (spec 4): the counts of the
-    positions with one tau word are summed in the word's lowest position first.  Returns bool [entries, S, 4] x 2: deferred, of kind 0."""
-    tau, gamma, eta = state
-    x = counts
-    if pooled:
-        _, first, inv = np.unique(np.argmax(tau, axis=2), axis=0, return_index=True, return_inverse=True)
-        x = np.zeros((len(first),) + counts.shape[1:], dtype=np.int64)
-        np.add.at(x, inv.reshape(-1), counts)
-        tau = tau[first]
-    gam = np.einsum("sg,vga->vsa", gamma, tau.astype(np.float64))
-    W = eta[None, None, :, :] * gam[:, :, :, None]                # [v, s, true base a, observed base b]
-    T, wm = W.sum(axis=2), W.max(axis=2)
-    mean = x * np.minimum(T - wm, wm) / T
-    margin = 1.0 + 1e-9                                           # (the device sums the weights in another order)
-    return mean > LEAN_CAP * margin, mean > BINV_MEAN_CAP * margin
+    """bool [entries, S, 4] x 2: the items stage 1 defers from `state` by the mean of the rarer outcome (a lower bound), of kind 0"""
+    return first_rule(counts, *state, pooled=pooled)
 
 
 def _longest_sublist(deferred, kind0):

@@ -14,13 +14,14 @@ through, with stage 1's own rule (dsm_binom.h: s1_item -- x min(ws, wl) > 64 (ws
 import numpy as np
 import pytest
 
+from _deferred import handed_over as _handed_over
+
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(48, 5, 2), (64, 17, 3), (40, 64, 8), (32, 70, 4)]          # (32, 70, 4): S > 64
 SHALLOW, DEEP = 1.0, 40.0
 MIXED = ((64, 17, 3), 4.0, 0.7)                                        # shape, depth_scale, diagonal of the starting eta
 N_IT = 6
-LEAN_CAP = 64.0
 
 
 def _table(shape, scale, diag=0.96):
@@ -57,19 +58,6 @@ def _result(c):
 def _same(a, b, what):
     for k in a:
         assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), "%s: %s differs" % (what, k)
-
-
-def _handed_over(counts, tau, gamma, eta):
-    """items stage 1 hands over at this state by the mean of the rarer outcome (s1_item's first rule)"""
-    idx = tau.argmax(axis=2)                                             # [V, G]
-    onehot = (idx[:, :, None] == np.arange(4)[None, None, :]).astype(np.float64)     # [V, G, 4]
-    Gam = np.einsum("vga,sg->vsa", onehot, gamma)                        # [V, S, a]
-    W = Gam[:, :, :, None] * eta[None, None, :, :]                       # [V, S, a, b] = eta[a, b] Gamma_a
-    wm = W.max(axis=2)
-    T = W.sum(axis=2)
-    ws = np.minimum(wm, T - wm)
-    x = counts.astype(np.float64)
-    return int(np.count_nonzero((x > 0) & (x * ws > LEAN_CAP * T)))
 
 
 def _items_per_iteration(table):
