@@ -289,6 +289,18 @@ class HaploSNP_Sampler:
         res = self._assign(assignMatrix, None)
         return dict(tau=self._onehot(res["map_state"]), conf=res["conf"], logz=res["logz"], marg=res["marg"])
 
+    def assignTauSampled(self, assignMatrix, kept=_lib.SAMPLED_KEPT, burn=_lib.SAMPLED_BURN, seed=None):
+        """the same posterior by four private Gibbs chains per position (every G <= 32): dict of tau [N,G,4]
+        (one-hot polished best state), map_ll, conf (Monte-Carlo), marg [N,G,4] (Rao-Blackwellised), spread [N] (the chains'
+        disagreement: large where they sit in different modes) and draw [N,G,4].  seed=None: one randint of the sampler's randomState."""
+        if seed is None:
+            seed = int(self.randomState.randint(0, 2 ** 31 - 1))
+        a = np.asarray(assignMatrix)
+        counts = np.ascontiguousarray(np.reshape(a, (a.shape[0], self.S, 4)), dtype=np.int64)
+        res = _lib.assign_tau_sampled(counts, self.gamma_star, self.eta_star, seed=seed, burn=burn, kept=kept, device=self._device)
+        return dict(tau=self._onehot(res["map_state"]), map_ll=res["map_ll"], conf=res["conf"], marg=res["marg"], spread=res["spread"],
+                    draw=self._onehot(res["draw_state"]))
+
     # ---- samples that were not in the fit (no counterpart upstream; DESIGN.md sec. 8b)
     def fitGamma(self, snps=None, tau=None, eta=None, presence=False, max_iter=_lib.FIT_MAX_ITER, tol=_lib.FIT_TOL):
         """maximum-likelihood abundances with the haplotypes and the error matrix held fixed: a dict of gamma [S',G], loglik, deviance,

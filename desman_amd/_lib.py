@@ -130,6 +130,10 @@ SIGNATURES = {
     "dsm_assign_tau": (_i, [_i, _i64p, _i, _i, _i, _f64p, _f64p, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "dsm_ctx_assign_tau": (_i, [_vp, _f64p, _f64p, _i, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "dsm_assign_debug_set_chunk": (_i, [_i]),
+    "dsm_assign_tau_sampled": (_i, [_i, _i64p, _i, _i, _i, _f64p, _f64p, C.c_uint64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dsm_ctx_assign_tau_sampled": (_i, [_vp, _f64p, _f64p, _i, C.c_uint64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dsm_assign_sampled_debug_set_chunk": (_i, [_i]),
+    "dsm_assign_sampled_debug_path": (_i, [_i, _i, C.POINTER(_i)]),
     "dsm_fit_gamma": (_i, [_i, _i64p, _i, _i, _i, _i64p, _f64p, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dsm_ctx_fit_gamma": (_i, [_vp, _i, _vp, _f64p, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dsm_abund_debug_set_chunk": (_i, [_i]),
@@ -278,6 +282,59 @@ def assign_tau(counts, gamma, eta, seed=None, device=0):
 def assign_debug_set_chunk(positions=0):
     """test hook: positions per launch of assign_tau / Context.assign_tau (0 = the default bound); results do not depend on it"""
     check(load().dsm_assign_debug_set_chunk(int(positions)))
+
+
+SAMPLED_KEPT, SAMPLED_BURN = 100, 20    # conventions of `desman-assign --sampled`, not tuned
+SAMPLED_OPTIONAL = ("map_ll", "conf", "spread", "draw_state")
+
+
+def _assign_sampled_out(N, G, want):
+    """the output arrays of the sampled call; ``want`` names the optional ones (None: all of them)"""
+    want = SAMPLED_OPTIONAL if want is None else tuple(want)
+    bad = [k for k in want if k not in SAMPLED_OPTIONAL]
+    if bad:
+        raise ValueError("assign_tau_sampled: unknown optional output %r" % bad[0])
+    out = dict(map_state=np.zeros((N, G), dtype=np.uint8), marg=np.zeros((N, G, 4)))
+    for k in want:
+        out[k] = np.zeros((N, G), dtype=np.uint8) if k == "draw_state" else np.zeros(N)
+    return out
+
+
+def _sweeps(burn, kept):
+    burn, kept = int(burn), int(kept)
+    if not (-2 ** 31 <= burn < 2 ** 31 and -2 ** 31 <= kept < 2 ** 31):
+        raise ValueError("assign_tau_sampled: burn / kept outside the int range")
+    return burn, kept
+
+
+def assign_tau_sampled(counts, gamma, eta, seed=0, burn=SAMPLED_BURN, kept=SAMPLED_KEPT, want=None, device=0):
+    """Sampled joint assignment of the positions ``counts`` [N,S,4] under fitted gamma [S,G], eta [4,4] (dsm_assign_tau_sampled;
+    G <= 32): four private Gibbs chains per position, ``burn`` + ``kept`` sweeps each.  A dict of map_state [N,G] uint8, marg
+    [N,G,4] and the optional outputs named by ``want`` (default all): map_ll [N], conf [N], spread [N], draw_state [N,G]."""
+    x = np.ascontiguousarray(counts, dtype=np.int64)
+    if x.ndim != 3 or x.shape[2] != 4:
+        raise ValueError("assign_tau_sampled: counts must be [N,S,4]")
+    N, S = x.shape[0], x.shape[1]
+    gamma, eta = _assign_model(gamma, eta, S)
+    G = gamma.shape[1]
+    burn, kept = _sweeps(burn, kept)
+    out = _assign_sampled_out(N, G, want)
+    check(load().dsm_assign_tau_sampled(int(device), x, N, S, G, gamma, eta, int(seed) & 0xFFFFFFFFFFFFFFFF, burn, kept,
+                                        _ptr(out["map_state"]), _ptr(out.get("map_ll")), _ptr(out.get("conf")), _ptr(out["marg"]),
+                                        _ptr(out.get("spread")), _ptr(out.get("draw_state"))))
+    return out
+
+
+def assign_sampled_debug_set_chunk(positions=0):
+    """test hook: positions per launch of assign_tau_sampled / Context.assign_tau_sampled (0 = the default bound)"""
+    check(load().dsm_assign_sampled_debug_set_chunk(int(positions)))
+
+
+def assign_sampled_debug_path(S, G):
+    """test hook: the path a shape takes -- dict of inst, lpv, nsl, gamma_chunk, positions_per_workgroup; nothing is launched"""
+    out = (C.c_int * 5)()
+    check(load().dsm_assign_sampled_debug_path(int(S), int(G), out))
+    return dict(zip(("inst", "lpv", "nsl", "gamma_chunk", "positions_per_workgroup"), [int(v) for v in out]))
 
 
 def diag_debug_set_parts(parts=0):
@@ -557,6 +614,17 @@ class Context:
         out = _assign_out(self.V, G, seed)
         check(self.lib.dsm_ctx_assign_tau(self._h, gamma, eta, G, int(seed or 0) & 0xFFFFFFFFFFFFFFFF, _ptr(out["map_state"]),
                                           _ptr(out["conf"]), _ptr(out["logz"]), _ptr(out["marg"]), _ptr(out.get("draw_state"))))
+        return out
+
+    def assign_tau_sampled(self, gamma, eta, seed=0, burn=SAMPLED_BURN, kept=SAMPLED_KEPT, want=None):
+        """assign_tau_sampled() of the module on the count tensor resident in this context; the chain state is not touched"""
+        gamma, eta = _assign_model(gamma, eta, self.S)
+        G = gamma.shape[1]
+        burn, kept = _sweeps(burn, kept)
+        out = _assign_sampled_out(self.V, G, want)
+        check(self.lib.dsm_ctx_assign_tau_sampled(self._h, gamma, eta, G, int(seed) & 0xFFFFFFFFFFFFFFFF, burn, kept,
+                                                  _ptr(out["map_state"]), _ptr(out.get("map_ll")), _ptr(out.get("conf")),
+                                                  _ptr(out["marg"]), _ptr(out.get("spread")), _ptr(out.get("draw_state"))))
         return out
 
     def fit_gamma(self, eta, tau=None, max_iter=FIT_MAX_ITER, tol=FIT_TOL, presence=False):

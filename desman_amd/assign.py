@@ -1,6 +1,7 @@
 """`desman-assign`: haplotype calls for positions that were not in a fit, from the fit's result files.
 
     python -m desman_amd.assign <run_dir> <positions.freq> [-o DIR] [--mean] [--draw] [--seed N] [--device N]
+                                [--sampled [T]] [--burn B]
 
 The reference reserves `desman -a` for this (bin/desman:209-240, HaploSNP_Sampler.assignTau) but the branch is dead upstream and
 its 4^G Python loops are unusable above G ~ 5; `desman -a` stays rejected here (desman_amd/cli.py).  This entry point needs no
@@ -13,6 +14,15 @@ states of every position on the GPU (include/desman_hip.h: dsm_assign_tau, G <= 
     Assigned_Tau_conf.csv   index = contig, Position, column 0 = posterior probability of the MAP state (the reference's conf)
     Assigned_Tau_mean.csv   the exact marginals P(tau_vg = a), layout of Tau_Mean.csv
     assign_fit.txt          Assign,<G>,<N>,<sum of the positions' log normalisers>
+
+With ``--sampled [T]`` every G <= 32 is accepted: each position runs four private Gibbs chains of B burn-in and T kept sweeps on the
+GPU (dsm_assign_tau_sampled), keyed by ``--seed``.  The three tables keep their layout -- the MAP state is the
+best state any chain saw, polished by coordinate ascent (``--draw``: chain 0's last state), conf the share of the kept end-of-sweep
+states equal to it, the marginals Rao-Blackwellised means -- and there are
+
+    Assigned_Tau_spread.csv index = contig, Position, column 0 = the largest disagreement between the four chains' own marginals:
+                            large where the chains sit in different modes (two haplotypes of near-equal abundance with swapped bases)
+    assign_fit.txt          AssignSampled,<G>,<N>,<B>,<T>,<sum of the MAP states' log-likelihoods>
 """
 import argparse
 import os
@@ -24,6 +34,14 @@ import pandas as pd
 from .Output_Results import _table_bytes, rchop
 
 DRAW_SEED = 23724839        # default --seed: the default sampler seed of `desman` (bin/desman:51)
+SAMPLED_KEPT, SAMPLED_BURN = 100, 20    # --sampled / --burn: conventions, not tuned (desman_amd/_lib.py has the same pair)
+SAMPLED_MAX_G = 32          # DSM_MAX_G
+SPREAD_HIGH = 0.1           # the log line counts the positions above it: a convention for that line only, like check.Z_HIGH
+
+
+# where the sampled form becomes the cheaper one: measured on the MI355X at S = 64, N = 10 000 ("Measurement")
+SAMPLED_CHEAPER = ("At the default sweeps it is the cheaper form from G = 8 (measured at S = 64: 2.9 times faster than the exact call at "
+                   "G = 8, 38 times at G = 10, 3 times slower at G = 6).")
 
 
 def build_parser():
@@ -34,7 +52,12 @@ def build_parser():
     ap.add_argument("-o", "--output_dir", type=str, default=None, help="directory for the result files (default: run_dir)")
     ap.add_argument("--mean", action="store_true", help="use Gamma_mean.csv / Eta_mean.csv instead of the MAP sample's files")
     ap.add_argument("--draw", action="store_true", help="write one posterior draw per position instead of the MAP state")
-    ap.add_argument("--seed", type=int, default=DRAW_SEED, help="seed of --draw")
+    ap.add_argument("--seed", type=int, default=DRAW_SEED, help="seed of --draw; with --sampled the key of the chains")
+    ap.add_argument("--sampled", type=int, nargs="?", const=SAMPLED_KEPT, default=None, metavar="T",
+                    help="four private Gibbs chains per position with T kept sweeps (default %d: a convention, not tuned) instead of "
+                         "all 4^G states: any G <= %d.  %s" % (SAMPLED_KEPT, SAMPLED_MAX_G, SAMPLED_CHEAPER))
+    ap.add_argument("--burn", type=int, default=None, metavar="B",
+                    help="burn-in sweeps of --sampled (default %d: a convention, not tuned)" % SAMPLED_BURN)
     ap.add_argument("--device", type=int, default=0, help="GPU ordinal")
     return ap
 
@@ -103,18 +126,49 @@ def write_results(out_dir, names, positions, res, draw=False):
         fh.write("Assign,%d,%d,%f\n" % (G, N, float(np.sum(res["logz"]))))
 
 
+def write_sampled_results(out_dir, names, positions, res, burn, kept, draw=False):
+    os.makedirs(out_dir, exist_ok=True)
+    state = res["draw_state"] if draw else res["map_state"]
+    N, G = state.shape
+    write_table(os.path.join(out_dir, "Assigned_Tau_star.csv"), onehot(state), names, positions)
+    for key, fname in (("conf", "Assigned_Tau_conf.csv"), ("spread", "Assigned_Tau_spread.csv")):
+        frame = pd.DataFrame(res[key], index=names)
+        frame['Position'] = np.asarray(positions)
+        order = frame.columns.tolist()
+        frame[order[-1:] + order[:-1]].to_csv(os.path.join(out_dir, fname))
+    write_table(os.path.join(out_dir, "Assigned_Tau_mean.csv"), res["marg"], names, positions)
+    with open(os.path.join(out_dir, "assign_fit.txt"), "w") as fh:
+        fh.write("AssignSampled,%d,%d,%d,%d,%f\n" % (G, N, burn, kept, float(np.sum(res["map_ll"]))))
+
+
 def main(argv=None):
     opts = build_parser().parse_args(argv)
+    if opts.burn is not None and opts.sampled is None:
+        sys.exit("desman-assign: --burn needs --sampled")
+    if opts.sampled is not None:
+        burn = SAMPLED_BURN if opts.burn is None else opts.burn
+        if opts.sampled < 1 or burn < 0 or opts.sampled + burn > 65536:
+            sys.exit("desman-assign: --sampled T --burn B need T >= 1, B >= 0 and B + T <= 65536")
     names, gamma, eta = load_model(opts.run_dir, opts.mean)
     if not os.path.isfile(opts.freq_file):
         sys.exit("desman-assign: can't open '%s'" % opts.freq_file)
     table = pd.read_csv(opts.freq_file, header=0, index_col=0)
     counts = map_samples(table, names)
+    out_dir, row_names, positions = opts.output_dir or opts.run_dir, [str(n) for n in table.index.tolist()], table['Position'].to_numpy()
+    if opts.sampled is not None and gamma.shape[1] > SAMPLED_MAX_G:
+        sys.exit("desman-assign: %d haplotypes; the limit of --sampled is G = %d" % (gamma.shape[1], SAMPLED_MAX_G))
     from . import _lib                                                      # nothing above needs the library or a GPU
+    if opts.sampled is not None:
+        res = _lib.assign_tau_sampled(counts, gamma, eta, seed=opts.seed, burn=burn, kept=opts.sampled, device=opts.device)
+        write_sampled_results(out_dir, row_names, positions, res, burn, opts.sampled, opts.draw)
+        print("desman-assign --sampled: %d of %d positions with spread > %.1f (chains in different modes)"
+              % (int(np.sum(res["spread"] > SPREAD_HIGH)), len(res["spread"]), SPREAD_HIGH), file=sys.stderr)
+        return res
     if gamma.shape[1] > _lib.ASSIGN_MAX_G:
-        sys.exit("desman-assign: %d haplotypes; all 4^G joint states are evaluated, the limit is G = %d" % (gamma.shape[1], _lib.ASSIGN_MAX_G))
+        sys.exit("desman-assign: %d haplotypes; all 4^G joint states are evaluated, the limit is G = %d (--sampled runs to G = %d)"
+                 % (gamma.shape[1], _lib.ASSIGN_MAX_G, SAMPLED_MAX_G))
     res = _lib.assign_tau(counts, gamma, eta, seed=opts.seed if opts.draw else None, device=opts.device)
-    write_results(opts.output_dir or opts.run_dir, [str(n) for n in table.index.tolist()], table['Position'].to_numpy(), res, opts.draw)
+    write_results(out_dir, row_names, positions, res, opts.draw)
     return res
 
 

@@ -11,6 +11,7 @@
 #define DSM_STREAM_STATS 0x53544154u   // 'STAT'  mu/E per-read draws
 #define DSM_STREAM_DIRI  0x44495249u   // 'DIRI'  gamma / eta Dirichlet draws
 #define DSM_STREAM_TAUU  0x54415555u   // 'TAUU'  tau-sweep uniforms (Philox mode)
+#define DSM_STREAM_ASMP  0x41534D50u   // 'ASMP'  dsm_assign_tau_sampled: chain c of a position draws from stream 'ASMP' + c
 
 #define DSM_EPS 2.220446049250313e-16
 

@@ -393,6 +393,37 @@ int dsm_ctx_assign_tau(dsm_ctx *ctx, const double *gamma, const double *eta, int
 /* test hook: positions per launch of the two calls above (0 = by the scratch bound, the default) */
 int dsm_assign_debug_set_chunk(int positions);
 
+/* Sampled joint assignment: the model of dsm_assign_tau for every G <= DSM_MAX_G.  Each position runs four
+ * private Gibbs chains over its G sites; chain c starts at "every haplotype = base c", runs burn + kept sweeps over g = 0 .. G-1 and
+ * keeps the last `kept`.  A step forms the rest mixture afresh, the four candidate totals L_a (the L of the whole state with
+ * a_g = a) in fp64, q_a = exp(L_a - max) / sum, and draws by inverse CDF over a = 0..3 with u = word 0 / 2^32 of Philox4x32-10,
+ * key = (lo32, hi32) of seed, counter = (lo32 i, hi32 i, sweep, 'ASMP' + c), i = (position index within the call) G + g.  A step whose
+ * four candidates are all -inf keeps its base (q = 0) and still spends its uniform.  Host pointers (spread, conf, map_ll and
+ * draw_state may be NULL):
+ *     map_state [N][G]    digits 0..3 of the best state seen at any step of any chain (ties: lowest chain, earliest step), polished by
+ *                         coordinate ascent (arg-max candidate per site; ties keep the base, else the lowest a; at most 64 sweeps)
+ *     map_ll    [N]       L of map_state
+ *     conf      [N]       share of the 4 * kept end-of-sweep states equal to map_state: a Monte-Carlo estimate of dsm_assign_tau's conf
+ *     marg      [N][G][4] mean of q_a over the four chains and the kept sweeps (Rao-Blackwellised marginals)
+ *     spread    [N]       max over (g, a) of the largest minus the smallest of the four chains' own means: large where the chains sit
+ *                         in different modes (single-site moves do not cross swapped bases of two haplotypes with near-equal gamma)
+ *     draw_state[N][G]    chain 0's state after the last sweep
+ * A position whose best L is -inf: map_state = draw_state = 0..0, conf = marg = spread = 0, map_ll = -inf.  Nothing is ever NaN.
+ * Limits: 1 <= G <= DSM_MAX_G, S <= DSM_MAX_S, burn + kept <= 65536 (DSM_ERR_UNSUPPORTED above); kept >= 1, burn >= 0, counts as
+ * dsm_ctx_set_counts takes them, gamma and eta finite and >= 0 (DSM_ERR_ARG otherwise).  Device scratch stays below ~40 MB whatever
+ * N is.  The results depend on (seed, position index within the call, counts, gamma, eta, burn, kept) alone -- not on the chunking,
+ * on scheduling or on the entry point; two calls give the same bits.                                                             */
+int dsm_assign_tau_sampled(int device, const int64_t *counts /*[N][S][4]*/, int N, int S, int G, const double *gamma,
+                           const double *eta, uint64_t seed, int burn, int kept, uint8_t *map_state, double *map_ll, double *conf,
+                           double *marg, double *spread, uint8_t *draw_state);
+int dsm_ctx_assign_tau_sampled(dsm_ctx *ctx, const double *gamma, const double *eta, int G, uint64_t seed, int burn, int kept,
+                               uint8_t *map_state, double *map_ll, double *conf, double *marg, double *spread, uint8_t *draw_state);
+/* test hooks: positions per launch of the two calls above (0 = by the scratch bound); the path of a shape, nothing launched --
+ * out[5] = instantiation (2 log2 NSL + 1 where gamma is staged in chunks), lanes per (position, chain), sample slots per lane,
+ * haplotypes per staged chunk of gamma, positions per workgroup */
+int dsm_assign_sampled_debug_set_chunk(int positions);
+int dsm_assign_sampled_debug_path(int S, int G, int *out);
+
 /* Abundances of the fitted haplotypes in samples that were not in the fit: tau and eta are held fixed, every
  * sample's gamma row is the maximiser of its own log-likelihood
  *     L(gamma) = sum_{v,b} x_vb ln sum_g gamma_g eta[tau_vg][b]        (cells with x = 0 contribute exactly 0, as in dsm_assign_tau),
