@@ -289,15 +289,17 @@ class HaploSNP_Sampler:
         res = self._assign(assignMatrix, None)
         return dict(tau=self._onehot(res["map_state"]), conf=res["conf"], logz=res["logz"], marg=res["marg"])
 
-    def assignTauSampled(self, assignMatrix, kept=_lib.SAMPLED_KEPT, burn=_lib.SAMPLED_BURN, seed=None):
+    def assignTauSampled(self, assignMatrix, kept=_lib.SAMPLED_KEPT, burn=_lib.SAMPLED_BURN, seed=None, pair_every=0):
         """the same posterior by four private Gibbs chains per position (every G <= 32): dict of tau [N,G,4]
         (one-hot polished best state), map_ll, conf (Monte-Carlo), marg [N,G,4] (Rao-Blackwellised), spread [N] (the chains'
-        disagreement: large where they sit in different modes) and draw [N,G,4].  seed=None: one randint of the sampler's randomState."""
+        disagreement: large where they sit in different modes) and draw [N,G,4].  seed=None: one randint of the sampler's randomState.
+        pair_every = E > 0: joint moves of two haplotypes after every E-th sweep and in the polish (0: single-site moves only)."""
         if seed is None:
             seed = int(self.randomState.randint(0, 2 ** 31 - 1))
         a = np.asarray(assignMatrix)
         counts = np.ascontiguousarray(np.reshape(a, (a.shape[0], self.S, 4)), dtype=np.int64)
-        res = _lib.assign_tau_sampled(counts, self.gamma_star, self.eta_star, seed=seed, burn=burn, kept=kept, device=self._device)
+        res = _lib.assign_tau_sampled(counts, self.gamma_star, self.eta_star, seed=seed, burn=burn, kept=kept, device=self._device,
+                                      pair_every=pair_every)
         return dict(tau=self._onehot(res["map_state"]), map_ll=res["map_ll"], conf=res["conf"], marg=res["marg"], spread=res["spread"],
                     draw=self._onehot(res["draw_state"]))
 

@@ -132,6 +132,8 @@ SIGNATURES = {
     "dsm_assign_debug_set_chunk": (_i, [_i]),
     "dsm_assign_tau_sampled": (_i, [_i, _i64p, _i, _i, _i, _f64p, _f64p, C.c_uint64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dsm_ctx_assign_tau_sampled": (_i, [_vp, _f64p, _f64p, _i, C.c_uint64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dsm_assign_tau_sampled_pairs": (_i, [_i, _i64p, _i, _i, _i, _f64p, _f64p, C.c_uint64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dsm_ctx_assign_tau_sampled_pairs": (_i, [_vp, _f64p, _f64p, _i, C.c_uint64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dsm_assign_sampled_debug_set_chunk": (_i, [_i]),
     "dsm_assign_sampled_debug_path": (_i, [_i, _i, C.POINTER(_i)]),
     "dsm_fit_gamma": (_i, [_i, _i64p, _i, _i, _i, _i64p, _f64p, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -285,6 +287,7 @@ def assign_debug_set_chunk(positions=0):
 
 
 SAMPLED_KEPT, SAMPLED_BURN = 100, 20    # conventions of `desman-assign --sampled`, not tuned
+SAMPLED_PAIRS = 5                       # a bare `--pairs`: a pair pass after every fifth sweep -- a convention too, not tuned
 SAMPLED_OPTIONAL = ("map_ll", "conf", "spread", "draw_state")
 
 
@@ -300,28 +303,30 @@ def _assign_sampled_out(N, G, want):
     return out
 
 
-def _sweeps(burn, kept):
-    burn, kept = int(burn), int(kept)
-    if not (-2 ** 31 <= burn < 2 ** 31 and -2 ** 31 <= kept < 2 ** 31):
-        raise ValueError("assign_tau_sampled: burn / kept outside the int range")
-    return burn, kept
+def _sweeps(burn, kept, pair_every=0):
+    burn, kept, pair_every = int(burn), int(kept), int(pair_every)
+    if not all(-2 ** 31 <= v < 2 ** 31 for v in (burn, kept, pair_every)):
+        raise ValueError("assign_tau_sampled: burn / kept / pair_every outside the int range")
+    return burn, kept, pair_every
 
 
-def assign_tau_sampled(counts, gamma, eta, seed=0, burn=SAMPLED_BURN, kept=SAMPLED_KEPT, want=None, device=0):
+def assign_tau_sampled(counts, gamma, eta, seed=0, burn=SAMPLED_BURN, kept=SAMPLED_KEPT, want=None, device=0, pair_every=0):
     """Sampled joint assignment of the positions ``counts`` [N,S,4] under fitted gamma [S,G], eta [4,4] (dsm_assign_tau_sampled;
     G <= 32): four private Gibbs chains per position, ``burn`` + ``kept`` sweeps each.  A dict of map_state [N,G] uint8, marg
-    [N,G,4] and the optional outputs named by ``want`` (default all): map_ll [N], conf [N], spread [N], draw_state [N,G]."""
+    [N,G,4] and the optional outputs named by ``want`` (default all): map_ll [N], conf [N], spread [N], draw_state [N,G].
+    ``pair_every`` = E > 0: every E-th sweep is followed by a pass of joint moves of two haplotypes, and the polish climbs over pairs
+    as well (dsm_assign_tau_sampled_pairs); 0: single-site moves only."""
     x = np.ascontiguousarray(counts, dtype=np.int64)
     if x.ndim != 3 or x.shape[2] != 4:
         raise ValueError("assign_tau_sampled: counts must be [N,S,4]")
     N, S = x.shape[0], x.shape[1]
     gamma, eta = _assign_model(gamma, eta, S)
     G = gamma.shape[1]
-    burn, kept = _sweeps(burn, kept)
+    burn, kept, pair_every = _sweeps(burn, kept, pair_every)
     out = _assign_sampled_out(N, G, want)
-    check(load().dsm_assign_tau_sampled(int(device), x, N, S, G, gamma, eta, int(seed) & 0xFFFFFFFFFFFFFFFF, burn, kept,
-                                        _ptr(out["map_state"]), _ptr(out.get("map_ll")), _ptr(out.get("conf")), _ptr(out["marg"]),
-                                        _ptr(out.get("spread")), _ptr(out.get("draw_state"))))
+    check(load().dsm_assign_tau_sampled_pairs(int(device), x, N, S, G, gamma, eta, int(seed) & 0xFFFFFFFFFFFFFFFF, burn, kept, pair_every,
+                                              _ptr(out["map_state"]), _ptr(out.get("map_ll")), _ptr(out.get("conf")), _ptr(out["marg"]),
+                                              _ptr(out.get("spread")), _ptr(out.get("draw_state"))))
     return out
 
 
@@ -616,15 +621,15 @@ class Context:
                                           _ptr(out["conf"]), _ptr(out["logz"]), _ptr(out["marg"]), _ptr(out.get("draw_state"))))
         return out
 
-    def assign_tau_sampled(self, gamma, eta, seed=0, burn=SAMPLED_BURN, kept=SAMPLED_KEPT, want=None):
+    def assign_tau_sampled(self, gamma, eta, seed=0, burn=SAMPLED_BURN, kept=SAMPLED_KEPT, want=None, pair_every=0):
         """assign_tau_sampled() of the module on the count tensor resident in this context; the chain state is not touched"""
         gamma, eta = _assign_model(gamma, eta, self.S)
         G = gamma.shape[1]
-        burn, kept = _sweeps(burn, kept)
+        burn, kept, pair_every = _sweeps(burn, kept, pair_every)
         out = _assign_sampled_out(self.V, G, want)
-        check(self.lib.dsm_ctx_assign_tau_sampled(self._h, gamma, eta, G, int(seed) & 0xFFFFFFFFFFFFFFFF, burn, kept,
-                                                  _ptr(out["map_state"]), _ptr(out.get("map_ll")), _ptr(out.get("conf")),
-                                                  _ptr(out["marg"]), _ptr(out.get("spread")), _ptr(out.get("draw_state"))))
+        check(self.lib.dsm_ctx_assign_tau_sampled_pairs(self._h, gamma, eta, G, int(seed) & 0xFFFFFFFFFFFFFFFF, burn, kept, pair_every,
+                                                        _ptr(out["map_state"]), _ptr(out.get("map_ll")), _ptr(out.get("conf")),
+                                                        _ptr(out["marg"]), _ptr(out.get("spread")), _ptr(out.get("draw_state"))))
         return out
 
     def fit_gamma(self, eta, tau=None, max_iter=FIT_MAX_ITER, tol=FIT_TOL, presence=False):

@@ -1,7 +1,7 @@
 """`desman-assign`: haplotype calls for positions that were not in a fit, from the fit's result files.
 
     python -m desman_amd.assign <run_dir> <positions.freq> [-o DIR] [--mean] [--draw] [--seed N] [--device N]
-                                [--sampled [T]] [--burn B]
+                                [--sampled [T]] [--burn B] [--pairs [E]]
 
 The reference reserves `desman -a` for this (bin/desman:209-240, HaploSNP_Sampler.assignTau) but the branch is dead upstream and
 its 4^G Python loops are unusable above G ~ 5; `desman -a` stays rejected here (desman_amd/cli.py).  This entry point needs no
@@ -23,6 +23,10 @@ states equal to it, the marginals Rao-Blackwellised means -- and there are
     Assigned_Tau_spread.csv index = contig, Position, column 0 = the largest disagreement between the four chains' own marginals:
                             large where the chains sit in different modes (two haplotypes of near-equal abundance with swapped bases)
     assign_fit.txt          AssignSampled,<G>,<N>,<B>,<T>,<sum of the MAP states' log-likelihoods>
+
+``--pairs [E]`` adds joint moves of two haplotypes to ``--sampled``: every E-th sweep is followed by a pass that redraws the bases of
+every pair of haplotypes from their 16-state conditional, and the polish climbs over pairs as well, so swapped bases of two
+haplotypes are one step apart (dsm_assign_tau_sampled_pairs).  The files keep their names and formats.
 """
 import argparse
 import os
@@ -35,6 +39,7 @@ from .Output_Results import _table_bytes, rchop
 
 DRAW_SEED = 23724839        # default --seed: the default sampler seed of `desman` (bin/desman:51)
 SAMPLED_KEPT, SAMPLED_BURN = 100, 20    # --sampled / --burn: conventions, not tuned (desman_amd/_lib.py has the same pair)
+SAMPLED_PAIRS = 5           # a bare --pairs: a pair pass after every fifth sweep -- a convention, not tuned (_lib.SAMPLED_PAIRS)
 SAMPLED_MAX_G = 32          # DSM_MAX_G
 SPREAD_HIGH = 0.1           # the log line counts the positions above it: a convention for that line only, like check.Z_HIGH
 
@@ -58,6 +63,10 @@ def build_parser():
                          "all 4^G states: any G <= %d.  %s" % (SAMPLED_KEPT, SAMPLED_MAX_G, SAMPLED_CHEAPER))
     ap.add_argument("--burn", type=int, default=None, metavar="B",
                     help="burn-in sweeps of --sampled (default %d: a convention, not tuned)" % SAMPLED_BURN)
+    ap.add_argument("--pairs", type=int, nargs="?", const=SAMPLED_PAIRS, default=None, metavar="E",
+                    help="with --sampled: a pass of joint moves of two haplotypes after every E-th sweep (default %d: a convention, not "
+                         "tuned) and in the polish; crosses swapped bases of two haplotypes, costs about 2 (G - 1) / E more time"
+                         % SAMPLED_PAIRS)
     ap.add_argument("--device", type=int, default=0, help="GPU ordinal")
     return ap
 
@@ -145,6 +154,10 @@ def main(argv=None):
     opts = build_parser().parse_args(argv)
     if opts.burn is not None and opts.sampled is None:
         sys.exit("desman-assign: --burn needs --sampled")
+    if opts.pairs is not None and opts.sampled is None:
+        sys.exit("desman-assign: --pairs needs --sampled")
+    if opts.pairs is not None and not 0 <= opts.pairs <= 65536:
+        sys.exit("desman-assign: --pairs E needs 0 <= E <= 65536")
     if opts.sampled is not None:
         burn = SAMPLED_BURN if opts.burn is None else opts.burn
         if opts.sampled < 1 or burn < 0 or opts.sampled + burn > 65536:
@@ -159,7 +172,8 @@ def main(argv=None):
         sys.exit("desman-assign: %d haplotypes; the limit of --sampled is G = %d" % (gamma.shape[1], SAMPLED_MAX_G))
     from . import _lib                                                      # nothing above needs the library or a GPU
     if opts.sampled is not None:
-        res = _lib.assign_tau_sampled(counts, gamma, eta, seed=opts.seed, burn=burn, kept=opts.sampled, device=opts.device)
+        res = _lib.assign_tau_sampled(counts, gamma, eta, seed=opts.seed, burn=burn, kept=opts.sampled, device=opts.device,
+                                      pair_every=opts.pairs or 0)
         write_sampled_results(out_dir, row_names, positions, res, burn, opts.sampled, opts.draw)
         print("desman-assign --sampled: %d of %d positions with spread > %.1f (chains in different modes)"
               % (int(np.sum(res["spread"] > SPREAD_HIGH)), len(res["spread"]), SPREAD_HIGH), file=sys.stderr)

@@ -12,6 +12,7 @@
 #define DSM_STREAM_DIRI  0x44495249u   // 'DIRI'  gamma / eta Dirichlet draws
 #define DSM_STREAM_TAUU  0x54415555u   // 'TAUU'  tau-sweep uniforms (Philox mode)
 #define DSM_STREAM_ASMP  0x41534D50u   // 'ASMP'  dsm_assign_tau_sampled: chain c of a position draws from stream 'ASMP' + c
+#define DSM_STREAM_APAR  0x41504152u   // 'APAR'  dsm_assign_tau_sampled_pairs: the pair steps of chain c draw from stream 'APAR' + c
 
 #define DSM_EPS 2.220446049250313e-16
 

@@ -25,8 +25,27 @@
 //     of q sit in LDS ([group][g][a], added to by lane 0 of the group) and meet in chain order at the end.
 //   * the kept end-of-sweep states go to device scratch [position][chain][T]; after the polish every group counts its own chain's.
 //   * every loop bound is workgroup-uniform (the polish runs until no position of the workgroup is active; a finished position is
-//     frozen), so the barriers of the chunked staging are safe.
+//     frozen), and a decision that only a chain shares (a step whose candidates are all -inf) skips no code that stages gamma, so
+//     the barriers of the chunked staging are safe.
 // Every sum runs in a fixed order, there are no atomics: the results depend on (seed, position index, counts, gamma, eta, B, T) only.
+//
+// Pair moves (PAIRS = true; dsm_assign_tau_sampled_pairs with pair_every = E > 0; E = 0 launches the PAIRS = false code above): sweep t
+// is followed by a pair pass when (t + 1) mod E = 0 -- after its G steps, before its end-of-sweep state is kept.  The pass visits
+// (g, h), g < h, in lexicographic order.  A step of pair (g, h):
+//     m_a[s]    = sum_{k != g, h; a_k = a} gamma[s][k]                      (k in order), rest[s][b] as above
+//     L_k       = sum_{s,b: x > 0} x[s][b] ln((rest[s][b] + eta[a][b] gamma[s][g]) + eta[a'][b] gamma[s][h]),  k = 4 a + a'
+//     q_k       = exp(L_k - max) / (e_0 + e_1 + ... + e_15, in this order);  all sixteen -inf: q = 0 and the pair stays
+//     new pair  = inverse CDF over ascending k (the last edge forced),
+//     u         = word 0 / 2^32 of Philox4x32-10(key as above; counter = (lo32 j, hi32 j, t, DSM_STREAM_APAR + c)),
+//                 j = (position index within the call) G^2 + g G + h
+// The largest of the sixteen totals (the lowest k among equals), with the state that has this pair, enters the best-state tracking like
+// a single-site step's chosen total; marg and spread see the single-site q only.
+// The polish then alternates: coordinate ascent to its fixed point, one pass of pair ascent over g < h (arg-max of the sixteen; a tie
+// with the current pair keeps it, else the lowest k), again while the pair pass changed something; ASMP_POLISH_CAP bounds the
+// coordinate sweeps and pair passes that changed something, together (rounding orders totals that tie in the model differently under
+// each pair: pair ascent alone need not end).  The sixteen totals are formed four at a time (one a, four a') from the m of the step.
+// The polish keeps none of them (a running best and the current pair's); the chain's step keeps the sixteen and their exponentials
+// in registers up to four slots per lane and, at eight, forms them three times (largest, sum, CDF) and keeps nothing.
 #include <math.h>
 #include <string.h>
 
@@ -55,9 +74,40 @@ struct SampledParams {
     uint64_t *kept;             // [N][4][T] scratch
     uint64_t *map_state, *draw_state;       // [N] packed
     double *map_ll, *conf, *marg, *spread;  // [N], [N], [N][G][4], [N]
+    int E;                      // a pair pass after every E-th sweep (PAIRS instantiations; 0 otherwise)
 };
 
-template <int NSL, bool ONE>
+// The four totals L[a'] of a thread's cells for the pair candidates (a, a') of haplotypes g and h, before they meet over the lanes:
+// m0..m3 = the rest mixture's weights without g and h, gg / gh = gamma of g / h at the thread's slots, eta [4][4] and the logarithm's
+// table in LDS.  Free of the kernel's tiling (a slot is any cell of the thread): the Gibbs sweep can take it over as it stands.
+template <int NSL>
+__device__ __forceinline__ void dsm_pair_candidates_row(const double (&x)[NSL][4], const double (&m0)[NSL], const double (&m1)[NSL],
+                                                        const double (&m2)[NSL], const double (&m3)[NSL], const double (&gg)[NSL],
+                                                        const double (&gh)[NSL], const double *eta, const double2 *ltab, int a,
+                                                        double (&L)[4])
+{
+    L[0] = 0.0; L[1] = 0.0; L[2] = 0.0; L[3] = 0.0;
+#pragma unroll
+    for (int j = 0; j < NSL; ++j) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const double rest = ((m0[j] * eta[b] + m1[j] * eta[4 + b]) + m2[j] * eta[8 + b]) + m3[j] * eta[12 + b];
+            const double with_g = rest + eta[a * 4 + b] * gg[j];
+            const bool seen = x[j][b] > 0.0;
+#pragma unroll
+            for (int a2 = 0; a2 < 4; ++a2) {
+                const double pr = with_g + eta[a2 * 4 + b] * gh[j];
+                double lg = 0.0;
+                if (__builtin_expect(dsm_log_ok(pr), 1)) lg = dsm_log_core(pr, ltab);
+                else if (seen) lg = dsm_log_slow(pr);               // 0 under a positive count: -inf (an unseen cell is never evaluated)
+                L[a2] += seen ? x[j][b] * lg : 0.0;
+            }
+            __builtin_amdgcn_sched_barrier(0);                      // one cell's four logarithms at a time: the next cell's are not issued early
+        }
+    }
+}
+
+template <int NSL, bool ONE, bool PAIRS>
 __global__ __launch_bounds__(256) void assign_sampled_kernel(const SampledParams p)
 {
     extern __shared__ double2 asmp_smem[];
@@ -147,6 +197,64 @@ __global__ __launch_bounds__(256) void assign_sampled_kernel(const SampledParams
         }
     };
 
+    // the sixteen candidate totals of the pair (g, h) of `state`, four at a time: row(a, R) is called for a = 0 .. 3 in order with
+    // R[a'] = L_{4 a + a'}, the same bits on every lane of the group.  Nothing of a row outlives its call here: what a caller keeps of the
+    // sixteen is its own choice (eight slots per lane leave no registers for all of them)
+    auto pair_rows = [&](uint64_t state, int g, int h, auto &&row) __attribute__((always_inline)) {
+        double m0[NSL], m1[NSL], m2[NSL], m3[NSL], gg[NSL], gh[NSL];
+#pragma unroll
+        for (int j = 0; j < NSL; ++j) { m0[j] = 0.0; m1[j] = 0.0; m2[j] = 0.0; m3[j] = 0.0; gg[j] = 0.0; gh[j] = 0.0; }
+        for (int g0 = 0; g0 < G; g0 += gc) {
+            const int gn = min(gc, G - g0);
+            if (!ONE) {
+                __syncthreads();                                    // the readers of the previous chunk are done
+                for (int i = tid; i < gn * SP; i += nthr) {
+                    const int kk = i / SP, s = i - kk * SP;
+                    lgam[i] = s < S ? p.gamma[(size_t)s * G + g0 + kk] : 0.0;
+                }
+                __syncthreads();
+            }
+            for (int kk = 0; kk < gn; ++kk) {
+                const int k = g0 + kk;
+                const bool isg = k == g, ish = k == h;
+                const int d = (isg || ish) ? 4 : (int)(state >> (2 * k)) & 3;
+#pragma unroll
+                for (int j = 0; j < NSL; ++j) {
+                    const double ga = lgam[kk * SP + l + j * LPV];
+                    m0[j] += d == 0 ? ga : 0.0;
+                    m1[j] += d == 1 ? ga : 0.0;
+                    m2[j] += d == 2 ? ga : 0.0;
+                    m3[j] += d == 3 ? ga : 0.0;
+                    gg[j] = isg ? ga : gg[j];
+                    gh[j] = ish ? ga : gh[j];
+                }
+            }
+        }
+#pragma unroll 1
+        for (int a = 0; a < 4; ++a) {                               // four candidates at a time: the register budget of a single-site step
+            double R[4];
+            dsm_pair_candidates_row<NSL>(x, m0, m1, m2, m3, gg, gh, leta, ltab, a, R);
+            for (int off = LPV >> 1; off > 0; off >>= 1) {
+                R[0] += __shfl_xor(R[0], off); R[1] += __shfl_xor(R[1], off); R[2] += __shfl_xor(R[2], off); R[3] += __shfl_xor(R[3], off);
+            }
+            row(a, R);
+        }
+    };
+    // row a of sixteen values kept in registers: selects, not indexed accesses
+    auto put_row = [](double (&L)[16], int a, const double (&R)[4]) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const bool here = a == k;
+            L[4 * k] = here ? R[0] : L[4 * k]; L[4 * k + 1] = here ? R[1] : L[4 * k + 1];
+            L[4 * k + 2] = here ? R[2] : L[4 * k + 2]; L[4 * k + 3] = here ? R[3] : L[4 * k + 3];
+        }
+    };
+    auto get_row = [](const double (&L)[16], int a, double (&R)[4]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) R[i] = a == 0 ? L[i] : (a == 1 ? L[4 + i] : (a == 2 ? L[8 + i] : L[12 + i]));
+    };
+    constexpr bool KEEP16 = NSL < 8;    // the chain's pair step keeps the sixteen totals; at eight slots it forms them three times instead
+
     // ---- the chain
     const uint64_t gmask = G == 32 ? ~0ull : ((1ull << (2 * G)) - 1ull);
     uint64_t state = (0x5555555555555555ull * (uint64_t)c) & gmask;
@@ -180,6 +288,68 @@ __global__ __launch_bounds__(256) void assign_sampled_kernel(const SampledParams
                 o[0] += q0; o[1] += q1; o[2] += q2; o[3] += q3;
             }
         }
+        if (PAIRS && (t + 1) % p.E == 0) {
+            // ---- the pair pass of sweep t: after its G steps, before its end-of-sweep state is kept
+            const unsigned long long jbase = (p.pos0 + (unsigned long long)(vin ? v : 0)) * (unsigned long long)G * (unsigned long long)G;
+            for (int g = 0; g < G; ++g)
+                for (int h = g + 1; h < G; ++h) {
+                    double L[16], mx = NINF;
+                    int kmax = 0;                                   // the lowest k of the largest total
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) L[k] = 0.0;
+                    pair_rows(state, g, h, [&](int a, const double (&R)[4]) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if (R[i] > mx) { mx = R[i]; kmax = 4 * a + i; }
+                        if (KEEP16) put_row(L, a, R);
+                    });
+                    // all sixteen -inf: the pair stays, its uniform is spent unseen.  The decision is per chain (group-uniform only), so
+                    // it may skip code only where no barrier follows: with the sixteen kept nothing below stages gamma; without them
+                    // the two further formations run in every chain of the workgroup and `live` guards their arithmetic instead
+                    const bool live = mx != NINF;
+                    if (KEEP16 && !live) continue;
+                    const uint64_t others = state & ~((3ull << (2 * g)) | (3ull << (2 * h)));
+                    if (mx > bestL) { bestL = mx; bestS = others | ((uint64_t)(kmax >> 2) << (2 * g)) | ((uint64_t)(kmax & 3) << (2 * h)); }
+                    const unsigned long long jj = jbase + (unsigned long long)(g * G + h);
+                    uint32_t w[4];
+                    philox4x32_10((uint32_t)jj, (uint32_t)(jj >> 32), (uint32_t)t, DSM_STREAM_APAR + (uint32_t)c, p.k0, p.k1, w);
+                    const double u = (double)w[0] * 2.3283064365386963e-10;
+                    double sum = 0.0, cdf = 0.0;
+                    int kn = 15;                                    // the last edge is forced
+                    bool found = false;
+                    if (KEEP16) {
+                        double e[16];
+#pragma unroll
+                        for (int k = 0; k < 16; ++k) e[k] = 0.0;
+#pragma unroll 1
+                        for (int a = 0; a < 4; ++a) {               // four exponentials at a time, e_k added in ascending k
+                            double r[4];
+                            get_row(L, a, r);
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) { r[i] = r[i] == NINF ? 0.0 : exp(r[i] - mx); sum += r[i]; }
+                            put_row(e, a, r);
+                        }
+#pragma unroll
+                        for (int k = 0; k < 15; ++k) {
+                            cdf += e[k] / sum;
+                            if (!found && u < cdf) { kn = k; found = true; }
+                        }
+                    } else {                                        // the same totals again, bit for bit: twice more
+                        pair_rows(state, g, h, [&](int, const double (&R)[4]) {
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) sum += (!live || R[i] == NINF) ? 0.0 : exp(R[i] - mx);
+                        });
+                        pair_rows(state, g, h, [&](int a, const double (&R)[4]) {
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) {
+                                cdf += live ? (R[i] == NINF ? 0.0 : exp(R[i] - mx)) / sum : 0.0;
+                                if (!found && 4 * a + i < 15 && u < cdf) { kn = 4 * a + i; found = true; }
+                            }
+                        });
+                    }
+                    if (live) state = others | ((uint64_t)(kn >> 2) << (2 * g)) | ((uint64_t)(kn & 3) << (2 * h));
+                }
+        }
         if (keep && l == 0 && vin) p.kept[((size_t)v * 4 + c) * p.T + (t - p.B)] = state;
     }
 
@@ -212,27 +382,57 @@ __global__ __launch_bounds__(256) void assign_sampled_kernel(const SampledParams
         p.draw_state[v] = dead ? 0ull : state;
     }
 
-    // ---- polish by coordinate ascent: the arg-max candidate of every site, ties keep the base, else the lowest a
-    bool active = vin && !dead;
+    // ---- polish by coordinate ascent: the arg-max candidate of every site, ties keep the base, else the lowest a.  PAIRS: rounds of
+    // (coordinate ascent to its fixed point, one pass of pair ascent) until a pair pass changes nothing
+    bool open = vin && !dead;       // the position's polish has not ended (read by the pair pass only)
+    bool active = open;
     int nsw = 0;
     for (;;) {
-        bool changed = false;
-        for (int g = 0; g < G; ++g) {
-            double L[4];
-            candidates(cur, g, L);
-            const int d = (int)(cur >> (2 * g)) & 3;
-            double best = d == 0 ? L[0] : (d == 1 ? L[1] : (d == 2 ? L[2] : L[3]));
-            int a = d;
+        for (;;) {
+            bool changed = false;
+            for (int g = 0; g < G; ++g) {
+                double L[4];
+                candidates(cur, g, L);
+                const int d = (int)(cur >> (2 * g)) & 3;
+                double best = d == 0 ? L[0] : (d == 1 ? L[1] : (d == 2 ? L[2] : L[3]));
+                int a = d;
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (L[k] > best) { best = L[k]; a = k; }
-            if (active) {
-                if (a != d) { cur = (cur & ~(3ull << (2 * g))) | ((uint64_t)a << (2 * g)); changed = true; }
-                curL = best;
+                for (int k = 0; k < 4; ++k)
+                    if (L[k] > best) { best = L[k]; a = k; }
+                if (active) {
+                    if (a != d) { cur = (cur & ~(3ull << (2 * g))) | ((uint64_t)a << (2 * g)); changed = true; }
+                    curL = best;
+                }
             }
+            if (active && (!changed || ++nsw == ASMP_POLISH_CAP)) { active = false; open = open && !changed; }
+            if (!__syncthreads_or(active ? 1 : 0)) break;
         }
-        if (active && (!changed || ++nsw == ASMP_POLISH_CAP)) active = false;
-        if (!__syncthreads_or(active ? 1 : 0)) break;
+        if (!PAIRS) break;
+        bool moved = false;
+        for (int g = 0; g < G; ++g)
+            for (int h = g + 1; h < G; ++h) {
+                const int k0 = (((int)(cur >> (2 * g)) & 3) << 2) | ((int)(cur >> (2 * h)) & 3);
+                double best = NINF, L0 = NINF;                      // the largest total (kn: its lowest k) and the current pair's
+                int kn = 0;
+                pair_rows(cur, g, h, [&](int a, const double (&R)[4]) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        if (R[i] > best) { best = R[i]; kn = 4 * a + i; }
+                        L0 = 4 * a + i == k0 ? R[i] : L0;
+                    }
+                });
+                const bool cur_is_best = L0 == best;                // the current pair's total equals the largest: it stays
+                if (open) {
+                    if (!cur_is_best) {
+                        cur = (cur & ~((3ull << (2 * g)) | (3ull << (2 * h)))) | ((uint64_t)(kn >> 2) << (2 * g)) | ((uint64_t)(kn & 3) << (2 * h));
+                        moved = true;
+                    }
+                    curL = best;
+                }
+            }
+        if (open && (!moved || ++nsw == ASMP_POLISH_CAP)) open = false;     // a pair pass that changed nothing ends the polish
+        active = open;
+        if (!__syncthreads_or(open ? 1 : 0)) break;
     }
 
     // ---- conf: the kept end-of-sweep states equal to the polished state
@@ -313,11 +513,16 @@ extern "C" int dsm_assign_sampled_debug_path(int S, int G, int *out)
     return DSM_OK;
 }
 
-static int asmp_check_model(int S, int G, const double *gamma, const double *eta, long long burn, long long kept)
+static int asmp_check_model(int S, int G, const double *gamma, const double *eta, long long burn, long long kept, long long pair_every)
 {
     SampledPlan pl;
     STRY(asmp_plan(S, G, &pl));
     if (kept < 1 || burn < 0) { dsm_set_error("assign_sampled: burn=%lld, kept=%lld", burn, kept); return DSM_ERR_ARG; }
+    if (pair_every < 0) { dsm_set_error("assign_sampled: pair_every=%lld", pair_every); return DSM_ERR_ARG; }
+    if (pair_every > ASMP_MAX_SWEEPS) {
+        dsm_set_error("assign_sampled: pair_every = %lld exceeds %d", pair_every, ASMP_MAX_SWEEPS);
+        return DSM_ERR_UNSUPPORTED;
+    }
     if (burn + kept > ASMP_MAX_SWEEPS) {
         dsm_set_error("assign_sampled: burn + kept = %lld exceeds %d sweeps", burn + kept, ASMP_MAX_SWEEPS);
         return DSM_ERR_UNSUPPORTED;
@@ -329,20 +534,27 @@ static int asmp_check_model(int S, int G, const double *gamma, const double *eta
     return DSM_OK;
 }
 
-template <int NSL, bool ONE>
-static int asmp_launch(const SampledPlan &pl, const SampledParams &q)
+template <int NSL, bool ONE, bool PAIRS>
+static int asmp_launch_as(const SampledPlan &pl, const SampledParams &q)
 {
-    const void *fn = reinterpret_cast<const void *>(&assign_sampled_kernel<NSL, ONE>);
+    const void *fn = reinterpret_cast<const void *>(&assign_sampled_kernel<NSL, ONE, PAIRS>);
     if (pl.lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
     const unsigned blocks = (unsigned)((q.N + pl.ppw - 1) / pl.ppw), threads = (unsigned)(pl.ppw * 4 * pl.lpv);
-    hipLaunchKernelGGL((assign_sampled_kernel<NSL, ONE>), dim3(blocks), dim3(threads), pl.lds, 0, q);
+    hipLaunchKernelGGL((assign_sampled_kernel<NSL, ONE, PAIRS>), dim3(blocks), dim3(threads), pl.lds, 0, q);
     HIP_TRY(hipGetLastError());
     return DSM_OK;
 }
 
+template <int NSL, bool ONE>
+static int asmp_launch(const SampledPlan &pl, const SampledParams &q)
+{
+    return q.E > 0 ? asmp_launch_as<NSL, ONE, true>(pl, q) : asmp_launch_as<NSL, ONE, false>(pl, q);
+}
+
 // d_cnt: the whole tensor on the device (context form), or null with h_cnt = the caller's int64 tensor (uploaded chunk by chunk)
 static int asmp_run(const int32_t *d_cnt, const int64_t *h_cnt, int N, int S, int G, const double *gamma, const double *eta, uint64_t seed,
-                    int burn, int kept, uint8_t *map_state, double *map_ll, double *conf, double *marg, double *spread, uint8_t *draw_state)
+                    int burn, int kept, int pair_every, uint8_t *map_state, double *map_ll, double *conf, double *marg, double *spread,
+                    uint8_t *draw_state)
 {
     SampledPlan pl;
     STRY(asmp_plan(S, G, &pl));
@@ -380,7 +592,7 @@ static int asmp_run(const int32_t *d_cnt, const int64_t *h_cnt, int N, int S, in
         }
         SampledParams q;
         q.cnt = cnt; q.gamma = d_gamma; q.eta = d_eta; q.log_tab = d_ltab;
-        q.N = n; q.S = S; q.G = G; q.lpv_log2 = pl.lpv_log2; q.gc = pl.gc; q.ppw = pl.ppw; q.B = burn; q.T = kept;
+        q.N = n; q.S = S; q.G = G; q.lpv_log2 = pl.lpv_log2; q.gc = pl.gc; q.ppw = pl.ppw; q.B = burn; q.T = kept; q.E = pair_every;
         q.k0 = (uint32_t)seed; q.k1 = (uint32_t)(seed >> 32); q.pos0 = (unsigned long long)n0;
         q.kept = d_kept; q.map_state = d_map; q.draw_state = d_draw; q.map_ll = d_ll; q.conf = d_conf; q.marg = d_marg; q.spread = d_spread;
         switch (pl.inst) {
@@ -407,15 +619,15 @@ static int asmp_run(const int32_t *d_cnt, const int64_t *h_cnt, int N, int S, in
     return DSM_OK;
 }
 
-extern "C" int dsm_assign_tau_sampled(int device, const int64_t *counts, int N, int S, int G, const double *gamma, const double *eta,
-                                      uint64_t seed, int burn, int kept, uint8_t *map_state, double *map_ll, double *conf, double *marg,
-                                      double *spread, uint8_t *draw_state)
+extern "C" int dsm_assign_tau_sampled_pairs(int device, const int64_t *counts, int N, int S, int G, const double *gamma, const double *eta,
+                                            uint64_t seed, int burn, int kept, int pair_every, uint8_t *map_state, double *map_ll,
+                                            double *conf, double *marg, double *spread, uint8_t *draw_state)
 {
     if (N < 0 || !gamma || !eta || (N > 0 && (!counts || !map_state || !marg))) {
         dsm_set_error("assign_tau_sampled: bad arguments");
         return DSM_ERR_ARG;
     }
-    STRY(asmp_check_model(S, G, gamma, eta, burn, kept));
+    STRY(asmp_check_model(S, G, gamma, eta, burn, kept, pair_every));
     // the count rules of dsm_ctx_set_counts: no negative count, no cell above 2^31 - 1 reads
     for (size_t i = 0; i < (size_t)N * S; ++i) {
         int64_t tot = 0;
@@ -431,18 +643,34 @@ extern "C" int dsm_assign_tau_sampled(int device, const int64_t *counts, int N, 
     if (nd <= 0) { dsm_set_error("no HIP device visible"); return DSM_ERR_NODEVICE; }
     if (device < 0 || device >= nd) { dsm_set_error("device %d out of range (0..%d)", device, nd - 1); return DSM_ERR_ARG; }
     HIP_TRY(hipSetDevice(device));
-    return asmp_run(nullptr, counts, N, S, G, gamma, eta, seed, burn, kept, map_state, map_ll, conf, marg, spread, draw_state);
+    return asmp_run(nullptr, counts, N, S, G, gamma, eta, seed, burn, kept, pair_every, map_state, map_ll, conf, marg, spread, draw_state);
+}
+
+extern "C" int dsm_assign_tau_sampled(int device, const int64_t *counts, int N, int S, int G, const double *gamma, const double *eta,
+                                      uint64_t seed, int burn, int kept, uint8_t *map_state, double *map_ll, double *conf, double *marg,
+                                      double *spread, uint8_t *draw_state)
+{
+    return dsm_assign_tau_sampled_pairs(device, counts, N, S, G, gamma, eta, seed, burn, kept, 0, map_state, map_ll, conf, marg, spread,
+                                        draw_state);
+}
+
+extern "C" int dsm_ctx_assign_tau_sampled_pairs(dsm_ctx *c, const double *gamma, const double *eta, int G, uint64_t seed, int burn, int kept,
+                                                int pair_every, uint8_t *map_state, double *map_ll, double *conf, double *marg,
+                                                double *spread, uint8_t *draw_state)
+{
+    if (!c) { dsm_set_error("null context"); return DSM_ERR_ARG; }
+    if (!c->cnt_vs) { dsm_set_error("no count tensor: call dsm_ctx_set_counts first"); return DSM_ERR_STATE; }
+    if (!gamma || !eta || !map_state || !marg) { dsm_set_error("ctx_assign_tau_sampled: null pointer"); return DSM_ERR_ARG; }
+    STRY(asmp_check_model(c->S, G, gamma, eta, burn, kept, pair_every));
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));           // the resident tensor is read from the default stream below
+    return asmp_run(c->cnt_vs, nullptr, c->V, c->S, G, gamma, eta, seed, burn, kept, pair_every, map_state, map_ll, conf, marg, spread,
+                    draw_state);
 }
 
 extern "C" int dsm_ctx_assign_tau_sampled(dsm_ctx *c, const double *gamma, const double *eta, int G, uint64_t seed, int burn, int kept,
                                           uint8_t *map_state, double *map_ll, double *conf, double *marg, double *spread,
                                           uint8_t *draw_state)
 {
-    if (!c) { dsm_set_error("null context"); return DSM_ERR_ARG; }
-    if (!c->cnt_vs) { dsm_set_error("no count tensor: call dsm_ctx_set_counts first"); return DSM_ERR_STATE; }
-    if (!gamma || !eta || !map_state || !marg) { dsm_set_error("ctx_assign_tau_sampled: null pointer"); return DSM_ERR_ARG; }
-    STRY(asmp_check_model(c->S, G, gamma, eta, burn, kept));
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));           // the resident tensor is read from the default stream below
-    return asmp_run(c->cnt_vs, nullptr, c->V, c->S, G, gamma, eta, seed, burn, kept, map_state, map_ll, conf, marg, spread, draw_state);
+    return dsm_ctx_assign_tau_sampled_pairs(c, gamma, eta, G, seed, burn, kept, 0, map_state, map_ll, conf, marg, spread, draw_state);
 }

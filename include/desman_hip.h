@@ -418,7 +418,33 @@ int dsm_assign_tau_sampled(int device, const int64_t *counts /*[N][S][4]*/, int 
                            double *marg, double *spread, uint8_t *draw_state);
 int dsm_ctx_assign_tau_sampled(dsm_ctx *ctx, const double *gamma, const double *eta, int G, uint64_t seed, int burn, int kept,
                                uint8_t *map_state, double *map_ll, double *conf, double *marg, double *spread, uint8_t *draw_state);
-/* test hooks: positions per launch of the two calls above (0 = by the scratch bound); the path of a shape, nothing launched --
+/* The same call with joint moves of two haplotypes.  pair_every = E >= 0; E = 0 is the call above exactly (the two entry points above
+ * are the E = 0 case of the same host code).  With E > 0, sweep t (t = 0 .. burn + kept - 1) is followed by a pair pass when
+ * (t + 1) mod E = 0 -- after the sweep's G single-site steps and before its end-of-sweep state is recorded, so conf, draw_state and
+ * the kept states see the state after the pass.  The pass visits the pairs (g, h), g < h, in lexicographic order.  A step of (g, h)
+ * forms m_a = sum of gamma[s][k] over k not in {g, h} with a_k = a (k in order), the rest mixture as in a single-site step, the
+ * sixteen totals L_k, k = 4 a + a' (a the new base of g, a' of h): the L of the whole state, x ln((rest + eta[a][b] gamma[s][g]) +
+ * eta[a'][b] gamma[s][h]) over the cells with x > 0, q_k = exp(L_k - max) / (e_0 + ... + e_15 in this order), and draws the pair by
+ * inverse CDF over ascending k with u = word 0 / 2^32 of Philox4x32-10, key = (lo32, hi32) of seed, counter = (lo32 j, hi32 j, sweep,
+ * 'APAR' + c), j = (position index within the call) G^2 + g G + h.  All sixteen -inf: the pair keeps its bases (q = 0), its uniform
+ * is spent.  Best-state tracking looks at all sixteen totals of a pair step: the largest of them (the lowest k among equals), with
+ * the state that has this pair, enters like a single-site step's chosen total (ties: lowest chain, earliest step); marg and spread
+ * keep their definition: the q of the single-site steps only.  The polish alternates
+ * coordinate ascent to its fixed point with one pass of pair ascent over g < h (arg-max of the sixteen totals; a tie with the
+ * current pair keeps it, else the lowest k) and repeats while the pair pass changed something.  The coordinate sweeps and pair passes
+ * that changed something number at most 64 together: the polish ends with the 64th, whichever kind it is (totals that tie in the
+ * model, as under equal gamma columns, are ordered by rounding differently under each pair, so pair ascent alone need not end).
+ * map_ll is the total as the last polish step formed it -- with E > 0 the pair form ((rest + g's term) + h's term) of the last
+ * pair, which can differ in the last bits from the single-site form that E = 0 reports for the same state.  G = 1 has no pairs.  Limits as above and 0 <= pair_every <= 65536
+ * (DSM_ERR_UNSUPPORTED above, DSM_ERR_ARG below 0); the same device scratch.  The results depend on (seed, position index within the
+ * call, counts, gamma, eta, burn, kept, pair_every) alone -- not on the chunking, on scheduling or on the entry point.             */
+int dsm_assign_tau_sampled_pairs(int device, const int64_t *counts /*[N][S][4]*/, int N, int S, int G, const double *gamma,
+                                 const double *eta, uint64_t seed, int burn, int kept, int pair_every, uint8_t *map_state,
+                                 double *map_ll, double *conf, double *marg, double *spread, uint8_t *draw_state);
+int dsm_ctx_assign_tau_sampled_pairs(dsm_ctx *ctx, const double *gamma, const double *eta, int G, uint64_t seed, int burn, int kept,
+                                     int pair_every, uint8_t *map_state, double *map_ll, double *conf, double *marg, double *spread,
+                                     uint8_t *draw_state);
+/* test hooks: positions per launch of the four calls above (0 = by the scratch bound); the path of a shape, nothing launched --
  * out[5] = instantiation (2 log2 NSL + 1 where gamma is staged in chunks), lanes per (position, chain), sample slots per lane,
  * haplotypes per staged chunk of gamma, positions per workgroup */
 int dsm_assign_sampled_debug_set_chunk(int positions);
