@@ -19,6 +19,7 @@ from . import _lib
 from . import fixed_tau as _fixed_tau
 from . import check as _check
 from . import diagnose as _diagnose
+from . import predictive as _predictive
 from . import relabel as _relabel
 from . import sampletau as _sampletau
 
@@ -521,6 +522,17 @@ class HaploSNP_Sampler:
             self._fit = _check.fit_scores(sums, self.max_iter, self.variants)
         f = self._fit
         return (f["sample"], f["position"], f["cell"]) if cells else (f["sample"], f["position"])
+
+    # ---- position-marginal predictive density of the last update() (desman_amd/predictive.py)
+    def predictive(self, n_use=_predictive.N_USE, counts=None):
+        """The pointwise table (predictive.pointwise: lppd, p_waic, elpd_waic per position) of about ``n_use`` evenly spaced stored
+        iterations -- stride max(1, stored // n_use) -- for the positions of the fit or, ``counts`` [N, S, 4], for other positions of the
+        same samples (held-out ones: their lppd is the honest score, p_waic does not apply).  Invariant to the haplotype labels."""
+        if n_use < 1:
+            raise ValueError("predictive: n_use must be at least 1; got %d" % n_use)
+        stride = max(1, self.max_iter // int(n_use))
+        res = self._trace_ctx().trace_predictive(counts=counts, it0=0, n_it=self.max_iter, stride=stride)
+        return _predictive.pointwise(res, self.variants if counts is None else counts, self.G)
 
     @property
     def tau_store(self):

@@ -268,6 +268,27 @@ class Output_Results:
         frame.to_csv(self._path("Fit_cells.csv"))
         logging.info("Fit_cells.csv written")
 
+    # ---- `desman --predictive`: position-marginal predictive density (desman_amd/predictive.py)
+    def output_Predictive(self, pointwise_fit, pointwise_rest, summary):
+        """Predictive_positions.csv: Contig, Position, kind, lppd, p_waic, elpd_waic -- the fitted positions (kind `fit`, keyed as
+        Tau_Mean.csv keys its rows) and, ``pointwise_rest`` not None, the positions -r left out of the fit (kind `heldout`, in input
+        order; p_waic empty, elpd_waic = lppd); Predictive_summary.csv: one row per kind from ``summary`` = {kind: predictive.summary}"""
+        from . import predictive
+        frames = [pd.DataFrame({"Contig": self.filtered_contig_names, "Position": self.filtered_position, "kind": "fit",
+                                "lppd": pointwise_fit["lppd"], "p_waic": pointwise_fit["p_waic"], "elpd_waic": pointwise_fit["elpd_waic"]})]
+        if pointwise_rest is not None:
+            vf = self.variantFilter
+            rows = np.asarray(vf.selected_indices_original, dtype=np.int64)
+            rows = rows[~np.asarray(vf.selected, dtype=bool)[:len(rows)]]
+            frames.append(pd.DataFrame({"Contig": [self.contig_names[i] for i in rows], "Position": self.position.to_numpy()[rows],
+                                        "kind": "heldout", "lppd": pointwise_rest["lppd"], "p_waic": np.nan,
+                                        "elpd_waic": pointwise_rest["lppd"]}))
+        pd.concat(frames, ignore_index=True)[list(predictive.POSITION_COLUMNS)].to_csv(self._path(predictive.POSITIONS_FILE), index=False)
+        rows = [predictive.summary_row(kind, summary[kind]) for kind in ("fit", "heldout") if kind in summary]
+        pd.DataFrame(rows, columns=list(predictive.SUMMARY_COLUMNS)).to_csv(self._path(predictive.SUMMARY_FILE), index=False)
+        logging.info("%s / %s written: %s" % (predictive.POSITIONS_FILE, predictive.SUMMARY_FILE, "; ".join(
+            "%s elpd %.3f (se %.3f) over %d positions" % (r["kind"], r["elpd"], r["se"], r["n_positions"]) for r in rows)))
+
     def output_Selected_Variants(self):
         """the selected rows of the input table.  Every chain of a G-sweep writes the same file (the -r selection is drawn from
         a fixed seed, bin/desman:85-86): serialising 50 000 x 385 integers takes longer than the chain's GPU work, so within one

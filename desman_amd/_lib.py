@@ -130,6 +130,9 @@ SIGNATURES = {
     "dsm_assign_tau": (_i, [_i, _i64p, _i, _i, _i, _f64p, _f64p, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "dsm_ctx_assign_tau": (_i, [_vp, _f64p, _f64p, _i, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "dsm_assign_debug_set_chunk": (_i, [_i]),
+    "dsm_ctx_trace_predictive": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "dsm_pred_debug_set_chunk": (_i, [_i]),
+    "dsm_pred_debug_set_parts": (_i, [_i]),
     "dsm_assign_tau_sampled": (_i, [_i, _i64p, _i, _i, _i, _f64p, _f64p, C.c_uint64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dsm_ctx_assign_tau_sampled": (_i, [_vp, _f64p, _f64p, _i, C.c_uint64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dsm_assign_tau_sampled_pairs": (_i, [_i, _i64p, _i, _i, _i, _f64p, _f64p, C.c_uint64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -284,6 +287,17 @@ def assign_tau(counts, gamma, eta, seed=None, device=0):
 def assign_debug_set_chunk(positions=0):
     """test hook: positions per launch of assign_tau / Context.assign_tau (0 = the default bound); results do not depend on it"""
     check(load().dsm_assign_debug_set_chunk(int(positions)))
+
+
+def pred_debug_set_chunk(positions=0):
+    """test hook: positions per chunk of Context.trace_predictive (0 = the library's own choice); results do not depend on it"""
+    check(load().dsm_pred_debug_set_chunk(int(positions)))
+
+
+def pred_debug_set_parts(parts=0):
+    """test hook: the parts a launch of Context.trace_predictive cuts its iterations into across workgroups (0 = the library's own
+    choice); results do not depend on it"""
+    check(load().dsm_pred_debug_set_parts(int(parts)))
 
 
 SAMPLED_KEPT, SAMPLED_BURN = 100, 20    # conventions of `desman-assign --sampled`, not tuned
@@ -924,6 +938,32 @@ class Context:
         check(self.lib.dsm_ctx_trace_fit_stats(self._h, int(it0), n_it, _ptr(out.get("sample")), _ptr(out.get("position")),
                                                _ptr(out.get("cell"))))
         out["n_it"] = n_it
+        return out
+
+    def trace_predictive(self, counts=None, it0=0, n_it=None, stride=1, want=("lppd", "mean", "var")):
+        """Position-marginal log predictive density over the stored iterations it0, it0 + stride, ... below it0 + n_it (include/
+        desman_hip.h: dsm_ctx_trace_predictive; desman_amd/predictive.py): per position of ``counts`` [N, S, 4] -- None: the resident
+        table -- logz[t] = ln of the sum over all 4^G haplotype states of exp L under (gamma_t, eta_t); a dict of lppd [N], mean [N],
+        var [N] and, when named in ``want``, logz_it [n_used, N]; only those named are allocated and fetched.  n_used is in the dict.
+        G <= ASSIGN_MAX_G."""
+        n_it = self.n_trace - int(it0) if n_it is None else int(n_it)
+        stride = int(stride)
+        x = None
+        N = self.V
+        if counts is not None:
+            x = np.ascontiguousarray(counts, dtype=np.int64)
+            if x.ndim != 3 or x.shape[1:] != (self.S, 4):
+                raise ValueError("trace_predictive: counts must be [N, S=%d, 4]; got %s" % (self.S, x.shape))
+            N = x.shape[0]
+        n_used = -(-n_it // stride) if stride >= 1 and n_it > 0 else 0
+        shapes = dict(lppd=(N,), mean=(N,), var=(N,), logz_it=(n_used, N))
+        bad = [k for k in want if k not in shapes]
+        if bad:
+            raise ValueError("trace_predictive: unknown output %r (lppd, mean, var, logz_it)" % bad[0])
+        out = {k: np.zeros(shapes[k]) for k in shapes if k in want}
+        check(self.lib.dsm_ctx_trace_predictive(self._h, _ptr(x), N, int(it0), n_it, stride, _ptr(out.get("lppd")), _ptr(out.get("mean")),
+                                                _ptr(out.get("var")), _ptr(out.get("logz_it"))))
+        out["n_used"] = n_used
         return out
 
     def fit_debug_path(self, n_it=None):

@@ -70,6 +70,12 @@ def build_parser():
                          "haplotypes do not explain; z is a conservative score, not a p-value (extension)")
     ap.add_argument('--check-cells', dest='check_cells', action='store_true',
                     help="with --check: also write Fit_cells.csv, positions x samples, the posterior mean X2 of every cell (extension)")
+    ap.add_argument('--predictive', nargs='?', const=50, default=None, type=int, metavar='N',
+                    help="also write the position-marginal predictive density of the chain, for choosing -g: Predictive_positions.csv "
+                         "(per position: lppd, p_waic, elpd_waic with the haplotype bases summed out; kind `fit` = WAIC of the fitted "
+                         "positions, with -r also kind `heldout` = the log predictive density of the positions left out of the fit) and "
+                         "Predictive_summary.csv; from N evenly spaced stored iterations (default 50, a convention); -g up to 10; "
+                         "compare runs with `python -m desman_amd.predictive compare` (extension)")
     return ap
 
 
@@ -231,6 +237,36 @@ def _report_check(report, chain, cells):
         report.output_Fit_cells(fit[2])
 
 
+def _predictive_options(opts, replicates=False):
+    """--predictive: refused here, before any chain, where it cannot be served"""
+    if opts.predictive is None:
+        return
+    from . import predictive
+    if replicates:
+        sys.exit("desman: --predictive is not available for replicate chains that share their launches: run the chains one by one")
+    if opts.predictive < 1:
+        sys.exit("desman: --predictive: at least 1 stored iteration must be used; got %d" % opts.predictive)
+    if opts.genomes > predictive.MAX_G:
+        sys.exit("desman: --predictive sums over all 4^G haplotype states of a position: -g %d is above %d" % (opts.genomes, predictive.MAX_G))
+    if opts.no_iter is not None and opts.no_iter < 1:
+        sys.exit("desman: --predictive: %d stored iterations (-i): at least 1 is needed" % opts.no_iter)
+
+
+def _report_predictive(report, flt, chain, n_use, subsample):
+    """--predictive: the fitted positions scored on the chain's resident table (WAIC) and, with -r, the positions left out of the fit --
+    the rows _assign_rest takes -- scored under the same traces (held-out log predictive density); next to the usual files, which do
+    not change"""
+    from . import predictive
+    fit = chain.predictive(n_use)
+    rest = None
+    if subsample is not None:
+        rest = chain.predictive(n_use, counts=flt.snps_filter_original[~np.asarray(flt.selected, dtype=bool), :])
+    summary = {"fit": predictive.summary(fit)}
+    if rest is not None:
+        summary["heldout"] = predictive.summary(rest)
+    report.output_Predictive(fit, rest, summary)
+
+
 def _assign_rest(opts, report, table, flt, chain):
     """-r: haplotypes of the positions left out of the fit, with tau-only sweeps driven by the fitted
     chain's gamma / eta traces (bin/desman:181-206)."""
@@ -304,6 +340,7 @@ def main(argv=None):
         sys.exit(-1)
     diag_len = _diagnose_batch_len(opts)
     _check_options(opts)
+    _predictive_options(opts)
     report = Output_Results(opts.output_dir)
     table, flt, subsample = _load(opts, report)
     ref = _relabel_reference(opts, table, flt)
@@ -315,6 +352,8 @@ def main(argv=None):
         _report_diagnose(report, chain, diag_len)
     if opts.check:
         _report_check(report, chain, opts.check_cells)
+    if opts.predictive is not None:
+        _report_predictive(report, flt, chain, opts.predictive, subsample)
     if subsample is not None:
         _assign_rest(opts, report, table, flt, chain)
     sampletau.freeRNG()
@@ -337,6 +376,7 @@ def main_replicates(argv_list, on_chain=None):
             sys.exit('desman: -a/--assign_file is not supported (dead in the reference: bin/desman:213-214)')
         diag_len = _diagnose_batch_len(opts)
         _check_options(opts)
+        _predictive_options(opts, replicates=True)
         report = Output_Results(opts.output_dir)
         table, flt, subsample = _load(opts, report)
         logging.info('sampler seed %d', opts.random_seed)

@@ -393,6 +393,39 @@ int dsm_ctx_assign_tau(dsm_ctx *ctx, const double *gamma, const double *eta, int
 /* test hook: positions per launch of the two calls above (0 = by the scratch bound, the default) */
 int dsm_assign_debug_set_chunk(int positions);
 
+/* Position-marginal predictive density of a chain (desman_amd/predictive.py): for every used iteration t of the
+ * resident gamma and eta traces and every position v of `counts` -- host [N][S][4] int64, or NULL = the count tensor resident in the
+ * context, N = its V (the argument N is then ignored) --
+ *     logz[t][v] = ln sum over the 4^G joint states of exp L_t(state),
+ * L exactly as dsm_assign_tau defines it under (gamma_t, eta_t): cells with a zero count are not evaluated, logarithms by dsm_log,
+ * the same sums in the same order (the value is dsm_ctx_assign_tau's logz for that gamma and eta).  The haplotype bases of the
+ * position are summed out, so the value does not depend on tau, on the haplotype labels or on whether the position was in the fit;
+ * p(x_v | gamma_t, eta_t) = M_v 4^-G exp logz[t][v], M_v the product of the samples' multinomial coefficients (the caller adds
+ * ln M_v - G ln 4).  Used iterations: t = it0, it0 + stride, ... below it0 + n_it, numbered as by dsm_ctx_get_tau_at;
+ * n_used = ceil(n_it / stride).  Outputs over them, host pointers, any may be NULL:
+ *     lppd    [N]          ln((1 / n_used) sum_t exp logz[t][v]), a max-shifted sum in iteration order
+ *     mean    [N]          the mean of logz[t][v]
+ *     var     [N]          the sample variance, divisor n_used - 1, from a second, centred pass; 0 when n_used = 1
+ *     logz_it [n_used][N]  the matrix itself
+ * A (t, v) whose every state has L = -inf (exact zeros in eta_t / gamma_t that contradict the counts) has logz = -inf: zero mass in
+ * lppd, mean = -inf, var = +inf; every iteration -inf: lppd = -inf.  Nothing is ever NaN for a trace that is finite and >= 0 (what
+ * the chain writes; a trace planted by dsm_ctx_debug_set_param_trace is not checked).  n_it = 0 (and N = 0) succeeds and writes
+ * nothing.  DSM_ERR_STATE when no update has run; DSM_ERR_ARG for a range outside the trace, stride < 1, N < 0 and counts that
+ * dsm_ctx_set_counts would refuse; DSM_ERR_UNSUPPORTED for G > DSM_ASSIGN_MAX_G; S <= DSM_MAX_S.  The work is n_used N 4^G states.
+ * Positions are processed in chunks and the iterations of a chunk in launches: device scratch stays below ~100 MB whatever N and n_used
+ * are (beyond 4 M used iterations: one position's logz column, 8 n_used bytes).  No floating-point atomics, every sum has one order:
+ * the results do not depend on the chunking, on the number of iteration parts or on scheduling, and NULL gives the same bits as a
+ * copy of the resident table.  The chain state, both RNG streams, every trace and the MAP record are only read: a chain continues
+ * bit for bit after the call.                                                                                                      */
+int dsm_ctx_trace_predictive(dsm_ctx *ctx, const int64_t *counts /*[N][S][4] host, or NULL = the resident table, N = its V*/, int N,
+                             int it0, int n_it, int stride, double *lppd /*[N]*/, double *mean /*[N]*/, double *var /*[N]*/,
+                             double *logz_it /*[n_used][N] or NULL*/);
+/* test hooks: positions per chunk of the call above (0 = the library's choice, by the scratch bounds), and the parts a launch cuts
+ * its iterations into across workgroups (0 = the library's choice: 1 once positions x partials fill the machine; never more parts
+ * than iterations) */
+int dsm_pred_debug_set_chunk(int positions);
+int dsm_pred_debug_set_parts(int parts);
+
 /* Sampled joint assignment: the model of dsm_assign_tau for every G <= DSM_MAX_G.  Each position runs four
  * private Gibbs chains over its G sites; chain c starts at "every haplotype = base c", runs burn + kept sweeps over g = 0 .. G-1 and
  * keeps the last `kept`.  A step forms the rest mixture afresh, the four candidate totals L_a (the L of the whole state with
