@@ -24,10 +24,18 @@ from . import relabel as _relabel
 from . import sampletau as _sampletau
 
 
+def _check_pair_every(pair_every):
+    """pair_every of the constructor: an int >= 0 (0 = no pair moves; E = a pair pass after every E-th sweep of update())"""
+    if isinstance(pair_every, bool) or not isinstance(pair_every, (int, np.integer)) or pair_every < 0:
+        raise ValueError("pair_every must be an integer >= 0 (0 = no pair moves); got %r" % (pair_every,))
+    return int(pair_every)
+
+
 class HaploSNP_Sampler:
 
     def __init__(self, snps, G, randomState, fixed_tau=None, burn_iter=None, max_iter=None,
-                 alpha_constant=0.1, delta_constant=0.1, epsilon=1.0e-6, device=0, ctx=None):
+                 alpha_constant=0.1, delta_constant=0.1, epsilon=1.0e-6, device=0, ctx=None, pair_every=0):
+        self.pair_every = _check_pair_every(pair_every)
         self.burn_iter = 250 if burn_iter is None else burn_iter
         self.max_iter = 250 if max_iter is None else max_iter
         self.randomState = randomState
@@ -57,6 +65,8 @@ class HaploSNP_Sampler:
         self._ctx = ctx if ctx is not None else _lib.Context(device)
         self._ctx.set_counts(self.variants)
         self._ctx.set_priors(alpha_constant, delta_constant, epsilon)
+        if ctx is None or self.pair_every > 0:      # (a context handed in keeps its own setting unless pair moves are asked for here)
+            self._ctx.set_pair_moves(self.pair_every)
         self._tau_sum = None
         self._relabel = None
         self._diag = None
@@ -131,7 +141,8 @@ class HaploSNP_Sampler:
 
     # ---- the Gibbs loop
     def update(self):
-        """max_iter Gibbs iterations (HaploSNP_Sampler.py:334-365), on the device."""
+        """max_iter Gibbs iterations (HaploSNP_Sampler.py:334-365), on the device.  pair_every = E > 0: a pair pass follows the sweep of
+        every iteration whose counter satisfies (iter_ctr + 1) mod E == 0."""
         self._push_state()
         self._bind_rng()
         self._ctx.gibbs_update(self.max_iter)
@@ -144,6 +155,8 @@ class HaploSNP_Sampler:
         all of them (dsm_batch_gibbs_update; the replicate chains of a G value, scripts/runDesman.sh:15-21).  Every sampler
         needs a GSL stream of its own (``mt_state``).  The mu/E pass of a batch is the aggregated sampler."""
         samplers = list(samplers)
+        if any(getattr(s, "pair_every", 0) > 0 for s in samplers):
+            raise ValueError("update_batch: pair moves (pair_every > 0) have no batched form; run such chains one by one with update()")
         n = samplers[0].max_iter
         if any(s.max_iter != n for s in samplers) or any(s.mt_state is None for s in samplers):
             raise ValueError("update_batch: samplers need equal max_iter and a GSL stream each (mt_state)")
@@ -204,7 +217,9 @@ class HaploSNP_Sampler:
         """max_iter Gibbs iterations with the LAST n_held haplotypes held and the others sampled, on the device
         (dsm_ctx_gibbs_update_held_tau; the reference has no counterpart).  Fills the stores, the star state and lp as update() does;
         the GSL stream advances by V (G - n_held) words per iteration.  fix_eta: eta is held as well.  n_held = 0 is update(),
-        n_held = G is update_fixed_tau(pool=0)."""
+        n_held = G is update_fixed_tau(pool=0).  Pair moves (pair_every > 0) have no held form: 0 < n_held < G is refused then."""
+        if self.pair_every > 0 and 0 < n_held < self.G:
+            raise ValueError("update_held: pair moves (pair_every = %d) have no partly held form (0 < n_held < G)" % self.pair_every)
         self._push_state()
         self._bind_rng()
         self._ctx.gibbs_update_held_tau(self.max_iter, n_held, fix_eta=fix_eta)

@@ -85,6 +85,10 @@ SIGNATURES = {
     "dsm_ctx_gibbs_update_fixed_tau": (_i, [_vp, _i, _i, _i]),
     "dsm_ctx_sample_tau_held": (_i, [_vp, _i, C.POINTER(_i)]),
     "dsm_ctx_gibbs_update_held_tau": (_i, [_vp, _i, _i, _i]),
+    "dsm_ctx_set_pair_moves": (_i, [_vp, _i]),
+    "dsm_ctx_get_pair_moves": (_i, [_vp, C.POINTER(_i)]),
+    "dsm_ctx_sample_tau_pairs": (_i, [_vp, C.c_uint32, C.POINTER(_i)]),
+    "dsm_pairtau_debug_path": (_i, [_i, _i, C.POINTER(_i)]),
     "dsm_ctx_debug_fixtau_pool": (_i, [_vp, C.POINTER(_i), _vp, _vp, _vp]),
     "dsm_ctx_debug_fixtau_sample_stats": (_i, [_vp, C.c_uint32, _u64p, _u64p]),
     "dsm_ctx_get_counters": (_i, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
@@ -354,6 +358,13 @@ def assign_sampled_debug_path(S, G):
     out = (C.c_int * 5)()
     check(load().dsm_assign_sampled_debug_path(int(S), int(G), out))
     return dict(zip(("inst", "lpv", "nsl", "gamma_chunk", "positions_per_workgroup"), [int(v) for v in out]))
+
+
+def pairtau_debug_path(S, G):
+    """test hook: (lanes per position, sample slots per lane) of the pair-pass kernel for S samples; nothing is launched"""
+    out = (C.c_int * 2)()
+    check(load().dsm_pairtau_debug_path(int(S), int(G), out))
+    return int(out[0]), int(out[1])
 
 
 def diag_debug_set_parts(parts=0):
@@ -790,6 +801,23 @@ class Context:
         dsm_ctx_sample_tau_held); returns the number of changed (position, haplotype) pairs"""
         n = _i(0)
         check(self.lib.dsm_ctx_sample_tau_held(self._h, int(n_held), C.byref(n)))
+        return n.value
+
+    def set_pair_moves(self, every):
+        """pair moves of gibbs_update (include/desman_hip.h: dsm_ctx_set_pair_moves): 0 = off, E > 0 = a pair pass after the sweep of
+        every iteration whose counter satisfies (iter_ctr + 1) mod E == 0"""
+        check(self.lib.dsm_ctx_set_pair_moves(self._h, int(every)))
+
+    def get_pair_moves(self):
+        e = _i(0)
+        check(self.lib.dsm_ctx_get_pair_moves(self._h, C.byref(e)))
+        return e.value
+
+    def sample_tau_pairs(self, iteration):
+        """one pair pass on the resident state with the resident gamma / eta, keyed by `iteration` (include/desman_hip.h:
+        dsm_ctx_sample_tau_pairs); returns the number of changed haplotype digits"""
+        n = _i(0)
+        check(self.lib.dsm_ctx_sample_tau_pairs(self._h, int(iteration) & 0xFFFFFFFF, C.byref(n)))
         return n.value
 
     def gibbs_update_held_tau(self, n_iter, n_held, fix_eta=False):

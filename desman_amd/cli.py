@@ -41,6 +41,9 @@ _FLAGS = [
 ]
 
 
+PAIR_MOVES = 5              # a bare --pair-moves: a pair pass after every fifth iteration -- the convention of `desman-assign --pairs`
+
+
 def build_parser():
     ap = argparse.ArgumentParser(prog="desman", description="strain haplotypes and abundances from base counts (MI355X)")
     ap.add_argument("variant_file", help="base-count table: Contig,Position,<sample>-A,-C,-G,-T,...")
@@ -76,7 +79,24 @@ def build_parser():
                          "positions, with -r also kind `heldout` = the log predictive density of the positions left out of the fit) and "
                          "Predictive_summary.csv; from N evenly spaced stored iterations (default 50, a convention); -g up to 10; "
                          "compare runs with `python -m desman_amd.predictive compare` (extension)")
+    ap.add_argument('--pair-moves', dest='pair_moves', nargs='?', const=PAIR_MOVES, default=None, type=int, metavar='E',
+                    help="add joint moves of two haplotypes to the Gibbs chain, burn-in and sampling alike: the sweep of every E-th "
+                         "iteration (default %d: a convention, not tuned) is followed by a pass that redraws the bases of every pair of "
+                         "haplotypes of a position from their 16-state conditional, so two haplotypes that carry each other's bases can "
+                         "swap them; the chain's law is unchanged; not for replicate chains that share their launches (extension)"
+                         % PAIR_MOVES)
     return ap
+
+
+def _pair_moves_options(opts, replicates=False):
+    """--pair-moves: refused here, before any chain, where it cannot be served; returns the pair_every of the sampler (0 = off)"""
+    if opts.pair_moves is None:
+        return 0
+    if replicates:
+        sys.exit("desman: --pair-moves is not available for replicate chains that share their launches: run the chains one by one")
+    if opts.pair_moves < 1:
+        sys.exit("desman: --pair-moves: a pair pass every E-th iteration needs E >= 1; got %d" % opts.pair_moves)
+    return opts.pair_moves
 
 
 _TABLES_LOCK = threading.Lock()
@@ -139,7 +159,8 @@ def _fit(opts, flt):
     logging.info('NMF-tensor initialisation')
     nmft.factorize()
     chain = HaploSNP_Sampler(flt.snps_filter, opts.genomes, rng, max_iter=opts.no_iter, device=opts.device,
-                             ctx=nmft._ctx)                        # same resident count tensor
+                             ctx=nmft._ctx,                        # same resident count tensor
+                             pair_every=_pair_moves_options(opts))
     chain.tau = np.copy(nmft.get_tau(), order='C')
     chain.updateTauIndices()
     chain.gamma = np.copy(nmft.get_gamma(), order='C')
@@ -338,6 +359,7 @@ def main(argv=None):
     if opts.genomes < 0:
         logging.error('the haplotype number must be positive, got %d' % opts.genomes)
         sys.exit(-1)
+    _pair_moves_options(opts)
     diag_len = _diagnose_batch_len(opts)
     _check_options(opts)
     _predictive_options(opts)
@@ -374,6 +396,7 @@ def main_replicates(argv_list, on_chain=None):
         opts = build_parser().parse_args(argv)
         if opts.assign_file is not None:
             sys.exit('desman: -a/--assign_file is not supported (dead in the reference: bin/desman:213-214)')
+        _pair_moves_options(opts, replicates=True)
         diag_len = _diagnose_batch_len(opts)
         _check_options(opts)
         _predictive_options(opts, replicates=True)

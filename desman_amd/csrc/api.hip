@@ -673,6 +673,36 @@ static int sample_tau_once(dsm_ctx *c, int n_held, int *nchange, double *logp_ou
 extern "C" int dsm_ctx_sample_tau(dsm_ctx *c, int *nchange, double *logp_out) { return sample_tau_once(c, 0, nchange, logp_out); }
 extern "C" int dsm_ctx_sample_tau_held(dsm_ctx *c, int n_held, int *nchange) { return sample_tau_once(c, n_held, nchange, nullptr); }
 
+// ---- pair moves of the main chain (kernels_pairtau.hip)
+extern "C" int dsm_ctx_set_pair_moves(dsm_ctx *c, int every)
+{
+    if (!c) { dsm_set_error("set_pair_moves: null context"); return DSM_ERR_ARG; }
+    if (every < 0) { dsm_set_error("set_pair_moves: every = %d is negative", every); return DSM_ERR_ARG; }
+    c->pair_every = every;
+    return DSM_OK;
+}
+extern "C" int dsm_ctx_get_pair_moves(dsm_ctx *c, int *every)
+{
+    if (!c || !every) { dsm_set_error("get_pair_moves: null argument"); return DSM_ERR_ARG; }
+    *every = c->pair_every;
+    return DSM_OK;
+}
+// one pair pass on the resident state with the resident gamma / eta, keyed by `iter`: neither the MT19937 stream nor the iteration
+// counter moves
+extern "C" int dsm_ctx_sample_tau_pairs(dsm_ctx *c, uint32_t iter, int *nchange)
+{
+    TRY(need(c, true, true));
+    BIND(c);
+    HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
+    TRY(k_pair_sweep(c, c->gamma, c->eta, iter));
+    int n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, c->nchange, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (nchange) *nchange = n;
+    return DSM_OK;
+}
+
 extern "C" int dsm_ctx_sample_stats(dsm_ctx *c, uint32_t iter, uint64_t *sum_mu, uint64_t *esum)
 {
     TRY(need(c, true, true));
@@ -903,8 +933,12 @@ static int gibbs_update(dsm_ctx *const *ctxs, int K, bool batched, int n_iter, T
     if (n_iter < 0) { dsm_set_error("n_iter < 0"); return DSM_ERR_ARG; }
     if (batched && step.n_held) { dsm_set_error("batch: no held haplotypes (the held sweep has no batched form)"); return DSM_ERR_UNSUPPORTED; }
     Chains ch{ctxs, K, batched};
-    TRY(ch.open(true, false, [](const dsm_ctx *a, const dsm_ctx *b, int k) -> int {
+    TRY(ch.open(true, false, [batched](const dsm_ctx *a, const dsm_ctx *b, int k) -> int {
         TRY(same_G_and_rng(a, b, k));
+        if (batched && b->pair_every > 0) {
+            dsm_set_error("batch: chain %d has pair moves on (dsm_ctx_set_pair_moves: every = %d); the pair pass has no batched form", k, b->pair_every);
+            return DSM_ERR_UNSUPPORTED;
+        }
         // one specification per batch (the launches are shared): chains of one shape on one table have the same by rule
         if (stats_spec(b) == stats_spec(a)) return DSM_OK;
         dsm_set_error("batch: chain %d runs mu/E specification %d, chain 0 specification %d (different tables or different dsm_ctx_force_stats_spec)", k, stats_spec(b), stats_spec(a));
@@ -912,6 +946,12 @@ static int gibbs_update(dsm_ctx *const *ctxs, int K, bool batched, int n_iter, T
     }));
     dsm_ctx *const lead = ch.lead();
     const bool full = step.n_held == 0, fixed = step.n_held == lead->G, fix_eta = step.fix_eta && !full;
+    // pair moves belong to the full chain run alone; the fixed-tau chain has no tau step and ignores the setting
+    if (!full && !fixed && lead->pair_every > 0) {
+        dsm_set_error("gibbs_update_held_tau: pair moves are on (dsm_ctx_set_pair_moves: every = %d); the pair pass has no held form", lead->pair_every);
+        return DSM_ERR_UNSUPPORTED;
+    }
+    const uint32_t pair_E = (full && !batched && lead->G > 1) ? (uint32_t)lead->pair_every : 0u;
     const int spec = stats_spec(lead);
     // sampleMu (:341): spec v2 = stage 1, then stage 2 inside the Dirichlet launch; spec v1 = the per-read pass
     const bool agg = spec >= 2;
@@ -979,13 +1019,17 @@ static int gibbs_update(dsm_ctx *const *ctxs, int K, bool batched, int n_iter, T
             }));
             TRY(ch.each([&](dsm_ctx *, int k) { return words[k].release(it); }));
         }
+        // a pair iteration: the pair pass with the (gamma_new, eta_old) the sweep conditioned on; the likelihood of the state it leaves
+        // takes the likelihood-only pass below, which overwrites what the sweep's launch stored (tau's trace slot, the ll partials)
+        const bool pair_it = pair_E && (ic[0] + 1u) % pair_E == 0;
+        if (pair_it) TRY(k_pair_sweep(lead, lead->gamma, lead->eta, ic[0]));
         TRY(ch.each([&](dsm_ctx *c, int) -> int {
             if (fix_eta) HIP_TRY(hipMemcpyAsync(prior_slot(c, it) + c->S, held.p + c->S, 4 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
             else std::swap(c->eta, c->eta_new);                          // eta_new becomes the chain's eta
             return DSM_OK;
         }));
         // held and fixed: the likelihood-only pass at (tau_new, gamma_new, eta_new); it stores tau_new where tau moves
-        if (!full)
+        if (!full || pair_it)
             TRY(ch.each([&](dsm_ctx *c, int k) {
                 return k_tau_sweep(c, 2, c->gamma, c->eta, c->eta, fixed ? nullptr : c->tau_trace + (size_t)(it + 1) * c->V, nullptr, 0, &nb_prev[k], nullptr);
             }));
@@ -1038,6 +1082,10 @@ int comm_device(const dsm_comm *m);
 static int gibbs_update_sharded(dsm_ctx *c, int n_iter, int v_offset, int v_total, dsm_exchange_fn exchange, void *user, dsm_comm *comm)
 {
     TRY(need(c, true, true));
+    if (c->pair_every > 0) {
+        dsm_set_error("gibbs_update_sharded: pair moves are on (dsm_ctx_set_pair_moves: every = %d); the pair pass has no sharded form", c->pair_every);
+        return DSM_ERR_UNSUPPORTED;
+    }
     c->tau_neartie_on = false;                           // (a sharded chain runs the sweep's plain instantiation)
     if (n_iter < 0 || (!exchange && !comm) || v_offset < 0 || v_total < v_offset + c->V) { dsm_set_error("gibbs_update_sharded: bad arguments"); return DSM_ERR_ARG; }
     if (comm && comm_device(comm) != c->device) { dsm_set_error("gibbs_update_sharded: the communicator lives on device %d, the context on %d", comm_device(comm), c->device); return DSM_ERR_ARG; }

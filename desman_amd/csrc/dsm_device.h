@@ -13,6 +13,7 @@
 #define DSM_STREAM_TAUU  0x54415555u   // 'TAUU'  tau-sweep uniforms (Philox mode)
 #define DSM_STREAM_ASMP  0x41534D50u   // 'ASMP'  dsm_assign_tau_sampled: chain c of a position draws from stream 'ASMP' + c
 #define DSM_STREAM_APAR  0x41504152u   // 'APAR'  dsm_assign_tau_sampled_pairs: the pair steps of chain c draw from stream 'APAR' + c
+#define DSM_STREAM_TPAR  0x54504152u   // 'TPAR'  pair moves of the Gibbs chain (kernels_pairtau.hip): the uniforms of the pair steps
 
 #define DSM_EPS 2.220446049250313e-16
 
@@ -637,4 +638,35 @@ __device__ __forceinline__ int transpose_index(int lane)
 #pragma unroll
     for (int off = 1; off < 64 && h >= 1; off <<= 1, h >>= 1) idx += (lane & off) ? h : 0;
     return idx;
+}
+
+// ---- pair candidates, shared by assign_sampled_kernel (kernels_assign_sampled.hip) and pair_sweep_kernel (kernels_pairtau.hip)
+// The four totals L[a'] of a thread's cells for the pair candidates (a, a') of haplotypes g and h, before they meet over the lanes:
+// m0..m3 = the rest mixture's weights without g and h, gg / gh = gamma of g / h at the thread's slots, eta [4][4] and the logarithm's
+// table in LDS.  Free of the kernel's tiling (a slot is any cell of the thread): the Gibbs sweep can take it over as it stands.
+template <int NSL>
+__device__ __forceinline__ void dsm_pair_candidates_row(const double (&x)[NSL][4], const double (&m0)[NSL], const double (&m1)[NSL],
+                                                        const double (&m2)[NSL], const double (&m3)[NSL], const double (&gg)[NSL],
+                                                        const double (&gh)[NSL], const double *eta, const double2 *ltab, int a,
+                                                        double (&L)[4])
+{
+    L[0] = 0.0; L[1] = 0.0; L[2] = 0.0; L[3] = 0.0;
+#pragma unroll
+    for (int j = 0; j < NSL; ++j) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const double rest = ((m0[j] * eta[b] + m1[j] * eta[4 + b]) + m2[j] * eta[8 + b]) + m3[j] * eta[12 + b];
+            const double with_g = rest + eta[a * 4 + b] * gg[j];
+            const bool seen = x[j][b] > 0.0;
+#pragma unroll
+            for (int a2 = 0; a2 < 4; ++a2) {
+                const double pr = with_g + eta[a2 * 4 + b] * gh[j];
+                double lg = 0.0;
+                if (__builtin_expect(dsm_log_ok(pr), 1)) lg = dsm_log_core(pr, ltab);
+                else if (seen) lg = dsm_log_slow(pr);               // 0 under a positive count: -inf (an unseen cell is never evaluated)
+                L[a2] += seen ? x[j][b] * lg : 0.0;
+            }
+            __builtin_amdgcn_sched_barrier(0);                      // one cell's four logarithms at a time: the next cell's are not issued early
+        }
+    }
 }

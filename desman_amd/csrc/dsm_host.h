@@ -131,6 +131,8 @@ struct dsm_ctx {
     uint64_t ctr_seed = 0x243F6A8885A308D3ull;
     uint32_t iter_ctr = 0;          // global iteration counter for counter-based draws
     int tau_rng = DSM_RNG_MT19937;
+    int pair_every = 0;             // dsm_ctx_set_pair_moves: E > 0 = a pair pass (kernels_pairtau.hip) after the sweep of every Gibbs iteration
+                                    // whose counter satisfies (iter_ctr + 1) mod E == 0; 0 = never
     // scratch
     double *ll_partial = nullptr;   // [DSM_MAX_GRID]
     int *nchange = nullptr;         // device counter
@@ -271,6 +273,11 @@ int k_fixtau_add_const(dsm_ctx *c, int n, double K);                            
 // ---- launchers (kernels_heldtau.hip)
 // one sweep over haplotypes 0 .. G - n_held - 1 of the resident tau (0 < n_held < G); u_raw = V (G - n_held) MT19937 words or, Philox, null
 int k_held_sweep(dsm_ctx *c, int n_held, const double *gamma, const double *eta, uint32_t iter, const uint32_t *u_raw);
+
+// ---- launcher (kernels_pairtau.hip)
+// one pair pass over the resident tau with (gamma, eta): every pair (g, h), g < h, re-drawn jointly; Philox uniforms keyed by `iter` in
+// every tau RNG mode; the changed digits are added to *c->nchange
+int k_pair_sweep(dsm_ctx *c, const double *gamma, const double *eta, uint32_t iter);
 
 // ---- launchers (kernels_relabel.hip): reductions of the tau trace; trace_stride = words between two iterations' rows (0: one row for all)
 int k_trace_snd(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const uint64_t *ref, int Gr, int n_it, int *d_out);   // ref null: each iteration against itself

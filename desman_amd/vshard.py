@@ -113,7 +113,9 @@ class HostExchange:
 class ShardedChain:
     """this rank's shard of the chain: a device context holding positions v_offset .. v_offset + V of v_total"""
 
-    def __init__(self, counts_slice, v_offset, v_total, G, seed, device=0, ctr_seed=None):
+    def __init__(self, counts_slice, v_offset, v_total, G, seed, device=0, ctr_seed=None, pair_every=0):
+        if pair_every:
+            raise ValueError("sharded chain: pair moves (pair_every = %r) have no sharded form" % (pair_every,))
         counts_slice = np.ascontiguousarray(counts_slice, dtype=np.int64)
         self.V, self.S, self.G = counts_slice.shape[0], counts_slice.shape[1], int(G)
         self.v_offset, self.v_total = int(v_offset), int(v_total)

@@ -228,6 +228,30 @@ int dsm_ctx_debug_fixtau_sample_stats(dsm_ctx *ctx, uint32_t iter, uint64_t *sum
 int dsm_ctx_sample_tau_held(dsm_ctx *ctx, int n_held, int *nchange);
 int dsm_ctx_gibbs_update_held_tau(dsm_ctx *ctx, int n_iter, int n_held, int fix_eta);
 
+/* Pair moves of the main chain: an opt-in block-Gibbs step that redraws two haplotypes of a position jointly, so that
+ * two haplotypes carrying each other's bases can swap them without passing through the state in which both carry the same base.
+ *   dsm_ctx_set_pair_moves: every = 0 (the default) is off; E > 0 = in dsm_ctx_gibbs_update a pair pass follows the single-site sweep of
+ *     every iteration whose counter satisfies (iter_ctr + 1) mod E == 0, iter_ctr being the value the iteration takes (it persists across
+ *     calls and through dsm_ctx_get_counters / dsm_ctx_set_counters: a chain is the same whether its iterations come in one call or
+ *     several, and after a checkpoint).  On such an iteration the sweep runs as always, the pair pass runs with the gamma and the eta the
+ *     sweep conditioned on, and a likelihood-only pass at (tau after the pairs, new gamma, new eta) stores tau in the iteration's trace
+ *     slot and gives ll, lp and the MAP record; the iteration's nchange is the sweep's count plus the pass's.  Every other iteration
+ *     launches what it launches without the setting.  every < 0: DSM_ERR_ARG.  With E > 0 dsm_batch_gibbs_update, the partly held chain
+ *     (0 < n_held < G) and both sharded forms return DSM_ERR_UNSUPPORTED; the fixed-tau chain has no tau step and ignores the setting;
+ *     dsm_ctx_update_tau keeps the single-site sweep.
+ *   dsm_ctx_sample_tau_pairs: one pair pass on the resident state with the resident gamma / eta, keyed by `iter`; the counterpart of
+ *     dsm_ctx_sample_tau_held.  The pass visits the pairs (g, h), g < h, of every position in lexicographic order; a step is the pair
+ *     step of dsm_assign_tau_sampled_pairs (sixteen totals L_k, k = 4 a + a', q_k = exp(L_k - max) / (e_0 + ... + e_15), inverse CDF over
+ *     ascending k with the last edge forced; all sixteen -inf: the pair stays).  The uniform of step (v, g, h) is word 0 / 2^32 of
+ *     Philox4x32-10(key = the context's counter seed (lo32, hi32); counter = (lo32 j, hi32 j, iter, 'TPAR')), j = v G^2 + g G + h, in
+ *     every tau RNG mode: the MT19937 stream and the iteration counter are not touched.  *nchange = haplotype digits that differ from
+ *     their value before their step (0, 1 or 2 per step).  G < 2: nothing to do.
+ *   dsm_pairtau_debug_path: test hook, out = {lanes per position, sample slots per lane} of the kernel instantiation for S samples. */
+int dsm_ctx_set_pair_moves(dsm_ctx *ctx, int every);
+int dsm_ctx_get_pair_moves(dsm_ctx *ctx, int *every);
+int dsm_ctx_sample_tau_pairs(dsm_ctx *ctx, uint32_t iter, int *nchange);
+int dsm_pairtau_debug_path(int S, int G, int out[2]);
+
 /* results of the last update call.  Any pointer may be NULL.                 */
 int dsm_ctx_get_trace(dsm_ctx *ctx, double *ll, double *lp, int32_t *nchange,
                       double *gamma_store, double *eta_store);
