@@ -640,7 +640,7 @@ __device__ __forceinline__ int transpose_index(int lane)
     return idx;
 }
 
-// ---- pair candidates, shared by assign_sampled_kernel (kernels_assign_sampled.hip) and pair_sweep_kernel (kernels_pairtau.hip)
+// ---- the pair step, shared by assign_sampled_kernel (kernels_assign_sampled.hip) and pair_sweep_kernel (kernels_pairtau.hip)
 // The four totals L[a'] of a thread's cells for the pair candidates (a, a') of haplotypes g and h, before they meet over the lanes:
 // m0..m3 = the rest mixture's weights without g and h, gg / gh = gamma of g / h at the thread's slots, eta [4][4] and the logarithm's
 // table in LDS.  Free of the kernel's tiling (a slot is any cell of the thread): the Gibbs sweep can take it over as it stands.
@@ -669,4 +669,57 @@ __device__ __forceinline__ void dsm_pair_candidates_row(const double (&x)[NSL][4
             __builtin_amdgcn_sched_barrier(0);                      // one cell's four logarithms at a time: the next cell's are not issued early
         }
     }
+}
+
+// row a of sixteen values kept in registers: selects, not indexed accesses
+__device__ __forceinline__ void dsm_put_row(double (&L)[16], int a, const double (&R)[4])
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const bool here = a == k;
+        L[4 * k] = here ? R[0] : L[4 * k]; L[4 * k + 1] = here ? R[1] : L[4 * k + 1];
+        L[4 * k + 2] = here ? R[2] : L[4 * k + 2]; L[4 * k + 3] = here ? R[3] : L[4 * k + 3];
+    }
+}
+__device__ __forceinline__ void dsm_get_row(const double (&L)[16], int a, double (&R)[4])
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i) R[i] = a == 0 ? L[i] : (a == 1 ? L[4 + i] : (a == 2 ? L[8 + i] : L[12 + i]));
+}
+
+// The sixteen-way draw of a pair step: e_k = exp(L_k - mx), 0 where L_k = -inf, mx the largest total (not -inf); sum = e_0 + ... + e_15
+// added in this order; the new pair is the first k < 15 with u < q_0 + ... + q_k, q_k = e_k / sum added in ascending k, else 15 (the
+// last edge is forced).  Two forms of the exponentials, the same operations in the same order, because neither leaves both callers'
+// register numbers alone: ROWS (four at a time under `#pragma unroll 1`) is assign_sampled_kernel's, written for its register budget --
+// in pair_sweep_kernel it costs 8 VGPRs on every 16- and 32-lane tiling (143 -> 151 ... 246 -> 254); unrolled, pair_sweep_kernel's form,
+// moves assign_sampled_kernel's four-slot instantiations (315 -> 313 VGPRs, other SGPR spill counts), at a speed nobody measured.
+template <bool ROWS>
+__device__ __forceinline__ int dsm_pair_draw16(const double (&L)[16], double mx, double u)
+{
+    const double NINF = -INFINITY;
+    double e[16], sum = 0.0;
+    if (ROWS) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) e[k] = 0.0;
+#pragma unroll 1
+        for (int a = 0; a < 4; ++a) {
+            double r[4];
+            dsm_get_row(L, a, r);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { r[i] = r[i] == NINF ? 0.0 : exp(r[i] - mx); sum += r[i]; }
+            dsm_put_row(e, a, r);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) { e[k] = L[k] == NINF ? 0.0 : exp(L[k] - mx); sum += e[k]; }
+    }
+    double cdf = 0.0;
+    int kn = 15;
+    bool found = false;
+#pragma unroll
+    for (int k = 0; k < 15; ++k) {
+        cdf += e[k] / sum;
+        if (!found && u < cdf) { kn = k; found = true; }
+    }
+    return kn;
 }

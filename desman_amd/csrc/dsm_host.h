@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/desman_hip.h"
@@ -260,6 +261,19 @@ int k_tau_sweep(dsm_ctx *c, int mode, const double *gamma, const double *eta_swe
                 const uint32_t *u_raw, int slot = 0, const TauFinalRider *rider = nullptr);
 int tau_launch_info(dsm_ctx *c, int *launched, int *resident);
 int tau_shape(int S, int *lpv, int *nsl);      // lanes per position and sample slots per lane of the sweep kernels for S samples
+// Every (lanes, slots) tau_shape returns, written once: the kernels on this tiling (tau_kernel*, held_sweep_kernel, pair_sweep_kernel)
+// are instantiated for these and no others.  X(L, N) is expanded as a statement.
+#define DSM_TAU_TILINGS(X) X(16, 1); X(16, 2); X(16, 3); X(32, 2); X(32, 3); X(64, 2); X(64, 3); X(64, 4); X(64, 6); X(64, 8);
+// The list as a call: f(L, N), the tiling as std::integral_constant; DSM_ERR_UNSUPPORTED for a pair that is not listed.  (kernels_gibbs.hip
+// expands the list itself: instantiated from inside a lambda, one form of tau_kernel comes out with another SGPR count.)
+template <class F>
+static inline int tau_tiling_dispatch(int lpv, int nsl, F &&f)
+{
+#define DSM_TILING(L, N) if (lpv == L && nsl == N) return f(std::integral_constant<int, L>(), std::integral_constant<int, N>())
+    DSM_TAU_TILINGS(DSM_TILING)
+#undef DSM_TILING
+    return DSM_ERR_UNSUPPORTED;
+}
 int k_shard_pack(dsm_ctx *c, int nblocks);
 int k_shard_unpack(dsm_ctx *c);
 int k_finalize(dsm_ctx *c, int nblocks, int it, int star_mode, const double *prior, const double *gamma_src,

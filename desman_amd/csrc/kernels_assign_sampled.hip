@@ -77,8 +77,8 @@ struct SampledParams {
     int E;                      // a pair pass after every E-th sweep (PAIRS instantiations; 0 otherwise)
 };
 
-// (dsm_pair_candidates_row, the sixteen pair totals four at a time, lives in dsm_device.h: the pair pass of the Gibbs chain,
-// kernels_pairtau.hip, shares it)
+// (dsm_pair_candidates_row, the sixteen pair totals four at a time, dsm_put_row / dsm_get_row and the sixteen-way draw dsm_pair_draw16
+// live in dsm_device.h: the pair pass of the Gibbs chain, kernels_pairtau.hip, shares them)
 template <int NSL, bool ONE, bool PAIRS>
 __global__ __launch_bounds__(256) void assign_sampled_kernel(const SampledParams p)
 {
@@ -117,36 +117,49 @@ __global__ __launch_bounds__(256) void assign_sampled_kernel(const SampledParams
         x[j][0] = (double)q.x; x[j][1] = (double)q.y; x[j][2] = (double)q.z; x[j][3] = (double)q.w;
     }
 
-    // the four candidate totals of site g of `state`, the same bits on every lane of the group
-    auto candidates = [&](uint64_t state, int g, double (&L)[4]) {
-        double m0[NSL], m1[NSL], m2[NSL], m3[NSL], gg[NSL];
+    // The masses of a step at the thread's slots, one pass over the haplotypes in order: m_a = the abundance of those that carry base a in
+    // `state`, the step's own left out -- site g (gamma -> gg) and, `pair` a std::true_type, site h (gamma -> gh; else h and gh are not
+    // looked at).  !ONE: the one place that stages gamma, chunk by chunk between its two barriers; every thread comes through here
+    auto masses = [&](auto pair, uint64_t state, int g, int h, double (&m0)[NSL], double (&m1)[NSL], double (&m2)[NSL], double (&m3)[NSL],
+                      double (&gg)[NSL], double (&gh)[NSL]) __attribute__((always_inline)) {
+        constexpr bool PAIR = decltype(pair)::value;
 #pragma unroll
-        for (int j = 0; j < NSL; ++j) { m0[j] = 0.0; m1[j] = 0.0; m2[j] = 0.0; m3[j] = 0.0; gg[j] = 0.0; }
+        for (int j = 0; j < NSL; ++j) {
+            m0[j] = 0.0; m1[j] = 0.0; m2[j] = 0.0; m3[j] = 0.0; gg[j] = 0.0;
+            if constexpr (PAIR) gh[j] = 0.0;
+        }
         for (int g0 = 0; g0 < G; g0 += gc) {
             const int gn = min(gc, G - g0);
             if (!ONE) {
                 __syncthreads();                                    // the readers of the previous chunk are done
                 for (int i = tid; i < gn * SP; i += nthr) {
-                    const int hh = i / SP, s = i - hh * SP;
-                    lgam[i] = s < S ? p.gamma[(size_t)s * G + g0 + hh] : 0.0;
+                    const int kk = i / SP, s = i - kk * SP;
+                    lgam[i] = s < S ? p.gamma[(size_t)s * G + g0 + kk] : 0.0;
                 }
                 __syncthreads();
             }
-            for (int hh = 0; hh < gn; ++hh) {
-                const int h = g0 + hh;
-                const bool self = h == g;
-                const int d = self ? 4 : (int)(state >> (2 * h)) & 3;
+            for (int kk = 0; kk < gn; ++kk) {
+                const int k = g0 + kk;
+                const bool isg = k == g, ish = PAIR && k == h;
+                const int d = (isg || ish) ? 4 : (int)(state >> (2 * k)) & 3;
 #pragma unroll
                 for (int j = 0; j < NSL; ++j) {
-                    const double ga = lgam[hh * SP + l + j * LPV];
+                    const double ga = lgam[kk * SP + l + j * LPV];
                     m0[j] += d == 0 ? ga : 0.0;
                     m1[j] += d == 1 ? ga : 0.0;
                     m2[j] += d == 2 ? ga : 0.0;
                     m3[j] += d == 3 ? ga : 0.0;
-                    gg[j] = self ? ga : gg[j];
+                    gg[j] = isg ? ga : gg[j];
+                    if constexpr (PAIR) gh[j] = ish ? ga : gh[j];
                 }
             }
         }
+    };
+
+    // the four candidate totals of site g of `state`, the same bits on every lane of the group
+    auto candidates = [&](uint64_t state, int g, double (&L)[4]) {
+        double m0[NSL], m1[NSL], m2[NSL], m3[NSL], gg[NSL];
+        masses(std::false_type(), state, g, 0, m0, m1, m2, m3, gg, gg);
         L[0] = 0.0; L[1] = 0.0; L[2] = 0.0; L[3] = 0.0;
 #pragma unroll
         for (int j = 0; j < NSL; ++j) {
@@ -174,34 +187,7 @@ __global__ __launch_bounds__(256) void assign_sampled_kernel(const SampledParams
     // sixteen is its own choice (eight slots per lane leave no registers for all of them)
     auto pair_rows = [&](uint64_t state, int g, int h, auto &&row) __attribute__((always_inline)) {
         double m0[NSL], m1[NSL], m2[NSL], m3[NSL], gg[NSL], gh[NSL];
-#pragma unroll
-        for (int j = 0; j < NSL; ++j) { m0[j] = 0.0; m1[j] = 0.0; m2[j] = 0.0; m3[j] = 0.0; gg[j] = 0.0; gh[j] = 0.0; }
-        for (int g0 = 0; g0 < G; g0 += gc) {
-            const int gn = min(gc, G - g0);
-            if (!ONE) {
-                __syncthreads();                                    // the readers of the previous chunk are done
-                for (int i = tid; i < gn * SP; i += nthr) {
-                    const int kk = i / SP, s = i - kk * SP;
-                    lgam[i] = s < S ? p.gamma[(size_t)s * G + g0 + kk] : 0.0;
-                }
-                __syncthreads();
-            }
-            for (int kk = 0; kk < gn; ++kk) {
-                const int k = g0 + kk;
-                const bool isg = k == g, ish = k == h;
-                const int d = (isg || ish) ? 4 : (int)(state >> (2 * k)) & 3;
-#pragma unroll
-                for (int j = 0; j < NSL; ++j) {
-                    const double ga = lgam[kk * SP + l + j * LPV];
-                    m0[j] += d == 0 ? ga : 0.0;
-                    m1[j] += d == 1 ? ga : 0.0;
-                    m2[j] += d == 2 ? ga : 0.0;
-                    m3[j] += d == 3 ? ga : 0.0;
-                    gg[j] = isg ? ga : gg[j];
-                    gh[j] = ish ? ga : gh[j];
-                }
-            }
-        }
+        masses(std::true_type(), state, g, h, m0, m1, m2, m3, gg, gh);
 #pragma unroll 1
         for (int a = 0; a < 4; ++a) {                               // four candidates at a time: the register budget of a single-site step
             double R[4];
@@ -211,19 +197,6 @@ __global__ __launch_bounds__(256) void assign_sampled_kernel(const SampledParams
             }
             row(a, R);
         }
-    };
-    // row a of sixteen values kept in registers: selects, not indexed accesses
-    auto put_row = [](double (&L)[16], int a, const double (&R)[4]) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const bool here = a == k;
-            L[4 * k] = here ? R[0] : L[4 * k]; L[4 * k + 1] = here ? R[1] : L[4 * k + 1];
-            L[4 * k + 2] = here ? R[2] : L[4 * k + 2]; L[4 * k + 3] = here ? R[3] : L[4 * k + 3];
-        }
-    };
-    auto get_row = [](const double (&L)[16], int a, double (&R)[4]) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) R[i] = a == 0 ? L[i] : (a == 1 ? L[4 + i] : (a == 2 ? L[8 + i] : L[12 + i]));
     };
     constexpr bool KEEP16 = NSL < 8;    // the chain's pair step keeps the sixteen totals; at eight slots it forms them three times instead
 
@@ -273,7 +246,7 @@ __global__ __launch_bounds__(256) void assign_sampled_kernel(const SampledParams
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
                             if (R[i] > mx) { mx = R[i]; kmax = 4 * a + i; }
-                        if (KEEP16) put_row(L, a, R);
+                        if (KEEP16) dsm_put_row(L, a, R);
                     });
                     // all sixteen -inf: the pair stays, its uniform is spent unseen.  The decision is per chain (group-uniform only), so
                     // it may skip code only where no barrier follows: with the sixteen kept nothing below stages gamma; without them
@@ -286,27 +259,12 @@ __global__ __launch_bounds__(256) void assign_sampled_kernel(const SampledParams
                     uint32_t w[4];
                     philox4x32_10((uint32_t)jj, (uint32_t)(jj >> 32), (uint32_t)t, DSM_STREAM_APAR + (uint32_t)c, p.k0, p.k1, w);
                     const double u = (double)w[0] * 2.3283064365386963e-10;
-                    double sum = 0.0, cdf = 0.0;
                     int kn = 15;                                    // the last edge is forced
-                    bool found = false;
                     if (KEEP16) {
-                        double e[16];
-#pragma unroll
-                        for (int k = 0; k < 16; ++k) e[k] = 0.0;
-#pragma unroll 1
-                        for (int a = 0; a < 4; ++a) {               // four exponentials at a time, e_k added in ascending k
-                            double r[4];
-                            get_row(L, a, r);
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) { r[i] = r[i] == NINF ? 0.0 : exp(r[i] - mx); sum += r[i]; }
-                            put_row(e, a, r);
-                        }
-#pragma unroll
-                        for (int k = 0; k < 15; ++k) {
-                            cdf += e[k] / sum;
-                            if (!found && u < cdf) { kn = k; found = true; }
-                        }
+                        kn = dsm_pair_draw16<true>(L, mx, u);
                     } else {                                        // the same totals again, bit for bit: twice more
+                        double sum = 0.0, cdf = 0.0;
+                        bool found = false;
                         pair_rows(state, g, h, [&](int, const double (&R)[4]) {
 #pragma unroll
                             for (int i = 0; i < 4; ++i) sum += (!live || R[i] == NINF) ? 0.0 : exp(R[i] - mx);

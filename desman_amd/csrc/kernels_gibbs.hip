@@ -1682,8 +1682,7 @@ int k_tau_sweep(dsm_ctx *c, int mode, const double *gamma, const double *eta_swe
     const size_t sh = tau_lds_bytes(G, LPV, NSL);
     if (sh > 160 * 1024) { dsm_set_error("gamma tile (%zu B) exceeds LDS", sh); return DSM_ERR_UNSUPPORTED; }
 #define TAU_CASE(L, N) if (LPV == L && NSL == N) launch_tau<L, N>(c, mode, p, grid, sh)
-    TAU_CASE(16, 1); TAU_CASE(16, 2); TAU_CASE(16, 3); TAU_CASE(32, 1); TAU_CASE(32, 2); TAU_CASE(32, 3); TAU_CASE(64, 1); TAU_CASE(64, 2); TAU_CASE(64, 3); TAU_CASE(64, 4);
-    TAU_CASE(64, 6); TAU_CASE(64, 8);
+    DSM_TAU_TILINGS(TAU_CASE)
 #undef TAU_CASE
     HIP_TRY(hipGetLastError());
     if (nblocks) *nblocks = grid;
@@ -1702,8 +1701,7 @@ int tau_launch_info(dsm_ctx *c, int *launched, int *resident)
     const size_t sh = tau_lds_bytes(c->G, LPV, NSL);
     int per_cu = 0, cus = 0;
 #define TAU_CASE(L, N) if (LPV == L && NSL == N) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tau_kernel<L, N, true, true>, 256, sh))
-    TAU_CASE(16, 1); TAU_CASE(16, 2); TAU_CASE(16, 3); TAU_CASE(32, 1); TAU_CASE(32, 2); TAU_CASE(32, 3); TAU_CASE(64, 1); TAU_CASE(64, 2); TAU_CASE(64, 3); TAU_CASE(64, 4);
-    TAU_CASE(64, 6); TAU_CASE(64, 8);
+    DSM_TAU_TILINGS(TAU_CASE)
 #undef TAU_CASE
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
     *launched = grid;

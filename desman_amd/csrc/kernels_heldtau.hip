@@ -5,24 +5,14 @@
 //                                 packed word are only read
 //
 // The chain around it runs on the launchers of the Gibbs loop (kernels_stats.hip, kernels_gibbs.hip).
-#include <algorithm>
+#include "dsm_sweep_tile.h"
 
-#include "dsm_device.h"
-#include "dsm_host.h"
-#include "log_table.h"
-
-struct HeldParams {
-    const int32_t *cnt_vs;     // [V][S][4]
-    uint64_t *tau;             // [V] packed, 2 bits per haplotype
-    const double *gamma, *eta; // [S][G], [4][4]
+struct HeldParams : SweepTileParams {
     const uint32_t *u_raw;     // MT19937 words, [V][F]; null -> Philox
-    const double *log_tab;     // [256][2]
-    int *nchange;
-    int V, S, G, F;
-    uint32_t k0, k1, iter;
+    int F;                     // free haplotypes
 };
 
-// One group of LPV lanes per position, NSL sample slots per lane (slot j of lane l = sample l + j LPV; kernels_gibbs.hip: tau_shape).
+// The frame of dsm_sweep_tile.h: one group of LPV lanes per position, NSL sample slots per lane (slot j of lane l = sample l + j LPV).
 // Step g < F is the step of c_sample_tau.c:136-190 in plain fp64: the rest mixture is the h-ascending fma chain over ALL h != g --
 // the links h < g (already re-drawn, final for this sweep) are carried from step to step, the links h > g, the held haplotypes among
 // them, are re-done: the same operations in the same order as the chain from zero --, the four candidates are lane-partial sums
@@ -34,34 +24,24 @@ struct HeldParams {
 template <int LPV, int NSL>
 __global__ __launch_bounds__(256) void held_sweep_kernel(HeldParams p)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem_h[];
     constexpr int SP = LPV * NSL;
     constexpr int GPB = 256 / LPV;
     const int tid = threadIdx.x, G = p.G, S = p.S, F = p.F;
-    double *gT = reinterpret_cast<double *>(smem_h);                 // [G][SP]
-    double *eS = gT + (size_t)G * SP;                                  // [16]
-    double2 *ltab = reinterpret_cast<double2 *>(eS + 16);             // [256] log table
-    __shared__ int redi[4];
-    if (tid < DSM_LOG_TAB_N) ltab[tid] = reinterpret_cast<const double2 *>(p.log_tab)[tid];
-    for (int i = tid; i < G * SP; i += 256) {
-        const int g = i / SP, s = i % SP;
-        gT[i] = (s < S) ? p.gamma[(size_t)s * G + g] : 1.0;         // padded slot: abundance 1, count 0 (dsm_device.h: sweep_candidate)
-    }
-    if (tid < 16) eS[tid] = p.eta[tid];
-    __syncthreads();
+    const SweepTileLds lds = sweep_tile_stage<LPV, NSL>(p, 1.0);      // padded slot: abundance 1, count 0 (dsm_device.h: sweep_candidate)
+    const double *gT = lds.gT, *eS = lds.eS;
+    const double2 *ltab = lds.ltab;
 
     const int grp = tid / LPV, lig = tid % LPV;
     int nchg = 0;
     for (int v = (int)blockIdx.x * GPB + grp; v < p.V; v += (int)gridDim.x * GPB) {
         uint64_t t = p.tau[v];
+        int4 c[NSL];
+        sweep_tile_counts<LPV, NSL>(p, v, lig, c);
         double xf[NSL][4], pre[NSL][4];
 #pragma unroll
         for (int j = 0; j < NSL; ++j) {
-            const int s = lig + j * LPV;
-            int4 c = make_int4(0, 0, 0, 0);
-            if (s < S) c = reinterpret_cast<const int4 *>(p.cnt_vs)[(size_t)v * S + s];
-            xf[j][0] = (double)(float)c.x; xf[j][1] = (double)(float)c.y;      // c_sample_tau.c:164
-            xf[j][2] = (double)(float)c.z; xf[j][3] = (double)(float)c.w;
+            xf[j][0] = (double)(float)c[j].x; xf[j][1] = (double)(float)c[j].y;      // c_sample_tau.c:164
+            xf[j][2] = (double)(float)c[j].z; xf[j][3] = (double)(float)c[j].w;
 #pragma unroll
             for (int b = 0; b < 4; ++b) pre[j][b] = 0.0;
         }
@@ -115,27 +95,7 @@ __global__ __launch_bounds__(256) void held_sweep_kernel(HeldParams p)
         }
         if (lig == 0) p.tau[v] = t;
     }
-    const int wn = (int)group_allreduce_sum_u32<64>((unsigned)nchg);
-    if ((tid & 63) == 0) redi[tid >> 6] = wn;
-    __syncthreads();
-    if (tid == 0) {
-        const int tot = redi[0] + redi[1] + redi[2] + redi[3];
-        if (tot) atomicAdd(p.nchange, tot);
-    }
-}
-
-static size_t held_lds_bytes(int G, int LPV, int NSL) { return ((size_t)G * LPV * NSL + 16 + 2 * DSM_LOG_TAB_N) * sizeof(double); }
-
-template <int LPV, int NSL>
-static int launch_held(dsm_ctx *c, const HeldParams &p, int grid, size_t sh)
-{
-    static bool attr_set = false;                  // more than 64 KB of dynamic LDS has to be asked for, once per instantiation
-    if (sh > 64 * 1024 && !attr_set) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&held_sweep_kernel<LPV, NSL>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((held_sweep_kernel<LPV, NSL>), dim3(grid), dim3(256), sh, c->stream, p);
-    return DSM_OK;
+    sweep_tile_nchange(p.nchange, nchg);
 }
 
 // One held sweep of the resident tau: haplotypes 0 .. G - n_held - 1 re-drawn with (gamma, eta), changed (v, g) pairs added to *c->nchange.
@@ -145,10 +105,6 @@ int k_held_sweep(dsm_ctx *c, int n_held, const double *gamma, const double *eta,
     KTimer tm(c, DSM_K_TAU);
     const int S = c->S, G = c->G, V = c->V;
     if (n_held < 1 || n_held >= G) { dsm_set_error("held sweep: n_held = %d outside 1..%d", n_held, G - 1); return DSM_ERR_ARG; }
-    int LPV, NSL;
-    { const int rc = tau_shape(S, &LPV, &NSL); if (rc != DSM_OK) return rc; }
-    const int gpb = 256 / LPV;
-    const int grid = std::max(1, std::min((V + gpb - 1) / gpb, DSM_MAX_GRID));
     HeldParams p;
     p.cnt_vs = c->cnt_vs; p.tau = c->tau; p.gamma = gamma; p.eta = eta;
     p.u_raw = c->tau_rng == DSM_RNG_MT19937 ? u_raw : nullptr;
@@ -156,15 +112,7 @@ int k_held_sweep(dsm_ctx *c, int n_held, const double *gamma, const double *eta,
     p.log_tab = c->log_tab; p.nchange = c->nchange;
     p.V = V; p.S = S; p.G = G; p.F = G - n_held;
     p.k0 = (uint32_t)c->ctr_seed; p.k1 = (uint32_t)(c->ctr_seed >> 32); p.iter = iter;
-    const size_t sh = held_lds_bytes(G, LPV, NSL);
-    if (sh > 160 * 1024) { dsm_set_error("gamma tile (%zu B) exceeds LDS", sh); return DSM_ERR_UNSUPPORTED; }
-    int rc = DSM_ERR_UNSUPPORTED;
-    // every (LPV, NSL) tau_shape returns
-#define HELD_CASE(L, N) if (LPV == L && NSL == N) rc = launch_held<L, N>(c, p, grid, sh)
-    HELD_CASE(16, 1); HELD_CASE(16, 2); HELD_CASE(16, 3); HELD_CASE(32, 2); HELD_CASE(32, 3);
-    HELD_CASE(64, 2); HELD_CASE(64, 3); HELD_CASE(64, 4); HELD_CASE(64, 6); HELD_CASE(64, 8);
-#undef HELD_CASE
-    if (rc != DSM_OK) { if (rc == DSM_ERR_UNSUPPORTED) dsm_set_error("held sweep: no kernel for %d lanes x %d samples", LPV, NSL); return rc; }
-    HIP_TRY(hipGetLastError());
-    return DSM_OK;
+    return sweep_tile_dispatch(p, "", "held sweep", [&](auto L, auto N, int grid, size_t sh) {
+        return sweep_tile_launch<held_sweep_kernel<L.value, N.value>>(c, p, grid, sh);
+    });
 }

@@ -50,6 +50,16 @@ def _helds(G):
 
 # ---- 1. one sweep against the oracle composition -----------------------------------------------------------------------------------
 VS, SS, GS = (1, 63, 65, 257), (1, 3, 16, 17, 33, 64, 65, 130), (2, 3, 5, 8, 12, 16)
+WIDE_VS, WIDE_SS, WIDE_GS = (1, 63), (100, 200, 300, 400), (2, 3)       # the tilings SS leaves out: 64 x 2, 64 x 4, 64 x 6, 64 x 8
+TILINGS = {(16, 1), (16, 2), (16, 3), (32, 2), (32, 3), (64, 2), (64, 3), (64, 4), (64, 6), (64, 8)}   # dsm_host.h: DSM_TAU_TILINGS
+
+
+def test_the_sample_counts_reach_every_tiling_of_the_launcher():
+    """the twin of tests/test_gpu_tau_pairs.py: test_the_shapes_reach_every_instantiation_of_the_launcher.  The held sweep has no hook of
+    its own: k_held_sweep and k_pair_sweep take their tiling from the same tau_shape through the same sweep_tile_dispatch
+    (dsm_sweep_tile.h), so the pair pass's pairtau_debug_path answers for both"""
+    assert {_lib.pairtau_debug_path(S, 2) for S in SS + WIDE_SS} == TILINGS
+    assert {_lib.pairtau_debug_path(S, 2) for S in WIDE_SS} == {(64, 2), (64, 4), (64, 6), (64, 8)}
 
 
 @pytest.mark.parametrize("eta_kind", ["random", "identity", "zero-row"])
@@ -73,6 +83,33 @@ def test_one_held_sweep_is_the_oracle_composition(ctx, S, rng, eta_kind):
                     u = cbind.MT19937(MT_SEED).uniform(V * Fr) if rng == "mt" else H.philox_free_uniforms(CTR_SEED, 0, V, G, n_held)
                     want, n_ref = H.held_sweep(tau, gamma, eta, counts, u, n_held)
                     where = "V=%d S=%d G=%d n_held=%d %s %s" % (V, S, G, n_held, rng, eta_kind)
+                    assert np.array_equal(got[:, Fr:], tau[:, Fr:]), where
+                    assert np.array_equal(got, want) and n == n_ref, where
+                    assert ctx.counters() == (CTR_SEED, 1), where
+    finally:
+        ctx.set_tau_rng(_lib.RNG_MT19937)
+
+
+@pytest.mark.parametrize("rng", ["mt", "philox"])
+@pytest.mark.parametrize("S", WIDE_SS)
+def test_one_held_sweep_on_the_wide_tilings(ctx, S, rng):
+    """the check above on 64 x 2 / 4 / 6 / 8 (S = 100 / 200 / 300 / 400), at the smallest shapes where their grid-stride tail (V = 63: the
+    last workgroup has groups beyond V), a lone group (V = 1) and their padded slots (every S here leaves some) can go wrong"""
+    mode = _lib.RNG_MT19937 if rng == "mt" else _lib.RNG_PHILOX
+    try:
+        for V in WIDE_VS:
+            for G in WIDE_GS:
+                counts, _, _ = synth_counts(V, S, G, seed=V + S)
+                tau, gamma, _ = random_state(V, S, G, seed=G)
+                eta = H.etas("random", seed=G)
+                for n_held in _helds(G):
+                    _load(ctx, counts, tau, gamma, eta, rng=mode)
+                    n = ctx.sample_tau_held(n_held)
+                    got = ctx.get_state()[0]
+                    Fr = G - n_held
+                    u = cbind.MT19937(MT_SEED).uniform(V * Fr) if rng == "mt" else H.philox_free_uniforms(CTR_SEED, 0, V, G, n_held)
+                    want, n_ref = H.held_sweep(tau, gamma, eta, counts, u, n_held)
+                    where = "V=%d S=%d G=%d n_held=%d %s" % (V, S, G, n_held, rng)
                     assert np.array_equal(got[:, Fr:], tau[:, Fr:]), where
                     assert np.array_equal(got, want) and n == n_ref, where
                     assert ctx.counters() == (CTR_SEED, 1), where

@@ -74,7 +74,7 @@ SHAPES = [(1, 1, 2), (63, 9, 3), (257, 16, 8), (63, 17, 17), (257, 33, 3), (63, 
           (257, 1, 3), (1, 100, 3), (63, 200, 2), (1, 300, 3), (63, 400, 2)]
 DEPTH = 0.05       # of synth_counts' depth (about ten reads per sample): at full depth nearly every pair has one candidate with all the mass and
                    # the draw does not depend on its uniform -- a wrong keying or CDF would pass
-INSTANTIATIONS = {(16, 1), (16, 2), (16, 3), (32, 2), (32, 3), (64, 2), (64, 3), (64, 4), (64, 6), (64, 8)}   # kernels_pairtau.hip: PAIR_CASE
+INSTANTIATIONS = {(16, 1), (16, 2), (16, 3), (32, 2), (32, 3), (64, 2), (64, 3), (64, 4), (64, 6), (64, 8)}   # dsm_host.h: DSM_TAU_TILINGS
 
 
 def test_the_shapes_reach_every_instantiation_of_the_launcher():
