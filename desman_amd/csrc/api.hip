@@ -10,6 +10,7 @@
 #include <thread>
 
 #include "dsm_host.h"
+#include "dsm_host_util.h"
 #include "log_table.h"
 
 static thread_local char g_err[512] = "";
@@ -96,41 +97,11 @@ extern "C" int dsm_ctx_get_timing(dsm_ctx *c, double *ms_total, int64_t *launche
     return DSM_OK;
 }
 
-// ---------------------------------------------------------------- helpers
-template <typename T>
-static int dev_alloc(T **p, size_t n)
-{
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    if (n == 0) n = 1;
-    hipError_t e = hipMalloc((void **)p, n * sizeof(T));
-    if (e != hipSuccess) { dsm_set_error("hipMalloc(%zu B) failed: %s", n * sizeof(T), hipGetErrorString(e)); return DSM_ERR_NOMEM; }
-    return DSM_OK;
-}
+// ---------------------------------------------------------------- helpers (dev_alloc, DevBuf, DSM_TRY, dsm_ctx_need: dsm_host_util.h)
 template <typename T>
 static void dev_free(T **p) { if (*p) { (void)hipFree(*p); *p = nullptr; } }
 
-// scratch device buffer released on every exit path (error returns included)
-template <typename T>
-struct Scratch {
-    T *p = nullptr;
-    ~Scratch() { if (p) (void)hipFree(p); }
-    int alloc(size_t n) { return dev_alloc(&p, n); }
-    operator T *() const { return p; }
-    Scratch() = default;
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-};
-
-#define TRY(x) do { int _r = (x); if (_r != DSM_OK) return _r; } while (0)
 #define BIND(c) HIP_TRY(hipSetDevice((c)->device))
-
-static int need(dsm_ctx *c, bool counts, bool state)
-{
-    if (!c) { dsm_set_error("null context"); return DSM_ERR_ARG; }
-    if (counts && !c->cnt_vs) { dsm_set_error("no count tensor: call dsm_ctx_set_counts first"); return DSM_ERR_STATE; }
-    if (state && !c->have_state) { dsm_set_error("no chain state: call dsm_ctx_set_state first"); return DSM_ERR_STATE; }
-    return DSM_OK;
-}
 
 // Esum and the DSM_ESUM_PARTS copies stage 1 adds to, all zero: what a failed pass left in the copies is not added to the next one
 static int esum_reset(dsm_ctx *c)
@@ -156,10 +127,7 @@ extern "C" int dsm_ctx_create(dsm_ctx **out, int device)
 {
     if (!out) return DSM_ERR_ARG;
     *out = nullptr;
-    int n = dsm_device_count();
-    if (n <= 0) { dsm_set_error("no HIP device visible"); return DSM_ERR_NODEVICE; }
-    if (device < 0 || device >= n) { dsm_set_error("device %d out of range (0..%d)", device, n - 1); return DSM_ERR_ARG; }
-    HIP_TRY(hipSetDevice(device));
+    DSM_TRY(dsm_bind_device(device));
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
@@ -179,29 +147,29 @@ extern "C" int dsm_ctx_create(dsm_ctx **out, int device)
         HIP_TRY(hipEventCreateWithFlags(&c->ev_u_ready[i], hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&c->ev_u_free[i], hipEventDisableTiming));
     }
-    TRY(dev_alloc(&c->mt_state, 625));
-    TRY(dev_alloc(&c->ll_partial, 2 * DSM_MAX_GRID));     // two parities (updateTau pipelines finalize into the next sweep)
-    TRY(dev_alloc(&c->nchange, 2));
-    TRY(dev_alloc(&c->sweep_stats, 2));
+    DSM_TRY(dev_alloc(&c->mt_state, 625));
+    DSM_TRY(dev_alloc(&c->ll_partial, 2 * DSM_MAX_GRID));     // two parities (updateTau pipelines finalize into the next sweep)
+    DSM_TRY(dev_alloc(&c->nchange, 2));
+    DSM_TRY(dev_alloc(&c->sweep_stats, 2));
     HIP_TRY(hipMemsetAsync(c->sweep_stats, 0, 2 * sizeof(unsigned long long), c->stream));
-    TRY(dev_alloc(&c->step_cnt, (size_t)2 * 2 * DSM_MAX_GRID));
+    DSM_TRY(dev_alloc(&c->step_cnt, (size_t)2 * 2 * DSM_MAX_GRID));
     HIP_TRY(hipMemsetAsync(c->step_cnt, 0, (size_t)2 * 2 * DSM_MAX_GRID * sizeof(uint32_t), c->stream));
-    TRY(dev_alloc(&c->blk_order, (size_t)2 * DSM_MAX_GRID));
-    TRY(reset_blk_order(c));
-    TRY(dev_alloc(&c->screen_ctl, 4));
+    DSM_TRY(dev_alloc(&c->blk_order, (size_t)2 * DSM_MAX_GRID));
+    DSM_TRY(reset_blk_order(c));
+    DSM_TRY(dev_alloc(&c->screen_ctl, 4));
     HIP_TRY(hipMemsetAsync(c->screen_ctl, 0, 4 * sizeof(uint32_t), c->stream));
-    TRY(dev_alloc(&c->prior, 2 * (DSM_MAX_S + 4)));
-    TRY(dev_alloc(&c->scalars, 8));
-    TRY(dev_alloc(&c->star, 2));
-    TRY(dev_alloc(&c->eta, 16));
-    TRY(dev_alloc(&c->eta_new, 16));
-    TRY(dev_alloc(&c->eta_star, 16));
-    TRY(dev_alloc(&c->esum, 16 + 16 * DSM_ESUM_PARTS));
-    TRY(dev_alloc(&c->log_tab, 2 * DSM_LOG_TAB_N + DSM_EXP_TAB_N));           // log table, then the exp table of spec 3
+    DSM_TRY(dev_alloc(&c->prior, 2 * (DSM_MAX_S + 4)));
+    DSM_TRY(dev_alloc(&c->scalars, 8));
+    DSM_TRY(dev_alloc(&c->star, 2));
+    DSM_TRY(dev_alloc(&c->eta, 16));
+    DSM_TRY(dev_alloc(&c->eta_new, 16));
+    DSM_TRY(dev_alloc(&c->eta_star, 16));
+    DSM_TRY(dev_alloc(&c->esum, 16 + 16 * DSM_ESUM_PARTS));
+    DSM_TRY(dev_alloc(&c->log_tab, 2 * DSM_LOG_TAB_N + DSM_EXP_TAB_N));           // log table, then the exp table of spec 3
     HIP_TRY(hipMemcpyAsync(c->log_tab, dsm_log_table_host, sizeof dsm_log_table_host, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->log_tab + 2 * DSM_LOG_TAB_N, dsm_exp_table_host, sizeof dsm_exp_table_host, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->nchange, 0, 2 * sizeof(int), c->stream));
-    TRY(esum_reset(c));
+    DSM_TRY(esum_reset(c));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *out = c;
     return DSM_OK;
@@ -266,21 +234,21 @@ extern "C" int dsm_ctx_set_counts(dsm_ctx *c, const int64_t *variants, int V, in
     c->have_state = false;
     c->G = 0;                       // V/S changed: every state-sized buffer is re-made by set_state
     c->big_hot = true;
-    TRY(dev_alloc(&c->cnt_vs, n * 4));
-    TRY(dev_alloc(&c->nitems, (size_t)S));
-    TRY(dev_alloc(&c->tau, (size_t)V));
+    DSM_TRY(dev_alloc(&c->cnt_vs, n * 4));
+    DSM_TRY(dev_alloc(&c->nitems, (size_t)S));
+    DSM_TRY(dev_alloc(&c->tau, (size_t)V));
     dev_free(&c->F); dev_free(&c->ntau); dev_free(&c->ntau2); dev_free(&c->ngam); dev_free(&c->ngam_raw); c->nG = 0;
     free_traces(c);
-    Scratch<int64_t> d_in; Scratch<int> d_flag; Scratch<double> d_part; Scratch<unsigned long long> d_depth;
+    DevBuf<int64_t> d_in; DevBuf<int> d_flag; DevBuf<double> d_part; DevBuf<unsigned long long> d_depth;
     const int nblk = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
-    TRY(d_in.alloc(n * 4));
-    TRY(d_flag.alloc(1));
-    TRY(d_part.alloc((size_t)nblk));
-    TRY(d_depth.alloc((size_t)S));
+    DSM_TRY(d_in.alloc(n * 4));
+    DSM_TRY(d_flag.alloc(1));
+    DSM_TRY(d_part.alloc((size_t)nblk));
+    DSM_TRY(d_depth.alloc((size_t)S));
     HIP_TRY(hipMemcpyAsync(d_in, variants, n * 4 * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(int), c->stream));
     HIP_TRY(hipMemsetAsync(d_depth, 0, (size_t)S * sizeof(unsigned long long), c->stream));
-    TRY(k_convert_counts(c, d_in, d_flag, d_part, nblk, d_depth));
+    DSM_TRY(k_convert_counts(c, d_in, d_flag, d_part, nblk, d_depth));
     std::vector<double> part(nblk);
     std::vector<unsigned long long> dep((size_t)S);
     int flag = 0;
@@ -294,7 +262,7 @@ extern "C" int dsm_ctx_set_counts(dsm_ctx *c, const int64_t *variants, int V, in
     c->blk_gmax = 0;
     c->stats_grid = 0;
     dev_free(&c->pat_x); c->pat_x_len = 0;      // the aggregated counts of the old table's positions
-    TRY(reset_blk_order(c));              // another table, another grid: no block order of the old one survives
+    DSM_TRY(reset_blk_order(c));              // another table, another grid: no block order of the old one survives
     HIP_TRY(hipMemsetAsync(c->screen_ctl, 0, 4 * sizeof(uint32_t), c->stream));
     dev_free(&c->items);
     c->depth.assign((size_t)S, 0);
@@ -353,7 +321,7 @@ int build_stats_items(dsm_ctx *c)
     for (int s = 0; s < S; ++s) max_items = std::max(max_items, (int)lst[s].size());
     c->item_stride = max_items > 0 ? max_items : 1;
     std::vector<int32_t> items((size_t)S * c->item_stride * 2, 0);
-    TRY(dev_alloc(&c->items, items.size()));
+    DSM_TRY(dev_alloc(&c->items, items.size()));
     std::vector<int32_t> first;
     const int32_t rd_mask = CH ? 0xfff : 0x7fffffff;
     for (int s = 0; s < S; ++s) {
@@ -388,15 +356,15 @@ static int ensure_state_buffers(dsm_ctx *c, int G)
     if (G != c->G || !c->gamma) {
         c->G = G;
         const size_t sg = (size_t)c->S * G;
-        TRY(dev_alloc(&c->gamma, sg));
-        TRY(dev_alloc(&c->gamma_star, sg));
-        TRY(dev_alloc(&c->sum_mu, sg));
+        DSM_TRY(dev_alloc(&c->gamma, sg));
+        DSM_TRY(dev_alloc(&c->gamma_star, sg));
+        DSM_TRY(dev_alloc(&c->sum_mu, sg));
         HIP_TRY(hipMemsetAsync(c->sum_mu, 0, sg * sizeof(unsigned long long), c->stream));
         c->stats_grid = 0;
         c->u_cap = (size_t)c->V * G;
         // two slots of up to DSM_U_CHUNK sweeps each, at most 64 MB per slot
         c->u_chunk_words = c->u_cap * std::max<size_t>(1, std::min<size_t>(DSM_U_CHUNK, ((size_t)16 << 20) / std::max<size_t>(1, c->u_cap)));
-        TRY(dev_alloc(&c->u_raw, 2 * c->u_chunk_words));
+        DSM_TRY(dev_alloc(&c->u_raw, 2 * c->u_chunk_words));
         free_traces(c);
     }
     return DSM_OK;
@@ -404,16 +372,16 @@ static int ensure_state_buffers(dsm_ctx *c, int G)
 
 extern "C" int dsm_ctx_set_state(dsm_ctx *c, const int64_t *tau, const double *gamma, const double *eta, int G)
 {
-    TRY(need(c, true, false));
+    DSM_TRY(dsm_ctx_need(c, true, false));
     if (!tau || !gamma || !eta) { dsm_set_error("set_state: null pointer"); return DSM_ERR_ARG; }
     BIND(c);
     HIP_TRY(hipStreamSynchronize(c->stream));
-    TRY(ensure_state_buffers(c, G));
+    DSM_TRY(ensure_state_buffers(c, G));
     const size_t nt = (size_t)c->V * G * 4;
-    Scratch<int64_t> d_t;
-    TRY(d_t.alloc(nt));
+    DevBuf<int64_t> d_t;
+    DSM_TRY(d_t.alloc(nt));
     HIP_TRY(hipMemcpyAsync(d_t, tau, nt * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    TRY(k_pack_tau(c, d_t, c->tau, c->V, G));
+    DSM_TRY(k_pack_tau(c, d_t, c->tau, c->V, G));
     HIP_TRY(hipMemcpyAsync(c->gamma, gamma, (size_t)c->S * G * sizeof(double), hipMemcpyHostToDevice, c->stream));
     c->tau_rare_n = tau_rare_from_host(gamma, c->S, G);
     c->big_hot = true;              // a new state: nothing is known about what stage 1 will hand over
@@ -425,7 +393,7 @@ extern "C" int dsm_ctx_set_state(dsm_ctx *c, const int64_t *tau, const double *g
 
 extern "C" int dsm_ctx_set_gamma_eta(dsm_ctx *c, const double *gamma, const double *eta)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     BIND(c);
     if (gamma) HIP_TRY(hipMemcpyAsync(c->gamma, gamma, (size_t)c->S * c->G * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (gamma) c->tau_rare_n = tau_rare_from_host(gamma, c->S, c->G);
@@ -438,9 +406,9 @@ extern "C" int dsm_ctx_set_gamma_eta(dsm_ctx *c, const double *gamma, const doub
 static int fetch_tau(dsm_ctx *c, const uint64_t *d_packed, int64_t *host_onehot)
 {
     const size_t nt = (size_t)c->V * c->G * 4;
-    Scratch<int64_t> d_t;
-    TRY(d_t.alloc(nt));
-    TRY(k_unpack_tau(c, d_packed, d_t, c->V, c->G));
+    DevBuf<int64_t> d_t;
+    DSM_TRY(d_t.alloc(nt));
+    DSM_TRY(k_unpack_tau(c, d_packed, d_t, c->V, c->G));
     HIP_TRY(hipMemcpyAsync(host_onehot, d_t, nt * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;
@@ -448,9 +416,9 @@ static int fetch_tau(dsm_ctx *c, const uint64_t *d_packed, int64_t *host_onehot)
 
 extern "C" int dsm_ctx_get_state(dsm_ctx *c, int64_t *tau, double *gamma, double *eta)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     BIND(c);
-    if (tau) TRY(fetch_tau(c, c->tau, tau));
+    if (tau) DSM_TRY(fetch_tau(c, c->tau, tau));
     if (gamma) HIP_TRY(hipMemcpyAsync(gamma, c->gamma, (size_t)c->S * c->G * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (eta) HIP_TRY(hipMemcpyAsync(eta, c->eta, 16 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -563,10 +531,10 @@ extern "C" int dsm_ctx_debug_mt_fill(dsm_ctx *c, size_t n, uint32_t *out)
     if (!c->mt_seeded) { dsm_set_error("tau RNG not seeded"); return DSM_ERR_STATE; }
     if (n == 0) return DSM_OK;
     BIND(c);
-    Scratch<uint32_t> d;
-    TRY(d.alloc(n));
+    DevBuf<uint32_t> d;
+    DSM_TRY(d.alloc(n));
     HIP_TRY(hipStreamSynchronize(c->stream_rng));
-    TRY(k_mt_fill(c, d, n, c->stream));
+    DSM_TRY(k_mt_fill(c, d, n, c->stream));
     HIP_TRY(hipMemcpyAsync(out, d, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;
@@ -604,7 +572,7 @@ struct SweepWords {
         const int slot = nchunk & 1;
         uint32_t *buf = c->u_raw + (size_t)slot * c->u_chunk_words;
         HIP_TRY(hipStreamWaitEvent(c->stream_rng, c->ev_u_free[slot], 0));   // the last reader of this slot is done
-        TRY(k_mt_fill(c, buf, (size_t)want * per, c->stream_rng));
+        DSM_TRY(k_mt_fill(c, buf, (size_t)want * per, c->stream_rng));
         HIP_TRY(hipEventRecord(c->ev_u_ready[slot], c->stream_rng));
         first[slot] = filled; len[slot] = want;
         filled += want; ++nchunk;
@@ -623,11 +591,11 @@ struct SweepWords {
         *u = nullptr;
         if (!active()) return DSM_OK;
         if (!c->mt_seeded) { dsm_set_error("tau RNG not seeded: call dsm_ctx_seed / dsm_setRNG"); return DSM_ERR_STATE; }
-        if (it >= filled) TRY(fill_next());
+        if (it >= filled) DSM_TRY(fill_next());
         int slot = (it >= first[0] && it < first[0] + len[0] && len[0]) ? 0 : 1;
         if (!(it >= first[slot] && it < first[slot] + len[slot])) { dsm_set_error("sweep words asked out of order"); return DSM_ERR_STATE; }
         if (it == first[slot]) {
-            if (filled < total) TRY(fill_next());            // keep one chunk ahead (into the other slot)
+            if (filled < total) DSM_TRY(fill_next());            // keep one chunk ahead (into the other slot)
             HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_u_ready[slot], 0));
         }
         *u = c->u_raw + (size_t)slot * c->u_chunk_words + (size_t)(it - first[slot]) * per;
@@ -647,20 +615,20 @@ struct SweepWords {
 // only one with logp_out) or the held sweep of DESIGN.md sec. 8e, which consumes V F words of the MT19937 stream instead of V G.
 static int sample_tau_once(dsm_ctx *c, int n_held, int *nchange, double *logp_out)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     if (n_held < 0 || n_held > c->G) { dsm_set_error("sample_tau_held: n_held = %d outside 0..%d", n_held, c->G); return DSM_ERR_ARG; }
     if (n_held == c->G) { c->iter_ctr++; if (nchange) *nchange = 0; return DSM_OK; }      // a sweep over no haplotype
     BIND(c);
-    Scratch<double> d_logp;
+    DevBuf<double> d_logp;
     const size_t nl = (size_t)c->V * c->G * 4;
-    if (logp_out) TRY(d_logp.alloc(nl));
+    if (logp_out) DSM_TRY(d_logp.alloc(nl));
     const uint32_t *u = nullptr;
     SweepWords words(c, 1, n_held ? (size_t)c->V * (c->G - n_held) : c->u_cap);
     HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
-    TRY(words.acquire(0, &u));
-    TRY(n_held ? k_held_sweep(c, n_held, c->gamma, c->eta, c->iter_ctr++, u)
+    DSM_TRY(words.acquire(0, &u));
+    DSM_TRY(n_held ? k_held_sweep(c, n_held, c->gamma, c->eta, c->iter_ctr++, u)
                : k_tau_sweep(c, 1, c->gamma, c->eta, c->eta, nullptr, d_logp, c->iter_ctr++, nullptr, u));
-    TRY(words.release(0));
+    DSM_TRY(words.release(0));
     int n = 0;
     HIP_TRY(hipMemcpyAsync(&n, c->nchange, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     if (logp_out) HIP_TRY(hipMemcpyAsync(logp_out, d_logp, nl * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -691,10 +659,10 @@ extern "C" int dsm_ctx_get_pair_moves(dsm_ctx *c, int *every)
 // counter moves
 extern "C" int dsm_ctx_sample_tau_pairs(dsm_ctx *c, uint32_t iter, int *nchange)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     BIND(c);
     HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
-    TRY(k_pair_sweep(c, c->gamma, c->eta, iter));
+    DSM_TRY(k_pair_sweep(c, c->gamma, c->eta, iter));
     int n = 0;
     HIP_TRY(hipMemcpyAsync(&n, c->nchange, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
@@ -705,19 +673,19 @@ extern "C" int dsm_ctx_sample_tau_pairs(dsm_ctx *c, uint32_t iter, int *nchange)
 
 extern "C" int dsm_ctx_sample_stats(dsm_ctx *c, uint32_t iter, uint64_t *sum_mu, uint64_t *esum)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     BIND(c);
     const size_t sg = (size_t)c->S * c->G;
     HIP_TRY(hipMemsetAsync(c->sum_mu, 0, sg * sizeof(unsigned long long), c->stream));
-    TRY(stats_ensure_ntab(c));
-    TRY(esum_reset(c));
+    DSM_TRY(stats_ensure_ntab(c));
+    DSM_TRY(esum_reset(c));
     // (the launch of stats_big_kernel left out where the context says so: stage 2 then draws the deferred items, the same sums)
-    TRY(k_stats(c, iter, !(stats_big_optional(c) && !stats_big_wanted(c))));
-    TRY(k_esum_fold(c));
+    DSM_TRY(k_stats(c, iter, !(stats_big_optional(c) && !stats_big_wanted(c))));
+    DSM_TRY(k_esum_fold(c));
     if (sum_mu) HIP_TRY(hipMemcpyAsync(sum_mu, c->sum_mu, sg * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     if (esum) HIP_TRY(hipMemcpyAsync(esum, c->esum, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemsetAsync(c->sum_mu, 0, sg * sizeof(unsigned long long), c->stream));
-    TRY(esum_reset(c));
+    DSM_TRY(esum_reset(c));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;
 }
@@ -737,19 +705,19 @@ extern "C" int dsm_ctx_force_stats_spec(dsm_ctx *c, int spec)
 
 extern "C" int dsm_ctx_debug_stage1(dsm_ctx *c, uint32_t iter, uint32_t *ntab, uint64_t *esum)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     if (stats_spec(c) < 2) { dsm_set_error("debug_stage1: the aggregated specification does not apply to this shape (force it with dsm_ctx_force_stats_spec)"); return DSM_ERR_UNSUPPORTED; }
     BIND(c);
-    TRY(esum_reset(c));
-    TRY(k_stats_stage1(c, iter));
-    TRY(k_esum_fold(c));
+    DSM_TRY(esum_reset(c));
+    DSM_TRY(k_stats_stage1(c, iter));
+    DSM_TRY(k_esum_fold(c));
     const size_t NH = (size_t)1 << c->G, S = (size_t)c->S;
     const size_t ld = (size_t)c->ntab_ld;
     std::vector<uint32_t> t((size_t)c->ntab_rep * NH * ld);
     HIP_TRY(hipMemcpyAsync(t.data(), c->ntab, t.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     if (esum) HIP_TRY(hipMemcpyAsync(esum, c->esum, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemsetAsync(c->ntab, 0, t.size() * sizeof(uint32_t), c->stream));
-    TRY(esum_reset(c));
+    DSM_TRY(esum_reset(c));
     HIP_TRY(hipMemsetAsync(c->big_count, 0, DSM_BIG_NT * DSM_BIG_NL * DSM_BIG_STRIDE * sizeof(uint32_t), c->stream));     // (the running count of non-empty lists with them)
     c->big_seen = 0; c->big_hot = true;
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -768,9 +736,9 @@ extern "C" int dsm_ctx_debug_binom(dsm_ctx *c, int kind, uint32_t n, const doubl
     if (!c || !w4 || !out || nsamp < 1 || kind < 0 || kind > 2 || spec < 2 || spec > 3) { dsm_set_error("debug_binom: bad arguments"); return DSM_ERR_ARG; }
     BIND(c);
     const size_t len = (size_t)nsamp * (kind == 2 ? 4 : 1);
-    Scratch<uint32_t> d;
-    TRY(d.alloc(len));
-    TRY(k_binom_test(c, kind, n, w4, seed, nsamp, d, spec));
+    DevBuf<uint32_t> d;
+    DSM_TRY(d.alloc(len));
+    DSM_TRY(k_binom_test(c, kind, n, w4, seed, nsamp, d, spec));
     HIP_TRY(hipMemcpyAsync(out, d, len * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;
@@ -779,16 +747,16 @@ extern "C" int dsm_ctx_debug_binom(dsm_ctx *c, int kind, uint32_t n, const doubl
 extern "C" int dsm_ctx_draw_gamma_eta(dsm_ctx *c, uint32_t iter, const uint64_t *sum_mu, const uint64_t *esum,
                                       double *gamma_out, double *eta_out)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     if (!sum_mu || !esum) { dsm_set_error("draw_gamma_eta: null sums"); return DSM_ERR_ARG; }
     BIND(c);
     const size_t sg = (size_t)c->S * c->G;
-    Scratch<double> d_g, d_e;
-    TRY(d_g.alloc(sg));
-    TRY(d_e.alloc(16));
+    DevBuf<double> d_g, d_e;
+    DSM_TRY(d_g.alloc(sg));
+    DSM_TRY(d_e.alloc(16));
     HIP_TRY(hipMemcpyAsync(c->sum_mu, sum_mu, sg * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->esum, esum, 16 * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    TRY(k_dirichlet(c, iter, d_g, nullptr, d_e, nullptr, c->prior, -1, 0, nullptr));
+    DSM_TRY(k_dirichlet(c, iter, d_g, nullptr, d_e, nullptr, c->prior, -1, 0, nullptr));
     if (gamma_out) HIP_TRY(hipMemcpyAsync(gamma_out, d_g, sg * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (eta_out) HIP_TRY(hipMemcpyAsync(eta_out, d_e, 16 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -799,17 +767,17 @@ extern "C" int dsm_ctx_draw_gamma_eta(dsm_ctx *c, uint32_t iter, const uint64_t 
 static int eval_state(dsm_ctx *c, const double *gamma, const double *eta, uint64_t *trace_slot, int star_mode)
 {
     int nb = 0;
-    TRY(k_prior(c, gamma, eta, c->prior));
-    TRY(k_tau_sweep(c, 2, gamma, eta, eta, trace_slot, nullptr, 0, &nb, nullptr));
+    DSM_TRY(k_prior(c, gamma, eta, c->prior));
+    DSM_TRY(k_tau_sweep(c, 2, gamma, eta, eta, trace_slot, nullptr, 0, &nb, nullptr));
     return k_finalize(c, nb, -1, star_mode, c->prior, gamma, eta);
 }
 
 extern "C" int dsm_ctx_loglik(dsm_ctx *c, double *ll, double *lp)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     BIND(c);
     double sc[2];
-    TRY(eval_state(c, c->gamma, c->eta, nullptr, 2));     // star_mode 2: MAP record untouched
+    DSM_TRY(eval_state(c, c->gamma, c->eta, nullptr, 2));     // star_mode 2: MAP record untouched
     HIP_TRY(hipMemcpyAsync(sc, c->scalars, sizeof sc, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (ll) *ll = sc[0];
@@ -828,12 +796,12 @@ static int alloc_traces(dsm_ctx *c, int n)
         // growing iteration count (burn-in 5, then 20, ...) does not pay hipFree + hipMalloc (~1 ms) inside every call
         const int want = n;
         if (n < 512 && (size_t)513 * c->V * sizeof(uint64_t) <= ((size_t)1 << 30)) n = 512;
-        TRY(dev_alloc(&c->tau_trace, (size_t)(n + 1) * c->V));
-        TRY(dev_alloc(&c->ll_trace, (size_t)n));
-        TRY(dev_alloc(&c->lp_trace, (size_t)n));
-        TRY(dev_alloc(&c->nchange_trace, (size_t)n));
-        TRY(dev_alloc(&c->gamma_trace, (size_t)n * sg));
-        TRY(dev_alloc(&c->eta_trace, (size_t)n * 16));
+        DSM_TRY(dev_alloc(&c->tau_trace, (size_t)(n + 1) * c->V));
+        DSM_TRY(dev_alloc(&c->ll_trace, (size_t)n));
+        DSM_TRY(dev_alloc(&c->lp_trace, (size_t)n));
+        DSM_TRY(dev_alloc(&c->nchange_trace, (size_t)n));
+        DSM_TRY(dev_alloc(&c->gamma_trace, (size_t)n * sg));
+        DSM_TRY(dev_alloc(&c->eta_trace, (size_t)n * 16));
         c->trace_cap = n;
         n = want;
     }
@@ -871,10 +839,10 @@ struct Chains {
     {
         if (!c || K < 1 || K > DSM_MAX_BATCH) { dsm_set_error("batch of %d chains (1..%d)", K, DSM_MAX_BATCH); return DSM_ERR_ARG; }
         for (int k = 0; k < K; ++k) {
-            TRY(need(c[k], true, state));
+            DSM_TRY(dsm_ctx_need(c[k], true, state));
             const dsm_ctx *a = c[0], *b = c[k];
             if (b->device != a->device || b->V != a->V || b->S != a->S) { dsm_set_error("batch: chain %d differs from chain 0 in device or shape", k); return DSM_ERR_ARG; }
-            TRY(fits(a, b, k));
+            DSM_TRY(fits(a, b, k));
             for (int j = 0; j < k; ++j) if (c[j] == b) { dsm_set_error("batch: chain %d listed twice", k); return DSM_ERR_ARG; }
         }
         BIND(lead());
@@ -890,7 +858,7 @@ struct Chains {
     // f(chain, k) chain by chain, each launch its own
     template <class F> int each(F f) const
     {
-        for (int k = 0; k < K; ++k) TRY(f(c[k], k));
+        for (int k = 0; k < K; ++k) DSM_TRY(f(c[k], k));
         return DSM_OK;
     }
     // f(chain, k) for every chain; batched, what each launcher f calls collects from the chains goes out as one launch
@@ -933,8 +901,8 @@ static int gibbs_update(dsm_ctx *const *ctxs, int K, bool batched, int n_iter, T
     if (n_iter < 0) { dsm_set_error("n_iter < 0"); return DSM_ERR_ARG; }
     if (batched && step.n_held) { dsm_set_error("batch: no held haplotypes (the held sweep has no batched form)"); return DSM_ERR_UNSUPPORTED; }
     Chains ch{ctxs, K, batched};
-    TRY(ch.open(true, false, [batched](const dsm_ctx *a, const dsm_ctx *b, int k) -> int {
-        TRY(same_G_and_rng(a, b, k));
+    DSM_TRY(ch.open(true, false, [batched](const dsm_ctx *a, const dsm_ctx *b, int k) -> int {
+        DSM_TRY(same_G_and_rng(a, b, k));
         if (batched && b->pair_every > 0) {
             dsm_set_error("batch: chain %d has pair moves on (dsm_ctx_set_pair_moves: every = %d); the pair pass has no batched form", k, b->pair_every);
             return DSM_ERR_UNSUPPORTED;
@@ -972,65 +940,65 @@ static int gibbs_update(dsm_ctx *const *ctxs, int K, bool batched, int n_iter, T
     std::vector<int> nb_prev(K, 0);
     std::vector<uint32_t> ic(K);
     std::vector<const uint32_t *> u(K, nullptr);
-    Scratch<double> held;                               // fix_eta: the four prior terms of the held matrix
-    TRY(ch.each([&](dsm_ctx *c, int) -> int {
-        TRY(alloc_traces(c, n_iter));
+    DevBuf<double> held;                               // fix_eta: the four prior terms of the held matrix
+    DSM_TRY(ch.each([&](dsm_ctx *c, int) -> int {
+        DSM_TRY(alloc_traces(c, n_iter));
         c->tau_fixed_trace = fixed;
         HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
         if (!full) {
             HIP_TRY(hipMemsetAsync(c->sum_mu, 0, sg * sizeof(unsigned long long), c->stream));
-            TRY(esum_reset(c));                         // Esum and every partial copy of it (a failed pass may have left counts there)
+            DSM_TRY(esum_reset(c));                         // Esum and every partial copy of it (a failed pass may have left counts there)
         }
         // entry state: ll, lp, storeStarState(0)  (HaploSNP_Sampler.py:336-338); tau -> slot 0 of the trace
-        TRY(eval_state(c, c->gamma, c->eta, c->tau_trace, 1));
-        TRY(stats_ensure_ntab(c));
-        if (full && !batched) TRY(k_tau_neartie_hint(c));   // which instantiation of the full sweep this call runs (same draws either way)
+        DSM_TRY(eval_state(c, c->gamma, c->eta, c->tau_trace, 1));
+        DSM_TRY(stats_ensure_ntab(c));
+        if (full && !batched) DSM_TRY(k_tau_neartie_hint(c));   // which instantiation of the full sweep this call runs (same draws either way)
         if (fix_eta && n_iter > 0) {
-            TRY(held.alloc((size_t)c->S + 4));
-            TRY(k_prior(c, c->gamma, c->eta, held));
-            TRY(k_fixtau_fill_eta(c, c->eta, c->eta_trace, n_iter));
+            DSM_TRY(held.alloc((size_t)c->S + 4));
+            DSM_TRY(k_prior(c, c->gamma, c->eta, held));
+            DSM_TRY(k_fixtau_fill_eta(c, c->eta, c->eta_trace, n_iter));
         }
         words.emplace_back(c, fixed ? 0 : n_iter, full ? c->u_cap : (size_t)c->V * (c->G - step.n_held));
         return DSM_OK;
     }));
-    TRY(ch.launch([&](dsm_ctx *, int k) { return words[k].prefetch(); }));
+    DSM_TRY(ch.launch([&](dsm_ctx *, int k) { return words[k].prefetch(); }));
     for (int it = 0; it < n_iter; ++it) {
         // (the abundances move during a burn-in: the choice of the full sweep's instantiation is looked at again now and then -- a stream
         // synchronisation and a 4-byte read-back every 64 iterations; the draws do not depend on it)
         // (the same look tells whether stage 1 still hands items over: a settled chain drops the launch of stats_big_kernel, at most 64 iterations late)
         if (full && !batched && it && (it & 63) == 0 && (lead->tau_neartie_mode == -1 || big_auto)) {
-            TRY(k_tau_rare_count(lead, true)); TRY(k_tau_neartie_hint(lead));
+            DSM_TRY(k_tau_rare_count(lead, true)); DSM_TRY(k_tau_neartie_hint(lead));
             launch_big = big_wanted();
         }
-        TRY(ch.launch([&](dsm_ctx *c, int k) { ic[k] = c->iter_ctr++; return agg ? k_stats_stage1(c, ic[k], launch_big) : k_stats_v1(c, ic[k]); }));
-        if (agg && !fuse_s2) TRY(ch.launch([&](dsm_ctx *c, int k) { return k_stats_stage2(c, ic[k]); }));
+        DSM_TRY(ch.launch([&](dsm_ctx *c, int k) { ic[k] = c->iter_ctr++; return agg ? k_stats_stage1(c, ic[k], launch_big) : k_stats_v1(c, ic[k]); }));
+        if (agg && !fuse_s2) DSM_TRY(ch.launch([&](dsm_ctx *c, int k) { return k_stats_stage2(c, ic[k]); }));
         // sampleGamma (:342) + the eta draw (:347: eta depends only on the E sums) + traces; the same
         // launch finalizes iteration it-1 (ll, lp, MAP test :349-353) in one extra workgroup
-        TRY(ch.launch([&](dsm_ctx *c, int k) {
+        DSM_TRY(ch.launch([&](dsm_ctx *c, int k) {
             return k_dirichlet(c, ic[k], c->gamma, c->gamma_trace + (size_t)it * sg, c->eta_new, fix_eta ? nullptr : c->eta_trace + (size_t)it * 16,
                                prior_slot(c, it), it - 1, nb_prev[k], prior_slot(c, it - 1), fuse_s2 ? 1 : 0);
         }));
         // tau sweep with (gamma_new, eta_old) (:345); the full sweep's launch is also the log-likelihood of the new state with eta_new (:349)
         if (!fixed) {
-            TRY(ch.launch([&](dsm_ctx *, int k) { return words[k].acquire(it, &u[k]); }));
-            TRY(ch.launch([&](dsm_ctx *c, int k) {
+            DSM_TRY(ch.launch([&](dsm_ctx *, int k) { return words[k].acquire(it, &u[k]); }));
+            DSM_TRY(ch.launch([&](dsm_ctx *c, int k) {
                 if (!full) return k_held_sweep(c, step.n_held, c->gamma, c->eta, ic[k], u[k]);
                 return k_tau_sweep(c, 3, c->gamma, c->eta, c->eta_new, c->tau_trace + (size_t)(it + 1) * c->V, nullptr, ic[k], &nb_prev[k], u[k]);
             }));
-            TRY(ch.each([&](dsm_ctx *, int k) { return words[k].release(it); }));
+            DSM_TRY(ch.each([&](dsm_ctx *, int k) { return words[k].release(it); }));
         }
         // a pair iteration: the pair pass with the (gamma_new, eta_old) the sweep conditioned on; the likelihood of the state it leaves
         // takes the likelihood-only pass below, which overwrites what the sweep's launch stored (tau's trace slot, the ll partials)
         const bool pair_it = pair_E && (ic[0] + 1u) % pair_E == 0;
-        if (pair_it) TRY(k_pair_sweep(lead, lead->gamma, lead->eta, ic[0]));
-        TRY(ch.each([&](dsm_ctx *c, int) -> int {
+        if (pair_it) DSM_TRY(k_pair_sweep(lead, lead->gamma, lead->eta, ic[0]));
+        DSM_TRY(ch.each([&](dsm_ctx *c, int) -> int {
             if (fix_eta) HIP_TRY(hipMemcpyAsync(prior_slot(c, it) + c->S, held.p + c->S, 4 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
             else std::swap(c->eta, c->eta_new);                          // eta_new becomes the chain's eta
             return DSM_OK;
         }));
         // held and fixed: the likelihood-only pass at (tau_new, gamma_new, eta_new); it stores tau_new where tau moves
         if (!full || pair_it)
-            TRY(ch.each([&](dsm_ctx *c, int k) {
+            DSM_TRY(ch.each([&](dsm_ctx *c, int k) {
                 return k_tau_sweep(c, 2, c->gamma, c->eta, c->eta, fixed ? nullptr : c->tau_trace + (size_t)(it + 1) * c->V, nullptr, 0, &nb_prev[k], nullptr);
             }));
     }
@@ -1039,19 +1007,19 @@ static int gibbs_update(dsm_ctx *const *ctxs, int K, bool batched, int n_iter, T
     const bool want_rare = !batched && n_iter > 0 && lead->tau_neartie_mode == -1;
     // ... and, for every chain whose launch of stats_big_kernel is a choice, the device's count of deferred lists found non-empty
     const bool want_big = big_opt && n_iter > 0;
-    TRY(ch.each([&](dsm_ctx *c, int) -> int {
+    DSM_TRY(ch.each([&](dsm_ctx *c, int) -> int {
         if ((want_rare || want_big) && !c->h_rare) HIP_TRY(hipHostMalloc((void **)&c->h_rare, 2 * sizeof(int), hipHostMallocDefault));
         return DSM_OK;
     }));
     if (n_iter > 0)
-        TRY(ch.each([&](dsm_ctx *c, int k) {
+        DSM_TRY(ch.each([&](dsm_ctx *c, int k) {
             return k_finalize(c, nb_prev[k], n_iter - 1, 0, prior_slot(c, n_iter - 1), c->gamma_trace + (size_t)(n_iter - 1) * sg,
                               c->eta_trace + (size_t)(n_iter - 1) * 16, 0, want_rare ? c->h_rare : nullptr, want_big ? c->h_rare + 1 : nullptr);
         }));
     HIP_TRY(hipStreamSynchronize(lead->stream));
     if (!full && !fixed) HIP_TRY(hipStreamSynchronize(lead->stream_rng));
     if (want_rare) lead->tau_rare_n = *lead->h_rare;
-    if (want_big) TRY(ch.each([&](dsm_ctx *c, int) -> int { stats_big_take(c, (uint32_t)c->h_rare[1]); return DSM_OK; }));
+    if (want_big) DSM_TRY(ch.each([&](dsm_ctx *c, int) -> int { stats_big_take(c, (uint32_t)c->h_rare[1]); return DSM_OK; }));
     return DSM_OK;
 }
 
@@ -1081,7 +1049,7 @@ int comm_device(const dsm_comm *m);
 // (not run through gibbs_update: its exchanges sit between stage 1 and stage 2 and around every finalize -- hooks there, no code saved)
 static int gibbs_update_sharded(dsm_ctx *c, int n_iter, int v_offset, int v_total, dsm_exchange_fn exchange, void *user, dsm_comm *comm)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     if (c->pair_every > 0) {
         dsm_set_error("gibbs_update_sharded: pair moves are on (dsm_ctx_set_pair_moves: every = %d); the pair pass has no sharded form", c->pair_every);
         return DSM_ERR_UNSUPPORTED;
@@ -1095,14 +1063,14 @@ static int gibbs_update_sharded(dsm_ctx *c, int n_iter, int v_offset, int v_tota
     if (c->force_stats_spec < 2) c->force_stats_spec = DSM_STATS_AGG;          // the aggregated pass whatever the shard's size
     struct Guard { dsm_ctx *c; int f; ~Guard() { c->shard_on = false; c->force_stats_spec = f; } } guard{c, keep_force};
     if (stats_spec(c) < 2) { dsm_set_error("gibbs_update_sharded: the aggregated mu/E pass does not apply to this shape (G <= 16)"); return DSM_ERR_UNSUPPORTED; }
-    if (!c->shard_vec) TRY(dev_alloc(&c->shard_vec, (size_t)18));
+    if (!c->shard_vec) DSM_TRY(dev_alloc(&c->shard_vec, (size_t)18));
     // shard_on before anything sizes the subset table: its layout (copies, row stride) must be the same on every rank -- it is
     // derived from v_total, S and G, never from this shard's own V (kernels_stats.hip: stats_ntab_rep)
     c->shard_on = true; c->shard_voff = v_offset; c->shard_vtot = v_total;
-    TRY(alloc_traces(c, n_iter));
+    DSM_TRY(alloc_traces(c, n_iter));
     const size_t sg = (size_t)c->S * c->G;
     HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
-    TRY(esum_reset(c));
+    DSM_TRY(esum_reset(c));
     auto swap_vec = [&](uint32_t *tab, size_t n_tab) -> int {
         if (comm) return comm_enqueue_exchange(comm, tab, n_tab, c->shard_vec, (size_t)18, c->stream);
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1112,34 +1080,34 @@ static int gibbs_update_sharded(dsm_ctx *c, int n_iter, int v_offset, int v_tota
     // entry state: ll, lp of the WHOLE table, storeStarState(0)
     {
         int nb = 0;
-        TRY(k_prior(c, c->gamma, c->eta, c->prior));
-        TRY(k_tau_sweep(c, 2, c->gamma, c->eta, c->eta, c->tau_trace, nullptr, 0, &nb, nullptr));
-        TRY(k_shard_pack(c, nb));
-        TRY(swap_vec(nullptr, 0));
-        TRY(k_finalize(c, nb, -1, 1, c->prior, c->gamma, c->eta));
-        TRY(esum_reset(c));
+        DSM_TRY(k_prior(c, c->gamma, c->eta, c->prior));
+        DSM_TRY(k_tau_sweep(c, 2, c->gamma, c->eta, c->eta, c->tau_trace, nullptr, 0, &nb, nullptr));
+        DSM_TRY(k_shard_pack(c, nb));
+        DSM_TRY(swap_vec(nullptr, 0));
+        DSM_TRY(k_finalize(c, nb, -1, 1, c->prior, c->gamma, c->eta));
+        DSM_TRY(esum_reset(c));
     }
-    TRY(stats_ensure_ntab(c));
+    DSM_TRY(stats_ensure_ntab(c));
     const bool fuse_s2 = c->G < 10;
     int nb_prev = 0;
     for (int it = 0; it < n_iter; ++it) {
         const uint32_t ic = c->iter_ctr++;
-        TRY(k_stats_stage1(c, ic));                                   // this shard's cells -> its subset table and Esum
-        TRY(k_shard_pack(c, nb_prev));                                // + ll / nchange of the previous sweep
-        TRY(swap_vec(c->ntab, c->ntab_len));
-        TRY(k_shard_unpack(c));
-        if (!fuse_s2) TRY(k_stats_stage2(c, ic));
-        TRY(k_dirichlet(c, ic, c->gamma, c->gamma_trace + (size_t)it * sg, c->eta_new, c->eta_trace + (size_t)it * 16,
+        DSM_TRY(k_stats_stage1(c, ic));                                   // this shard's cells -> its subset table and Esum
+        DSM_TRY(k_shard_pack(c, nb_prev));                                // + ll / nchange of the previous sweep
+        DSM_TRY(swap_vec(c->ntab, c->ntab_len));
+        DSM_TRY(k_shard_unpack(c));
+        if (!fuse_s2) DSM_TRY(k_stats_stage2(c, ic));
+        DSM_TRY(k_dirichlet(c, ic, c->gamma, c->gamma_trace + (size_t)it * sg, c->eta_new, c->eta_trace + (size_t)it * 16,
                         prior_slot(c, it), it - 1, nb_prev, prior_slot(c, it - 1), fuse_s2 ? 1 : 0));
-        TRY(k_tau_sweep(c, 3, c->gamma, c->eta, c->eta_new, c->tau_trace + (size_t)(it + 1) * c->V, nullptr, ic, &nb_prev, nullptr));
+        DSM_TRY(k_tau_sweep(c, 3, c->gamma, c->eta, c->eta_new, c->tau_trace + (size_t)(it + 1) * c->V, nullptr, ic, &nb_prev, nullptr));
         std::swap(c->eta, c->eta_new);
     }
     if (n_iter > 0) {
-        TRY(k_shard_pack(c, nb_prev));
-        TRY(swap_vec(nullptr, 0));
-        TRY(k_finalize(c, nb_prev, n_iter - 1, 0, prior_slot(c, n_iter - 1), c->gamma_trace + (size_t)(n_iter - 1) * sg,
+        DSM_TRY(k_shard_pack(c, nb_prev));
+        DSM_TRY(swap_vec(nullptr, 0));
+        DSM_TRY(k_finalize(c, nb_prev, n_iter - 1, 0, prior_slot(c, n_iter - 1), c->gamma_trace + (size_t)(n_iter - 1) * sg,
                        c->eta_trace + (size_t)(n_iter - 1) * 16));
-        TRY(esum_reset(c));
+        DSM_TRY(esum_reset(c));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;
@@ -1177,9 +1145,9 @@ static int tau_inputs(dsm_ctx *c, int n_iter, const double *gamma_store, const d
 {
     const size_t sg = (size_t)c->S * c->G;
     if (n_iter > c->in_cap || !c->gamma_in) {            // grow-only, like the traces
-        TRY(dev_alloc(&c->gamma_in, (size_t)n_iter * sg));
-        TRY(dev_alloc(&c->eta_in, (size_t)n_iter * 16));
-        TRY(dev_alloc(&c->prior_all, (size_t)n_iter * (c->S + 4)));
+        DSM_TRY(dev_alloc(&c->gamma_in, (size_t)n_iter * sg));
+        DSM_TRY(dev_alloc(&c->eta_in, (size_t)n_iter * 16));
+        DSM_TRY(dev_alloc(&c->prior_all, (size_t)n_iter * (c->S + 4)));
         c->in_cap = n_iter;
     }
     HIP_TRY(hipMemcpyAsync(c->gamma_in, gamma_store, (size_t)n_iter * sg * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -1188,9 +1156,9 @@ static int tau_inputs(dsm_ctx *c, int n_iter, const double *gamma_store, const d
     HIP_TRY(hipMemcpyAsync(c->eta_trace, c->eta_in, (size_t)n_iter * 16 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(c->nchange, 0, sizeof(int), c->stream));
     // entry: lp with (gamma_store[0], eta_store[0])  (HaploSNP_Sampler.py:386-389)
-    TRY(eval_state(c, c->gamma_in, c->eta_in, c->tau_trace, 1));
+    DSM_TRY(eval_state(c, c->gamma_in, c->eta_in, c->tau_trace, 1));
     // the Dirichlet log-priors of all stored (gamma, eta) pairs in one launch instead of one per sweep
-    TRY(k_prior_batch(c, c->gamma_in, c->eta_in, n_iter, c->prior_all));
+    DSM_TRY(k_prior_batch(c, c->gamma_in, c->eta_in, n_iter, c->prior_all));
     // sweep it writes parity it & 1 of (ll_partial, nchange); its finalize (ll / lp / MAP test / traces) rides as one
     // extra workgroup in the launch of sweep it + 1, which writes the other parity: one launch per sweep
     HIP_TRY(hipMemsetAsync(c->nchange, 0, 2 * sizeof(int), c->stream));
@@ -1203,21 +1171,21 @@ static int update_tau(dsm_ctx *const *ctxs, int K, bool batched, int n_iter, con
 {
     if (n_iter < 1 || !gamma_stores || !eta_stores) { dsm_set_error("update_tau: bad arguments"); return DSM_ERR_ARG; }
     Chains ch{ctxs, K, batched};
-    TRY(ch.open(true, false, [&](const dsm_ctx *a, const dsm_ctx *b, int k) {
+    DSM_TRY(ch.open(true, false, [&](const dsm_ctx *a, const dsm_ctx *b, int k) {
         if (!gamma_stores[k] || !eta_stores[k]) { dsm_set_error("update_tau: bad arguments"); return DSM_ERR_ARG; }
         return same_G_and_rng(a, b, k);
     }));
     const size_t sg = (size_t)ch.lead()->S * ch.lead()->G;
     std::vector<SweepWords> words;
     words.reserve(K);
-    TRY(ch.each([&](dsm_ctx *c, int) -> int { TRY(alloc_traces(c, n_iter)); words.emplace_back(c, n_iter, c->u_cap); return DSM_OK; }));
-    TRY(ch.launch([&](dsm_ctx *, int k) { return words[k].prefetch(); }));          // (generating while the inputs go in)
-    TRY(ch.each([&](dsm_ctx *c, int k) { return tau_inputs(c, n_iter, gamma_stores[k], eta_stores[k]); }));
+    DSM_TRY(ch.each([&](dsm_ctx *c, int) -> int { DSM_TRY(alloc_traces(c, n_iter)); words.emplace_back(c, n_iter, c->u_cap); return DSM_OK; }));
+    DSM_TRY(ch.launch([&](dsm_ctx *, int k) { return words[k].prefetch(); }));          // (generating while the inputs go in)
+    DSM_TRY(ch.each([&](dsm_ctx *c, int k) { return tau_inputs(c, n_iter, gamma_stores[k], eta_stores[k]); }));
     std::vector<int> nb_prev(K, 0);
     std::vector<const uint32_t *> u(K, nullptr);
     for (int it = 0; it < n_iter; ++it) {
-        TRY(ch.launch([&](dsm_ctx *, int k) { return words[k].acquire(it, &u[k]); }));
-        TRY(ch.launch([&](dsm_ctx *c, int k) -> int {
+        DSM_TRY(ch.launch([&](dsm_ctx *, int k) { return words[k].acquire(it, &u[k]); }));
+        DSM_TRY(ch.launch([&](dsm_ctx *c, int k) -> int {
             const uint32_t ic = c->iter_ctr++;
             const double *g = c->gamma_in + (size_t)it * sg, *e = c->eta_in + (size_t)it * 16;
             TauFinalRider rider;
@@ -1228,9 +1196,9 @@ static int update_tau(dsm_ctx *const *ctxs, int K, bool batched, int n_iter, con
             return k_tau_sweep(c, 3, g, e, e, c->tau_trace + (size_t)(it + 1) * c->V, nullptr, ic, &nb_prev[k], u[k], it & 1,
                                it > 0 ? &rider : nullptr);                                              // :392-393
         }));
-        TRY(ch.each([&](dsm_ctx *, int k) { return words[k].release(it); }));
+        DSM_TRY(ch.each([&](dsm_ctx *, int k) { return words[k].release(it); }));
     }
-    TRY(ch.each([&](dsm_ctx *c, int k) {
+    DSM_TRY(ch.each([&](dsm_ctx *c, int k) {
         return k_finalize(c, nb_prev[k], n_iter - 1, 0, c->prior_all + (size_t)(n_iter - 1) * (c->S + 4),
                           c->gamma_in + (size_t)(n_iter - 1) * sg, c->eta_in + (size_t)(n_iter - 1) * 16, (n_iter - 1) & 1);
     }));
@@ -1278,15 +1246,15 @@ static int fixtau_words(dsm_ctx *c, FixtauWords *p)
 }
 
 // pooled [W][S][4] on the device: zeroed, then fixtau_pool_kernel
-static int fixtau_pool_counts(dsm_ctx *c, const FixtauWords &p, Scratch<int32_t> &d_pooled)
+static int fixtau_pool_counts(dsm_ctx *c, const FixtauWords &p, DevBuf<int32_t> &d_pooled)
 {
     const size_t np = p.words.size() * (size_t)c->S * 4;
-    Scratch<int32_t> d_row;
-    TRY(d_row.alloc((size_t)c->V));
-    TRY(d_pooled.alloc(np));
+    DevBuf<int32_t> d_row;
+    DSM_TRY(d_row.alloc((size_t)c->V));
+    DSM_TRY(d_pooled.alloc(np));
     HIP_TRY(hipMemcpyAsync(d_row, p.row.data(), (size_t)c->V * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(d_pooled, 0, np * sizeof(int32_t), c->stream));
-    TRY(k_fixtau_pool(c, d_row, d_pooled));
+    DSM_TRY(k_fixtau_pool(c, d_row, d_pooled));
     HIP_TRY(hipStreamSynchronize(c->stream));                   // (d_row is released on return)
     return DSM_OK;
 }
@@ -1297,8 +1265,8 @@ static int fixtau_pool_counts(dsm_ctx *c, const FixtauWords &p, Scratch<int32_t>
 static int fixtau_enter(dsm_ctx *c, const FixtauWords &p, dsm_ctx **child_out)
 {
     const int W = (int)p.words.size(), S = c->S, G = c->G;
-    Scratch<int32_t> d_pooled;
-    TRY(fixtau_pool_counts(c, p, d_pooled));
+    DevBuf<int32_t> d_pooled;
+    DSM_TRY(fixtau_pool_counts(c, p, d_pooled));
     const size_t np = (size_t)W * S * 4;
     std::vector<int32_t> h32(np);
     std::vector<double> gamma((size_t)S * G), eta(16);
@@ -1310,11 +1278,11 @@ static int fixtau_enter(dsm_ctx *c, const FixtauWords &p, dsm_ctx **child_out)
     std::vector<int64_t> onehot((size_t)W * G * 4, 0);
     for (int w = 0; w < W; ++w)
         for (int g = 0; g < G; ++g) onehot[((size_t)w * G + g) * 4 + ((p.words[w] >> (2 * g)) & 3)] = 1;
-    if (!c->fixtau_child) TRY(dsm_ctx_create(&c->fixtau_child, c->device));
+    if (!c->fixtau_child) DSM_TRY(dsm_ctx_create(&c->fixtau_child, c->device));
     dsm_ctx *k = c->fixtau_child;
-    TRY(dsm_ctx_set_counts(k, h64.data(), W, S));
-    TRY(dsm_ctx_set_priors(k, c->alpha, c->delta, c->epsilon));
-    TRY(dsm_ctx_set_state(k, onehot.data(), gamma.data(), eta.data(), G));
+    DSM_TRY(dsm_ctx_set_counts(k, h64.data(), W, S));
+    DSM_TRY(dsm_ctx_set_priors(k, c->alpha, c->delta, c->epsilon));
+    DSM_TRY(dsm_ctx_set_state(k, onehot.data(), gamma.data(), eta.data(), G));
     k->ctr_seed = c->ctr_seed; k->iter_ctr = c->iter_ctr;
     k->force_stats_spec = c->force_stats_spec; k->tau_neartie_mode = c->tau_neartie_mode; k->tau_screen = c->tau_screen;
     *child_out = k;
@@ -1325,25 +1293,25 @@ extern "C" int dsm_ctx_gibbs_update_fixed_tau(dsm_ctx *c, int n_iter, int fix_et
 {
     if (n_iter < 0) { dsm_set_error("n_iter < 0"); return DSM_ERR_ARG; }
     if (pool < -1 || pool > 1) { dsm_set_error("gibbs_update_fixed_tau: pool -1 (auto), 0 or 1"); return DSM_ERR_ARG; }
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     BIND(c);
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream_rng));
     bool pooled = false;
     FixtauWords p;
     if (pool != 0) {
-        TRY(fixtau_words(c, &p));
+        DSM_TRY(fixtau_words(c, &p));
         if (p.overflow && pool == 1) { dsm_set_error("gibbs_update_fixed_tau: a pooled count would pass 2^31-1 (run with pool = 0 or -1)"); return DSM_ERR_UNSUPPORTED; }
         // auto: pooling is one pass over the table, less than one iteration's mu/E pass, so any reduction counts as worth it (not measured where it stops paying: DESIGN.md sec. 8c)
         pooled = !p.overflow && (pool == 1 || (int)p.words.size() < c->V);
     }
     if (!pooled) return gibbs_update(&c, 1, false, n_iter, TauStep{c->G, fix_eta != 0});
     dsm_ctx *k = nullptr;
-    TRY(fixtau_enter(c, p, &k));
-    TRY(gibbs_update(&k, 1, false, n_iter, TauStep{k->G, fix_eta != 0}));      // (returns with the child's stream drained)
+    DSM_TRY(fixtau_enter(c, p, &k));
+    DSM_TRY(gibbs_update(&k, 1, false, n_iter, TauStep{k->G, fix_eta != 0}));      // (returns with the child's stream drained)
     // back to the caller: gamma, eta, traces, MAP record, iteration counter; its counts and tau were only read
     const size_t sg = (size_t)c->S * c->G, n = (size_t)n_iter;
-    TRY(alloc_traces(c, n_iter));
+    DSM_TRY(alloc_traces(c, n_iter));
     c->tau_fixed_trace = true;
     auto d2d = [&](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream) : hipSuccess; };
     HIP_TRY(d2d(c->tau_trace, c->tau, (size_t)c->V * sizeof(uint64_t)));
@@ -1359,7 +1327,7 @@ extern "C" int dsm_ctx_gibbs_update_fixed_tau(dsm_ctx *c, int n_iter, int fix_et
     HIP_TRY(d2d(c->eta_star, k->eta_star, 16 * sizeof(double)));
     HIP_TRY(d2d(c->scalars, k->scalars, 2 * sizeof(double)));
     // the multinomial coefficients of the caller's table minus the pooled table's: every reported ll / lp is the caller's table's
-    TRY(k_fixtau_add_const(c, n_iter, c->ll_const - k->ll_const));
+    DSM_TRY(k_fixtau_add_const(c, n_iter, c->ll_const - k->ll_const));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->iter_ctr = k->iter_ctr;
     c->tau_rare_n = k->tau_rare_n;
@@ -1370,7 +1338,7 @@ extern "C" int dsm_ctx_gibbs_update_fixed_tau(dsm_ctx *c, int n_iter, int fix_et
 extern "C" int dsm_ctx_gibbs_update_held_tau(dsm_ctx *c, int n_iter, int n_held, int fix_eta)
 {
     if (n_iter < 0) { dsm_set_error("n_iter < 0"); return DSM_ERR_ARG; }
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     if (n_held < 0 || n_held > c->G) { dsm_set_error("gibbs_update_held_tau: n_held = %d outside 0..%d", n_held, c->G); return DSM_ERR_ARG; }
     if (n_held == 0) return dsm_ctx_gibbs_update(c, n_iter);
     if (n_held == c->G) return dsm_ctx_gibbs_update_fixed_tau(c, n_iter, fix_eta, 0);
@@ -1385,18 +1353,18 @@ extern "C" int dsm_ctx_gibbs_update_held_tau(dsm_ctx *c, int n_iter, int n_held,
 // words [W] ascending (room for V), row [V].  Any pointer may be null.
 extern "C" int dsm_ctx_debug_fixtau_pool(dsm_ctx *c, int *W, int32_t *pooled, uint64_t *words, int32_t *row)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     BIND(c);
     HIP_TRY(hipStreamSynchronize(c->stream));
     FixtauWords p;
-    TRY(fixtau_words(c, &p));
+    DSM_TRY(fixtau_words(c, &p));
     if (p.overflow) { dsm_set_error("debug_fixtau_pool: a pooled count would pass 2^31-1"); return DSM_ERR_UNSUPPORTED; }
     if (W) *W = (int)p.words.size();
     if (words) memcpy(words, p.words.data(), p.words.size() * sizeof(uint64_t));
     if (row) memcpy(row, p.row.data(), p.row.size() * sizeof(int32_t));
     if (pooled) {
-        Scratch<int32_t> d;
-        TRY(fixtau_pool_counts(c, p, d));
+        DevBuf<int32_t> d;
+        DSM_TRY(fixtau_pool_counts(c, p, d));
         HIP_TRY(hipMemcpy(pooled, d, p.words.size() * (size_t)c->S * 4 * sizeof(int32_t), hipMemcpyDeviceToHost));
     }
     return DSM_OK;
@@ -1405,14 +1373,14 @@ extern "C" int dsm_ctx_debug_fixtau_pool(dsm_ctx *c, int *W, int32_t *pooled, ui
 // test hook: dsm_ctx_sample_stats on the pooled state of the resident one (the caller's state and counters are untouched)
 extern "C" int dsm_ctx_debug_fixtau_sample_stats(dsm_ctx *c, uint32_t iter, uint64_t *sum_mu, uint64_t *esum)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     BIND(c);
     HIP_TRY(hipStreamSynchronize(c->stream));
     FixtauWords p;
-    TRY(fixtau_words(c, &p));
+    DSM_TRY(fixtau_words(c, &p));
     if (p.overflow) { dsm_set_error("debug_fixtau_sample_stats: a pooled count would pass 2^31-1"); return DSM_ERR_UNSUPPORTED; }
     dsm_ctx *k = nullptr;
-    TRY(fixtau_enter(c, p, &k));
+    DSM_TRY(fixtau_enter(c, p, &k));
     return dsm_ctx_sample_stats(k, iter, sum_mu, esum);
 }
 
@@ -1429,10 +1397,10 @@ extern "C" int dsm_ctx_debug_log2f(dsm_ctx *c, const float *in, float *out, size
     if (!c || !in || !out) { dsm_set_error("debug_log2f: bad arguments"); return DSM_ERR_ARG; }
     if (n == 0) return DSM_OK;
     BIND(c);
-    Scratch<float> d_in, d_out;
-    TRY(d_in.alloc(n)); TRY(d_out.alloc(n));
+    DevBuf<float> d_in, d_out;
+    DSM_TRY(d_in.alloc(n)); DSM_TRY(d_out.alloc(n));
     HIP_TRY(hipMemcpyAsync(d_in, in, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    TRY(k_log2f_test(c, d_in, d_out, n));
+    DSM_TRY(k_log2f_test(c, d_in, d_out, n));
     HIP_TRY(hipMemcpyAsync(out, d_out, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;
@@ -1441,7 +1409,7 @@ extern "C" int dsm_ctx_debug_log2f(dsm_ctx *c, const float *in, float *out, size
 // workgroups of one tau sweep: launched, and resident at once on this device (occupancy x compute units)
 extern "C" int dsm_ctx_tau_launch_info(dsm_ctx *c, int *launched, int *resident)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     if (!launched || !resident) { dsm_set_error("tau_launch_info: null argument"); return DSM_ERR_ARG; }
     BIND(c);
     return tau_launch_info(c, launched, resident);
@@ -1528,7 +1496,7 @@ extern "C" int dsm_ctx_sweep_stats(dsm_ctx *c, uint64_t *steps, uint64_t *exact_
 
 extern "C" int dsm_ctx_get_trace(dsm_ctx *c, double *ll, double *lp, int32_t *nchange, double *gamma_store, double *eta_store)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     BIND(c);
     const size_t n = (size_t)c->n_trace, sg = (size_t)c->S * c->G;
     if (n == 0) return DSM_OK;
@@ -1543,14 +1511,14 @@ extern "C" int dsm_ctx_get_trace(dsm_ctx *c, double *ll, double *lp, int32_t *nc
 
 extern "C" int dsm_ctx_get_star(dsm_ctx *c, int64_t *tau_star, double *gamma_star, double *eta_star, double *lp_star, int *iter_star)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     if (!c->tau_trace) { dsm_set_error("get_star: no update has run"); return DSM_ERR_STATE; }
     BIND(c);
     double st[2];
     HIP_TRY(hipMemcpyAsync(st, c->star, sizeof st, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const int slot = (int)st[1];
-    if (tau_star) TRY(fetch_tau(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)slot * c->V), tau_star));
+    if (tau_star) DSM_TRY(fetch_tau(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)slot * c->V), tau_star));
     if (gamma_star) HIP_TRY(hipMemcpyAsync(gamma_star, c->gamma_star, (size_t)c->S * c->G * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (eta_star) HIP_TRY(hipMemcpyAsync(eta_star, c->eta_star, 16 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1561,18 +1529,18 @@ extern "C" int dsm_ctx_get_star(dsm_ctx *c, int64_t *tau_star, double *gamma_sta
 
 extern "C" int dsm_ctx_get_tau_sum(dsm_ctx *c, int64_t *tau_sum)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     if (!c->tau_trace || !tau_sum) { dsm_set_error("get_tau_sum: no update has run"); return DSM_ERR_STATE; }
     BIND(c);
     const size_t nt = (size_t)c->V * c->G * 4;
     if (c->tau_fixed_trace) {                 // every stored iteration holds the tau of slot 0
-        TRY(fetch_tau(c, c->tau_trace, tau_sum));
+        DSM_TRY(fetch_tau(c, c->tau_trace, tau_sum));
         for (size_t i = 0; i < nt; ++i) tau_sum[i] *= c->n_trace;
         return DSM_OK;
     }
-    Scratch<int64_t> d;
-    TRY(d.alloc(nt));
-    TRY(k_tau_sum(c, c->tau_trace, c->n_trace, d));
+    DevBuf<int64_t> d;
+    DSM_TRY(d.alloc(nt));
+    DSM_TRY(k_tau_sum(c, c->tau_trace, c->n_trace, d));
     HIP_TRY(hipMemcpyAsync(tau_sum, d, nt * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;
@@ -1580,7 +1548,7 @@ extern "C" int dsm_ctx_get_tau_sum(dsm_ctx *c, int64_t *tau_sum)
 
 extern "C" int dsm_ctx_get_tau_at(dsm_ctx *c, int it, int64_t *tau)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     if (!c->tau_trace || !tau || it < -1 || it >= c->n_trace) { dsm_set_error("get_tau_at: bad iteration"); return DSM_ERR_ARG; }
     BIND(c);
     return fetch_tau(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it + 1) * c->V), tau);
@@ -1606,7 +1574,7 @@ static int pack_digits(const char *who, const int64_t *digits, size_t rows, int 
 // the checks the two trace reductions share: a trace, and a range inside it
 static int trace_range(dsm_ctx *c, const char *who, int it0, int n_it)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     if (!c->tau_trace) { dsm_set_error("%s: no update has run", who); return DSM_ERR_STATE; }
     if (it0 < 0 || n_it < 0 || it0 > c->n_trace || n_it > c->n_trace - it0) {
         dsm_set_error("%s: iterations %d .. %d + %d outside the trace of %d", who, it0, it0, n_it, c->n_trace);
@@ -1633,7 +1601,7 @@ static int perm_inverse(const char *who, const uint8_t *perm, int n_it, int G, s
 
 extern "C" int dsm_ctx_trace_snd(dsm_ctx *c, int mode, const int64_t *ref_tau, int Gr, int it0, int n_it, int32_t *snd)
 {
-    TRY(trace_range(c, "trace_snd", it0, n_it));
+    DSM_TRY(trace_range(c, "trace_snd", it0, n_it));
     if (mode != DSM_SND_STAR && mode != DSM_SND_SELF && mode != DSM_SND_GIVEN) { dsm_set_error("trace_snd: mode %d is none of DSM_SND_STAR / SELF / GIVEN", mode); return DSM_ERR_ARG; }
     if (mode == DSM_SND_GIVEN) {
         if (Gr < 1 || Gr > DSM_MAX_G) { dsm_set_error("trace_snd: Gr=%d outside 1..%d", Gr, DSM_MAX_G); return DSM_ERR_ARG; }
@@ -1644,13 +1612,13 @@ extern "C" int dsm_ctx_trace_snd(dsm_ctx *c, int mode, const int64_t *ref_tau, i
     }
     if (n_it > 0 && !snd) { dsm_set_error("trace_snd: no output buffer"); return DSM_ERR_ARG; }
     std::vector<uint64_t> packed;
-    if (mode == DSM_SND_GIVEN) TRY(pack_digits("trace_snd", ref_tau, (size_t)c->V, Gr, packed));
+    if (mode == DSM_SND_GIVEN) DSM_TRY(pack_digits("trace_snd", ref_tau, (size_t)c->V, Gr, packed));
     if (n_it == 0) return DSM_OK;
     BIND(c);
     const size_t V = (size_t)c->V, stride = c->tau_fixed_trace ? 0 : V;
     const uint64_t *trace = c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it0 + 1) * V);
     const uint64_t *ref = nullptr;
-    Scratch<uint64_t> d_ref;
+    DevBuf<uint64_t> d_ref;
     if (mode == DSM_SND_STAR) {
         double st[2];
         HIP_TRY(hipMemcpyAsync(st, c->star, sizeof st, hipMemcpyDeviceToHost, c->stream));
@@ -1658,14 +1626,14 @@ extern "C" int dsm_ctx_trace_snd(dsm_ctx *c, int mode, const int64_t *ref_tau, i
         if (!(st[1] >= 0.0 && st[1] <= (double)c->n_trace)) { dsm_set_error("trace_snd: the MAP record's slot lies outside the trace of %d", c->n_trace); return DSM_ERR_STATE; }
         ref = c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(int)st[1] * V);
     } else if (mode == DSM_SND_GIVEN) {
-        TRY(d_ref.alloc(V));
+        DSM_TRY(d_ref.alloc(V));
         HIP_TRY(hipMemcpyAsync(d_ref, packed.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
         ref = d_ref;
     }
     const size_t nout = (size_t)n_it * c->G * Gr;
-    Scratch<int> d_out;
-    TRY(d_out.alloc(nout));
-    TRY(k_trace_snd(c, trace, stride, ref, Gr, n_it, d_out));
+    DevBuf<int> d_out;
+    DSM_TRY(d_out.alloc(nout));
+    DSM_TRY(k_trace_snd(c, trace, stride, ref, Gr, n_it, d_out));
     HIP_TRY(hipMemcpyAsync(snd, d_out, nout * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;
@@ -1673,19 +1641,19 @@ extern "C" int dsm_ctx_trace_snd(dsm_ctx *c, int mode, const int64_t *ref_tau, i
 
 extern "C" int dsm_ctx_get_tau_sum_perm(dsm_ctx *c, const uint8_t *perm, int it0, int n_it, int64_t *tau_sum)
 {
-    TRY(trace_range(c, "get_tau_sum_perm", it0, n_it));
+    DSM_TRY(trace_range(c, "get_tau_sum_perm", it0, n_it));
     if (!tau_sum || (n_it > 0 && !perm)) { dsm_set_error("get_tau_sum_perm: null pointer"); return DSM_ERR_ARG; }
     const int G = c->G;
     std::vector<uint8_t> inv;
-    TRY(perm_inverse("get_tau_sum_perm", perm, n_it, G, inv));
+    DSM_TRY(perm_inverse("get_tau_sum_perm", perm, n_it, G, inv));
     BIND(c);
     const size_t V = (size_t)c->V, nt = V * G * 4;
-    Scratch<int64_t> d_out;
-    Scratch<uint8_t> d_inv;
-    TRY(d_out.alloc(nt));
-    TRY(d_inv.alloc(inv.size()));
+    DevBuf<int64_t> d_out;
+    DevBuf<uint8_t> d_inv;
+    DSM_TRY(d_out.alloc(nt));
+    DSM_TRY(d_inv.alloc(inv.size()));
     if (n_it > 0) HIP_TRY(hipMemcpyAsync(d_inv, inv.data(), inv.size(), hipMemcpyHostToDevice, c->stream));
-    TRY(k_tau_sum_perm(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it0 + 1) * V), c->tau_fixed_trace ? 0 : V, d_inv, n_it, d_out));
+    DSM_TRY(k_tau_sum_perm(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it0 + 1) * V), c->tau_fixed_trace ? 0 : V, d_inv, n_it, d_out));
     HIP_TRY(hipMemcpyAsync(tau_sum, d_out, nt * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;
@@ -1695,7 +1663,7 @@ extern "C" int dsm_ctx_get_tau_sum_perm(dsm_ctx *c, const uint8_t *perm, int it0
 extern "C" int dsm_ctx_trace_batch_stats(dsm_ctx *c, const uint8_t *perm, int it0, int n_it, int batch_len, int64_t *sum, int64_t *first,
                                          int64_t *bsq, int32_t *flips)
 {
-    TRY(trace_range(c, "trace_batch_stats", it0, n_it));
+    DSM_TRY(trace_range(c, "trace_batch_stats", it0, n_it));
     if (batch_len < 1) { dsm_set_error("trace_batch_stats: batch_len=%d, at least 1 is needed", batch_len); return DSM_ERR_ARG; }
     if (n_it > 0 && n_it / 2 < batch_len) {
         dsm_set_error("trace_batch_stats: %d iterations are fewer than two batches of %d", n_it, batch_len);
@@ -1703,19 +1671,19 @@ extern "C" int dsm_ctx_trace_batch_stats(dsm_ctx *c, const uint8_t *perm, int it
     }
     const int G = c->G, L = batch_len, B = n_it > 0 ? 2 * (n_it / (2 * L)) : 0, skip = n_it - B * L;       // (n_it > 0: 2 L <= n_it)
     std::vector<uint8_t> inv;
-    TRY(perm_inverse("trace_batch_stats", perm, n_it, G, inv));
+    DSM_TRY(perm_inverse("trace_batch_stats", perm, n_it, G, inv));
     BIND(c);
     const size_t V = (size_t)c->V, nt = V * G * 4, used = (size_t)B * L * G;
-    Scratch<int64_t> d_sum, d_first, d_bsq;
-    Scratch<int32_t> d_flips;
-    Scratch<uint8_t> d_inv;
-    TRY(d_sum.alloc(nt));
-    TRY(d_first.alloc(nt));
-    TRY(d_bsq.alloc(nt));
-    TRY(d_flips.alloc(V * G));
-    TRY(d_inv.alloc(used));
+    DevBuf<int64_t> d_sum, d_first, d_bsq;
+    DevBuf<int32_t> d_flips;
+    DevBuf<uint8_t> d_inv;
+    DSM_TRY(d_sum.alloc(nt));
+    DSM_TRY(d_first.alloc(nt));
+    DSM_TRY(d_bsq.alloc(nt));
+    DSM_TRY(d_flips.alloc(V * G));
+    DSM_TRY(d_inv.alloc(used));
     if (used > 0) HIP_TRY(hipMemcpyAsync(d_inv, inv.data() + (size_t)skip * G, used, hipMemcpyHostToDevice, c->stream));
-    TRY(k_trace_batch_stats(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it0 + 1 + skip) * V), c->tau_fixed_trace ? 0 : V, d_inv, B,
+    DSM_TRY(k_trace_batch_stats(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it0 + 1 + skip) * V), c->tau_fixed_trace ? 0 : V, d_inv, B,
                             L, d_sum, d_first, d_bsq, d_flips));
     if (sum) HIP_TRY(hipMemcpyAsync(sum, d_sum, nt * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     if (first) HIP_TRY(hipMemcpyAsync(first, d_first, nt * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
@@ -1729,7 +1697,7 @@ extern "C" int dsm_ctx_trace_batch_stats(dsm_ctx *c, const uint8_t *perm, int it
 // where it lies -- the counts, the tau, gamma and eta traces -- and nothing of the chain is written
 extern "C" int dsm_ctx_trace_fit_stats(dsm_ctx *c, int it0, int n_it, double *sample, double *position, double *cell)
 {
-    TRY(trace_range(c, "trace_fit_stats", it0, n_it));
+    DSM_TRY(trace_range(c, "trace_fit_stats", it0, n_it));
     const size_t V = (size_t)c->V, S = (size_t)c->S, sg = S * c->G;
     if (n_it == 0) {
         if (sample) std::fill(sample, sample + S * 4, 0.0);
@@ -1738,18 +1706,18 @@ extern "C" int dsm_ctx_trace_fit_stats(dsm_ctx *c, int it0, int n_it, double *sa
         return DSM_OK;
     }
     FitPlan pl;
-    TRY(fit_plan(c, n_it, &pl));
+    DSM_TRY(fit_plan(c, n_it, &pl));
     BIND(c);
-    Scratch<double> d_sample, d_position, d_cell, samp_part, pos_part, cell_part;
-    TRY(d_sample.alloc(S * 4));
-    TRY(d_position.alloc(V * 4));
-    TRY(samp_part.alloc((size_t)pl.parts * pl.tiles * S * 4));
-    TRY(pos_part.alloc((size_t)pl.parts * V * 4));
+    DevBuf<double> d_sample, d_position, d_cell, samp_part, pos_part, cell_part;
+    DSM_TRY(d_sample.alloc(S * 4));
+    DSM_TRY(d_position.alloc(V * 4));
+    DSM_TRY(samp_part.alloc((size_t)pl.parts * pl.tiles * S * 4));
+    DSM_TRY(pos_part.alloc((size_t)pl.parts * V * 4));
     if (cell) {
-        TRY(d_cell.alloc(V * S));
-        TRY(cell_part.alloc((size_t)pl.parts * V * S));
+        DSM_TRY(d_cell.alloc(V * S));
+        DSM_TRY(cell_part.alloc((size_t)pl.parts * V * S));
     }
-    TRY(k_trace_fit_stats(c, pl, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it0 + 1) * V), c->tau_fixed_trace ? 0 : V,
+    DSM_TRY(k_trace_fit_stats(c, pl, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it0 + 1) * V), c->tau_fixed_trace ? 0 : V,
                           c->gamma_trace + (size_t)it0 * sg, c->eta_trace + (size_t)it0 * 16, n_it, samp_part, pos_part, cell_part, d_sample,
                           d_position, cell ? d_cell.p : nullptr));
     if (sample) HIP_TRY(hipMemcpyAsync(sample, d_sample, S * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1762,10 +1730,10 @@ extern "C" int dsm_ctx_trace_fit_stats(dsm_ctx *c, int it0, int n_it, double *sa
 // test hook: which instantiation of the fit kernel, and which grid, a call over n_it iterations would launch (nothing is launched)
 extern "C" int dsm_fit_debug_path(dsm_ctx *c, int n_it, int out[5])
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     if (!out || n_it < 1) { dsm_set_error("fit_debug_path: bad arguments"); return DSM_ERR_ARG; }
     FitPlan pl;
-    TRY(fit_plan(c, n_it, &pl));
+    DSM_TRY(fit_plan(c, n_it, &pl));
     out[0] = pl.nsl; out[1] = pl.lpv; out[2] = pl.gc; out[3] = pl.tiles; out[4] = pl.parts;
     return DSM_OK;
 }
@@ -1773,7 +1741,7 @@ extern "C" int dsm_fit_debug_path(dsm_ctx *c, int n_it, int out[5])
 // test hook: the first n rows of the gamma and eta traces (the companion of dsm_ctx_debug_set_trace, called after it)
 extern "C" int dsm_ctx_debug_set_param_trace(dsm_ctx *c, const double *gamma, const double *eta, int n)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     const int have = c->tau_trace ? c->n_trace : 0;
     if (n < 0 || n > have || (n > 0 && (!gamma || !eta))) {
         dsm_set_error("debug_set_param_trace: n=%d outside the trace of %d, or a null pointer", n, have);
@@ -1793,15 +1761,15 @@ extern "C" int dsm_ctx_debug_set_param_trace(dsm_ctx *c, const double *gamma, co
 // no MAP record yet: it gets the resident state as one (slot 0, lp = -inf), so that DSM_SND_STAR has a reference; an existing record stays.
 extern "C" int dsm_ctx_debug_set_trace(dsm_ctx *c, const int64_t *tau_digits, int n)
 {
-    TRY(need(c, true, true));
+    DSM_TRY(dsm_ctx_need(c, true, true));
     if (n < 0 || (n > 0 && !tau_digits)) { dsm_set_error("debug_set_trace: bad arguments"); return DSM_ERR_ARG; }
     std::vector<uint64_t> packed;
-    TRY(pack_digits("debug_set_trace", tau_digits, (size_t)n * c->V, c->G, packed));
+    DSM_TRY(pack_digits("debug_set_trace", tau_digits, (size_t)n * c->V, c->G, packed));
     BIND(c);
     HIP_TRY(hipStreamSynchronize(c->stream));
     const bool fresh = !c->tau_trace || n > c->trace_cap;
     const bool no_star = !c->tau_trace;
-    TRY(alloc_traces(c, n));
+    DSM_TRY(alloc_traces(c, n));
     const size_t V = (size_t)c->V, sg = (size_t)c->S * c->G;
     if (fresh) {                                      // the other traces of a new allocation read as zero
         const size_t cap = (size_t)c->trace_cap;
@@ -1826,22 +1794,22 @@ extern "C" int dsm_ctx_debug_set_trace(dsm_ctx *c, const int64_t *tau_digits, in
 // ---------------------------------------------------------------- NMFT
 extern "C" int dsm_nmft_set(dsm_ctx *c, const double *tau, const double *gamma, int G)
 {
-    TRY(need(c, true, false));
+    DSM_TRY(dsm_ctx_need(c, true, false));
     if (!tau || !gamma || G < 1 || G > DSM_MAX_G) { dsm_set_error("nmft_set: bad arguments"); return DSM_ERR_ARG; }
     BIND(c);
     HIP_TRY(hipStreamSynchronize(c->stream));
     const int V = c->V, S = c->S;
-    if (!c->F) { TRY(dev_alloc(&c->F, (size_t)V * 4 * S)); TRY(k_nmft_freq(c)); }
+    if (!c->F) { DSM_TRY(dev_alloc(&c->F, (size_t)V * 4 * S)); DSM_TRY(k_nmft_freq(c)); }
     c->nG = G;
     c->nmft_blocks = nmft_grid(c);
-    TRY(dev_alloc(&c->ntau, (size_t)V * 4 * G));
+    DSM_TRY(dev_alloc(&c->ntau, (size_t)V * 4 * G));
     dev_free(&c->ntau2);                                  // sized by the previous G: factorize_tau's fused pass makes it again on first use
-    TRY(dev_alloc(&c->ngam, (size_t)G * S));
-    TRY(dev_alloc(&c->ngam_raw, (size_t)G * S));
-    TRY(dev_alloc(&c->ngam2, (size_t)G * S));            // the other parity's buffers of the update kernel's own gamma step
-    TRY(dev_alloc(&c->ngam_raw2, (size_t)G * S));
-    TRY(dev_alloc(&c->npart, (size_t)std::max(c->nmft_blocks, std::max(nmft_wide_grid(c), nmft_use_mfma(c) ? std::max(nmft_mfma_grid(c, false), nmft_mfma_grid(c, true)) : 0)) * ((size_t)G * S + G + 1)));
-    TRY(dev_alloc(&c->nstat, (size_t)G * S + 2 * G + 16));
+    DSM_TRY(dev_alloc(&c->ngam, (size_t)G * S));
+    DSM_TRY(dev_alloc(&c->ngam_raw, (size_t)G * S));
+    DSM_TRY(dev_alloc(&c->ngam2, (size_t)G * S));            // the other parity's buffers of the update kernel's own gamma step
+    DSM_TRY(dev_alloc(&c->ngam_raw2, (size_t)G * S));
+    DSM_TRY(dev_alloc(&c->npart, (size_t)std::max(c->nmft_blocks, std::max(nmft_wide_grid(c), nmft_use_mfma(c) ? std::max(nmft_mfma_grid(c, false), nmft_mfma_grid(c, true)) : 0)) * ((size_t)G * S + G + 1)));
+    DSM_TRY(dev_alloc(&c->nstat, (size_t)G * S + 2 * G + 16));
     // reference layout tau[v + a*V][g] -> device layout [v][a][g]
     std::vector<double> t((size_t)V * 4 * G);
     for (int a = 0; a < 4; ++a)
@@ -1856,7 +1824,7 @@ extern "C" int dsm_nmft_set(dsm_ctx *c, const double *tau, const double *gamma, 
 
 extern "C" int dsm_nmft_get(dsm_ctx *c, double *tau, double *gamma)
 {
-    TRY(need(c, true, false));
+    DSM_TRY(dsm_ctx_need(c, true, false));
     if (!c->ntau) { dsm_set_error("nmft_get: call dsm_nmft_set first"); return DSM_ERR_STATE; }
     BIND(c);
     const int V = c->V, S = c->S, G = c->nG;
@@ -1883,7 +1851,7 @@ static double *nmft_ctl(dsm_ctx *c) { return c->nstat + (size_t)c->nG * c->S + 2
 // what the update kernels read only during the call, on every return path.
 struct NmftRun {
     dsm_ctx *c = nullptr;
-    Scratch<double> trace;                  // objective after every update
+    DevBuf<double> trace;                  // objective after every update
     double h[12] = {};
     bool fusedfix = false;                  // gamma fixed on the matrix-core kernel: ntau / ntau2 alternate
     bool swap_tau = false, swap_gam = false;    // set by the update loops that alternate a pair (the persistent launch keeps its own)
@@ -1897,7 +1865,7 @@ struct NmftRun {
     int begin(dsm_ctx *ctx, int max_iter, int fix_gamma)
     {
         c = ctx;
-        TRY(trace.alloc((size_t)max_iter + 1));
+        DSM_TRY(trace.alloc((size_t)max_iter + 1));
         HIP_TRY(hipMemsetAsync(nmft_ctl(c), 0, 16 * sizeof(double), c->stream));
         c->ndiv_trace = trace;
         // gamma fixed: the update kernels leave out what only a gamma update reads (kernels_nmft.hip), and on the matrix-core kernel an
@@ -1905,9 +1873,9 @@ struct NmftRun {
         // not by the control step that follows: NmftMfmaParams.fix_gamma == 2)
         fusedfix = fix_gamma && nmft_use_mfma(c);
         c->nmft_fix_gamma = fusedfix ? 2 : fix_gamma ? 1 : 0;
-        if (fusedfix && !c->ntau2) TRY(dev_alloc(&c->ntau2, (size_t)c->V * 4 * c->nG));
+        if (fusedfix && !c->ntau2) DSM_TRY(dev_alloc(&c->ntau2, (size_t)c->V * 4 * c->nG));
         // factorize applies _adjustment once before the first objective (Init_NMFT.py:102)
-        if (!fix_gamma) TRY(k_nmft_clamp(c));
+        if (!fix_gamma) DSM_TRY(k_nmft_clamp(c));
         return DSM_OK;
     }
     int read_ctl() { HIP_TRY(hipMemcpyAsync(h, nmft_ctl(c), sizeof h, hipMemcpyDeviceToHost, c->stream)); return DSM_OK; }
@@ -1923,23 +1891,23 @@ struct NmftRun {
 
 extern "C" int dsm_nmft_factorize(dsm_ctx *c, int max_iter, double min_change, int fix_gamma, int *n_done, double *div_trace)
 {
-    TRY(need(c, true, false));
+    DSM_TRY(dsm_ctx_need(c, true, false));
     if (!c->ntau) { dsm_set_error("nmft_factorize: call dsm_nmft_set first"); return DSM_ERR_STATE; }
     if (max_iter < 0) { dsm_set_error("max_iter < 0"); return DSM_ERR_ARG; }
     BIND(c);
     NmftRun run;
-    TRY(run.begin(c, max_iter, fix_gamma));
+    DSM_TRY(run.begin(c, max_iter, fix_gamma));
     const int adjust = fix_gamma ? 0 : 1;
     const bool fusedfix = run.fusedfix;
     const int BATCH = 64;
     {
         // tables whose quads of variants are all resident at once: the whole loop as ONE persistent launch (kernels_nmft.hip)
         int used = 0;
-        TRY(k_nmft_persist(c, max_iter, min_change, fix_gamma, adjust, &used));
+        DSM_TRY(k_nmft_persist(c, max_iter, min_change, fix_gamma, adjust, &used));
         if (used) {
-            TRY(run.read_ctl());
+            DSM_TRY(run.read_ctl());
             HIP_TRY(hipStreamSynchronize(c->stream));
-            TRY(run.finish(n_done, div_trace));
+            DSM_TRY(run.finish(n_done, div_trace));
             HIP_TRY(hipStreamSynchronize(c->stream));
             return DSM_OK;
         }
@@ -1947,7 +1915,7 @@ extern "C" int dsm_nmft_factorize(dsm_ctx *c, int max_iter, double min_change, i
     const bool wave = nmft_use_wave(c);
     // one-pass path: statistics of the initial state, then every update launch also produces the
     // statistics of the next iteration; two-pass path (large S*G): pass A + pass B per iteration
-    if (wave && !fusedfix) TRY(k_nmft_wave(c, adjust, 0));
+    if (wave && !fusedfix) DSM_TRY(k_nmft_wave(c, adjust, 0));
     // One iteration = the same 2-3 launches every time (the iteration index and the stop flag live in
     // device memory), so BATCH iterations can be captured once into a hipGraph and replayed.  Measured on
     // MI355X / ROCm 7.2: a replayed kernel node costs ~10 us, more than a stream-ordered launch (V=10k: 70 vs
@@ -1961,22 +1929,22 @@ extern "C" int dsm_nmft_factorize(dsm_ctx *c, int max_iter, double min_change, i
     run.swap_gam = gstep;                    // an odd number of gamma steps: the current gamma is in ngam2
     auto enqueue_iteration = [&](int n) -> int {                                     // n = launch number of this call (parity slot)
         if (fusedfix) {                                                              // the pass first: its objective is what the control step tests
-            TRY(k_nmft_wave(c, adjust, 1));
+            DSM_TRY(k_nmft_wave(c, adjust, 1));
             return k_nmft_gamma(c, max_iter, min_change, fix_gamma, adjust, n & 1);
         }
-        if (!wave) TRY(k_nmft_pass_a(c));
+        if (!wave) DSM_TRY(k_nmft_pass_a(c));
         if (gstep) {
             // large tables on the matrix-core kernel (round 6): the reduction, then the update kernel, which begins with the gamma / control
             // step itself (NmftMfmaParams.gstep) -- two launches per update instead of three
-            TRY(k_nmft_reduce(c));
+            DSM_TRY(k_nmft_reduce(c));
             c->nmft_gstep = 1; c->nmft_gstep_parity = n & 1; c->nmft_gstep_max_iter = max_iter; c->nmft_gstep_min_change = min_change;
             const int rc = k_nmft_wave(c, adjust, 1);
             c->nmft_gstep = 0;
             return rc;
         }
         // the control kernel decides ON THE DEVICE whether this update runs at all (Init_NMFT.py:106)
-        TRY(k_nmft_gamma(c, max_iter, min_change, fix_gamma, adjust, n & 1));       // also records div_trace[it]
-        TRY(wave ? k_nmft_wave(c, adjust, 1) : k_nmft_pass_b(c, adjust));           // exits at once when stopped
+        DSM_TRY(k_nmft_gamma(c, max_iter, min_change, fix_gamma, adjust, n & 1));       // also records div_trace[it]
+        DSM_TRY(wave ? k_nmft_wave(c, adjust, 1) : k_nmft_pass_b(c, adjust));           // exits at once when stopped
         return DSM_OK;
     };
     hipGraph_t graph = nullptr;
@@ -1996,12 +1964,12 @@ extern "C" int dsm_nmft_factorize(dsm_ctx *c, int max_iter, double min_change, i
     // iterations 0..max_iter inclusive evaluate the objective; the last one can only stop
     for (int launched = 0; launched <= max_iter;) {
         if (use_graph) { HIP_TRY(hipGraphLaunch(gexec, c->stream)); launched += BATCH; }
-        else { for (int k = 0; k < BATCH && launched <= max_iter; ++k, ++launched) TRY(enqueue_iteration(launched)); }
-        TRY(run.read_ctl());
+        else { for (int k = 0; k < BATCH && launched <= max_iter; ++k, ++launched) DSM_TRY(enqueue_iteration(launched)); }
+        DSM_TRY(run.read_ctl());
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (run.h[2] != 0.0) break;
     }
-    TRY(run.finish(n_done, div_trace));
+    DSM_TRY(run.finish(n_done, div_trace));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;
 }
@@ -2020,32 +1988,32 @@ extern "C" int dsm_batch_nmft_factorize(dsm_ctx *const *ctxs, int K, int max_ite
     // profiles/r06_batch_nmft.txt.  The batched loop already is what the item asked a batch-persistent kernel for.)
     NmftRun run[DSM_MAX_BATCH];             // (before the chains: their destructor drains the stream before the traces are freed)
     Chains ch{ctxs, K, true};
-    TRY(ch.open(false, true, [](const dsm_ctx *a, const dsm_ctx *b, int k) {
+    DSM_TRY(ch.open(false, true, [](const dsm_ctx *a, const dsm_ctx *b, int k) {
         if (!b->ntau) { dsm_set_error("nmft_factorize: call dsm_nmft_set first (chain %d)", k); return DSM_ERR_STATE; }
         if (b->nG != a->nG) { dsm_set_error("batch: chain %d differs from chain 0 in device or shape", k); return DSM_ERR_ARG; }
         if (!nmft_use_mfma(b) && !nmft_use_wide(b)) { dsm_set_error("batch: the matrix-core NMFT kernels do not apply to this shape (S <= 512, G <= 16)"); return DSM_ERR_UNSUPPORTED; }
         return DSM_OK;
     }));
     const int adjust = fix_gamma ? 0 : 1;
-    TRY(ch.each([&](dsm_ctx *c, int k) { return run[k].begin(c, max_iter, fix_gamma); }));
+    DSM_TRY(ch.each([&](dsm_ctx *c, int k) { return run[k].begin(c, max_iter, fix_gamma); }));
     // gamma fixed: the fused pass where the shape has one (S <= 128), else the two-half form of nmft_split_kernel without gamma numerators
     const bool fused = run[0].fusedfix;
     for (int k = 0; k < K; ++k) run[k].swap_tau = fused;
-    if (!fused) TRY(ch.launch([&](dsm_ctx *c, int) { return k_nmft_wave(c, adjust, 0); }));
+    if (!fused) DSM_TRY(ch.launch([&](dsm_ctx *c, int) { return k_nmft_wave(c, adjust, 0); }));
     const int BATCH = 64;
     for (int launched = 0; launched <= max_iter;) {
         for (int i = 0; i < BATCH && launched <= max_iter; ++i, ++launched) {
-            if (fused) TRY(ch.launch([&](dsm_ctx *c, int) { return k_nmft_wave(c, adjust, 1); }));     // the fused pass first: its objective is what the control step tests
-            TRY(ch.launch([&](dsm_ctx *c, int) { return k_nmft_gamma(c, max_iter, min_change, fix_gamma, adjust, launched & 1); }));
-            if (!fused) TRY(ch.launch([&](dsm_ctx *c, int) { return k_nmft_wave(c, adjust, 1); }));
+            if (fused) DSM_TRY(ch.launch([&](dsm_ctx *c, int) { return k_nmft_wave(c, adjust, 1); }));     // the fused pass first: its objective is what the control step tests
+            DSM_TRY(ch.launch([&](dsm_ctx *c, int) { return k_nmft_gamma(c, max_iter, min_change, fix_gamma, adjust, launched & 1); }));
+            if (!fused) DSM_TRY(ch.launch([&](dsm_ctx *c, int) { return k_nmft_wave(c, adjust, 1); }));
         }
-        TRY(ch.each([&](dsm_ctx *, int k) { return run[k].read_ctl(); }));
+        DSM_TRY(ch.each([&](dsm_ctx *, int k) { return run[k].read_ctl(); }));
         HIP_TRY(hipStreamSynchronize(ch.lead()->stream));
         bool all = true;
         for (int k = 0; k < K; ++k) all = all && run[k].h[2] != 0.0;
         if (all) break;
     }
-    TRY(ch.each([&](dsm_ctx *, int k) {
+    DSM_TRY(ch.each([&](dsm_ctx *, int k) {
         return run[k].finish(n_done ? n_done + k : nullptr, div_traces ? div_traces + (size_t)k * ((size_t)max_iter + 1) : nullptr);
     }));
     HIP_TRY(hipStreamSynchronize(ch.lead()->stream));
@@ -2055,7 +2023,7 @@ extern "C" int dsm_batch_nmft_factorize(dsm_ctx *const *ctxs, int K, int max_ite
 // test hook (read only): the kernel family and instantiation dsm_nmft_factorize takes for this context as it is set up now
 extern "C" int dsm_nmft_debug_path(dsm_ctx *c, int fix_gamma, int *out)
 {
-    TRY(need(c, true, false));
+    DSM_TRY(dsm_ctx_need(c, true, false));
     if (!out) { dsm_set_error("nmft_debug_path: out is null"); return DSM_ERR_ARG; }
     if (!c->ntau) { dsm_set_error("nmft_debug_path: call dsm_nmft_set first"); return DSM_ERR_STATE; }
     BIND(c);
@@ -2064,12 +2032,12 @@ extern "C" int dsm_nmft_debug_path(dsm_ctx *c, int fix_gamma, int *out)
 
 extern "C" int dsm_nmft_objective(dsm_ctx *c, double *div)
 {
-    TRY(need(c, true, false));
+    DSM_TRY(dsm_ctx_need(c, true, false));
     if (!c->ntau || !div) { dsm_set_error("nmft_objective: call dsm_nmft_set first"); return DSM_ERR_STATE; }
     BIND(c);
     HIP_TRY(hipMemsetAsync(nmft_ctl(c), 0, 16 * sizeof(double), c->stream));
-    TRY(nmft_use_wave(c) ? k_nmft_wave(c, 0, 0) : k_nmft_pass_a(c));
-    TRY(k_nmft_gamma(c, 0, 0.0, 1, 0, 0));     // max_iter = 0: reduce + record div only
+    DSM_TRY(nmft_use_wave(c) ? k_nmft_wave(c, 0, 0) : k_nmft_pass_a(c));
+    DSM_TRY(k_nmft_gamma(c, 0, 0.0, 1, 0, 0));     // max_iter = 0: reduce + record div only
     HIP_TRY(hipMemcpyAsync(div, nmft_ctl(c), sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;
@@ -2077,12 +2045,12 @@ extern "C" int dsm_nmft_objective(dsm_ctx *c, double *div)
 
 extern "C" int dsm_nmft_get_tau(dsm_ctx *c, int64_t *tau_onehot)
 {
-    TRY(need(c, true, false));
+    DSM_TRY(dsm_ctx_need(c, true, false));
     if (!c->ntau || !tau_onehot) { dsm_set_error("nmft_get_tau: call dsm_nmft_set first"); return DSM_ERR_STATE; }
     BIND(c);
-    Scratch<uint64_t> d_p;
-    TRY(d_p.alloc((size_t)c->V));
-    TRY(k_nmft_get_tau(c, d_p));
+    DevBuf<uint64_t> d_p;
+    DSM_TRY(d_p.alloc((size_t)c->V));
+    DSM_TRY(k_nmft_get_tau(c, d_p));
     const int Gs = c->G;
     c->G = c->nG;
     int r = fetch_tau(c, d_p, tau_onehot);
@@ -2140,7 +2108,7 @@ static int legacy_ctx()
 extern "C" int dsm_initRNG(void)
 {
     std::lock_guard<std::mutex> lk(g_legacy_mu);
-    TRY(legacy_ctx());
+    DSM_TRY(legacy_ctx());
     g_legacy_rng = true;
     return seed_mt(g_legacy, 0);          // gsl_rng_alloc: default seed
 }
@@ -2185,13 +2153,13 @@ extern "C" int dsm_sample_tau(int64_t *tau, const double *pi, const double *eta,
     const uint64_t hsh = hash_words(variants, (size_t)nV * nS * 4);
     if (!(c->cnt_vs && variants == g_legacy_ptr && nV == g_legacy_V && nS == g_legacy_S && hsh == g_legacy_hash)) {
         g_legacy_ptr = nullptr;
-        TRY(dsm_ctx_set_counts(c, variants, nV, nS));
+        DSM_TRY(dsm_ctx_set_counts(c, variants, nV, nS));
         g_legacy_ptr = variants; g_legacy_V = nV; g_legacy_S = nS; g_legacy_hash = hsh;
     }
-    TRY(dsm_ctx_set_state(c, tau, pi, eta, nG));
+    DSM_TRY(dsm_ctx_set_state(c, tau, pi, eta, nG));
     int n = 0;
-    TRY(dsm_ctx_sample_tau(c, &n, nullptr));
-    TRY(dsm_ctx_get_state(c, tau, nullptr, nullptr));
+    DSM_TRY(dsm_ctx_sample_tau(c, &n, nullptr));
+    DSM_TRY(dsm_ctx_get_state(c, tau, nullptr, nullptr));
     return n;
 }
 

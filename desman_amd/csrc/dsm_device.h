@@ -80,6 +80,13 @@ __device__ __forceinline__ unsigned group_allreduce_sum_u32(unsigned x)
     for (int off = W / 2; off >= 1; off >>= 1) x += __shfl_xor(x, off, 64);
     return x;
 }
+// the largest of the wavefront's 64 values, on every lane (assign_kernel, pred_kernel)
+__device__ __forceinline__ double wave_max_f64(double x)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) x = fmax(x, __shfl_xor(x, off, 64));
+    return x;
+}
 
 // ---- table-driven fp64 natural log (tau sweep / LL).  x = 2^e * m, m in [1,2);
 // i = top 8 mantissa bits (256-entry table); r = m * invc_i - 1 (one fma, |r| <= 2^-9);

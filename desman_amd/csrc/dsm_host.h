@@ -293,6 +293,13 @@ int k_held_sweep(dsm_ctx *c, int n_held, const double *gamma, const double *eta,
 // every tau RNG mode; the changed digits are added to *c->nchange
 int k_pair_sweep(dsm_ctx *c, const double *gamma, const double *eta, uint32_t iter);
 
+// ---- the 4^G joint states of a position as assign_kernel and pred_kernel walk them (kernels_assign.hip): the GO outer haplotypes are
+// NB = 4^GO blocks of 64 states, cut into P = min(NB, 64) partials of bpp consecutive blocks, one wavefront each.  P depends on G only.
+struct JointSplit {
+    int GO, NB, P, bpp;
+    explicit JointSplit(int G) : GO(G > 3 ? G - 3 : 0), NB(1 << (2 * GO)), P(NB < 64 ? NB : 64), bpp(NB / P) {}
+};
+
 // ---- launchers (kernels_relabel.hip): reductions of the tau trace; trace_stride = words between two iterations' rows (0: one row for all)
 int k_trace_snd(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const uint64_t *ref, int Gr, int n_it, int *d_out);   // ref null: each iteration against itself
 int k_tau_sum_perm(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const uint8_t *d_inv, int n, int64_t *d_out);      // inv[t][perm[t][g]] = g

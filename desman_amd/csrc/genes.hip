@@ -20,6 +20,7 @@
 
 #include "dsm_device.h"
 #include "dsm_host.h"
+#include "dsm_host_util.h"
 #include "log_table.h"
 
 #define DSM_STREAM_GENE 0x47454E45u   // 'GENE'  tau-sweep uniforms of the batched gene sampler
@@ -28,29 +29,19 @@
 #define GENE_MIN_DELTA 1.0e-10        // Eta_Sampler.py:18
 #define GENE_ETA_PENALTY (-1.0e3)     // Eta_Sampler.py:19
 
-#define TRY(x) do { int _r = (x); if (_r != DSM_OK) return _r; } while (0)
-
 namespace {
 
 template <typename T>
-struct DBuf {                         // device array owned by the host object
-    T *p = nullptr;
+struct DBuf : DevBuf<T> {             // device array owned by the host object: it only grows
     size_t n = 0;
-    ~DBuf() { if (p) (void)hipFree(p); }
     int resize(size_t count)
     {
-        if (count <= n && p) return DSM_OK;
-        if (p) { (void)hipFree(p); p = nullptr; n = 0; }
-        const size_t bytes = (count ? count : 1) * sizeof(T);
-        const hipError_t e = hipMalloc((void **)&p, bytes);
-        if (e != hipSuccess) { dsm_set_error("hipMalloc(%zu B) failed: %s", bytes, hipGetErrorString(e)); return DSM_ERR_NOMEM; }
+        if (count <= n && this->p) return DSM_OK;
+        n = 0;
+        DSM_TRY(this->alloc(count));
         n = count;
         return DSM_OK;
     }
-    operator T *() const { return p; }
-    DBuf() = default;
-    DBuf(const DBuf &) = delete;
-    DBuf &operator=(const DBuf &) = delete;
 };
 
 // numpy's add.reduce over a contiguous axis of length n (what gammaR.sum(axis=1) does, maskGamma :154):
@@ -710,7 +701,7 @@ extern "C" int dsm_genes_create(dsm_genes **out, int device)
     if (!out) { dsm_set_error("null out pointer"); return DSM_ERR_ARG; }
     *out = nullptr;
     dsm_ctx *base = nullptr;
-    TRY(dsm_ctx_create(&base, device));
+    DSM_TRY(dsm_ctx_create(&base, device));
     dsm_genes *gs = new dsm_genes();
     gs->base = base;
     gs->device = device;
@@ -767,18 +758,18 @@ extern "C" int dsm_genes_set_data(dsm_genes *gs, const int64_t *variants, int Vt
         gs->task_off_h[c + 1] = (int32_t)(tab.size() / 2);
     }
     gs->ntask = (int)(tab.size() / 2);
-    TRY(gs->gene_off.resize(C + 1));
-    TRY(gs->task_tab.resize(tab.size()));
-    TRY(gs->gene_of.resize(gof.size()));
-    TRY(gs->cov.resize((size_t)C * S));
-    TRY(gs->cnt_vs.resize((size_t)Vtot * S * 4));
-    TRY(gs->tau0.resize(Vtot)); TRY(gs->tau1.resize(Vtot)); TRY(gs->tau2.resize(Vtot));
-    TRY(gs->cur.resize(C));
-    TRY(gs->nchange.resize((size_t)C * 2));
-    TRY(gs->n_iter.resize(C));
-    TRY(gs->lv_keep.resize(C)); TRY(gs->gene_ll.resize(C)); TRY(gs->gene_llstar.resize(C));
-    TRY(gs->v_ll.resize((size_t)2 * (Vtot ? Vtot : 1)));
-    TRY(gs->u_off.resize((size_t)C * 2));
+    DSM_TRY(gs->gene_off.resize(C + 1));
+    DSM_TRY(gs->task_tab.resize(tab.size()));
+    DSM_TRY(gs->gene_of.resize(gof.size()));
+    DSM_TRY(gs->cov.resize((size_t)C * S));
+    DSM_TRY(gs->cnt_vs.resize((size_t)Vtot * S * 4));
+    DSM_TRY(gs->tau0.resize(Vtot)); DSM_TRY(gs->tau1.resize(Vtot)); DSM_TRY(gs->tau2.resize(Vtot));
+    DSM_TRY(gs->cur.resize(C));
+    DSM_TRY(gs->nchange.resize((size_t)C * 2));
+    DSM_TRY(gs->n_iter.resize(C));
+    DSM_TRY(gs->lv_keep.resize(C)); DSM_TRY(gs->gene_ll.resize(C)); DSM_TRY(gs->gene_llstar.resize(C));
+    DSM_TRY(gs->v_ll.resize((size_t)2 * (Vtot ? Vtot : 1)));
+    DSM_TRY(gs->u_off.resize((size_t)C * 2));
     HIP_TRY(hipMemcpyAsync(gs->gene_off, gene_off, (C + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if (!tab.empty()) HIP_TRY(hipMemcpyAsync(gs->task_tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(gs->gene_of, gof.data(), gof.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -790,8 +781,8 @@ extern "C" int dsm_genes_set_data(dsm_genes *gs, const int64_t *variants, int Vt
         const size_t n = (size_t)Vtot * S * 4;
         DBuf<int64_t> raw;
         DBuf<int> flag;
-        TRY(raw.resize(n));
-        TRY(flag.resize(1));
+        DSM_TRY(raw.resize(n));
+        DSM_TRY(flag.resize(1));
         HIP_TRY(hipMemsetAsync(flag, 0, sizeof(int), st));
         HIP_TRY(hipMemcpyAsync(raw, variants, n * sizeof(int64_t), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(gene_convert_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, raw, gs->cnt_vs, n, flag);
@@ -813,7 +804,7 @@ extern "C" int dsm_genes_set_model(dsm_genes *gs, const double *gamma, const dou
                                    int G, int max_eta, const double *eta_log_prior, const double *cov_const,
                                    const double *mult_const)
 {
-    TRY(genes_need(gs, false, false));
+    DSM_TRY(genes_need(gs, false, false));
     if (!gamma || !epsilon || !delta || !eta_log_prior || !cov_const || !mult_const) { dsm_set_error("set_model: null pointer"); return DSM_ERR_ARG; }
     if (G < 1 || G > DSM_MAX_G) { dsm_set_error("G=%d outside 1..%d", G, DSM_MAX_G); return DSM_ERR_UNSUPPORTED; }
     if (max_eta < 2 || max_eta > DSM_MAX_ETA) { dsm_set_error("max_eta=%d outside 2..%d", max_eta, DSM_MAX_ETA); return DSM_ERR_UNSUPPORTED; }
@@ -822,9 +813,9 @@ extern "C" int dsm_genes_set_model(dsm_genes *gs, const double *gamma, const dou
     const int S = gs->S, C = gs->C;
     if (G != gs->G) gs->have_state = false;
     gs->G = G; gs->max_eta = max_eta;
-    TRY(gs->gamma.resize((size_t)S * G)); TRY(gs->eps.resize(16)); TRY(gs->delta.resize((size_t)G * S));
-    TRY(gs->prior.resize(DSM_MAX_ETA)); TRY(gs->cov_const.resize(C)); TRY(gs->mult_const.resize(C));
-    TRY(gs->eta.resize((size_t)C * G)); TRY(gs->eta_star.resize((size_t)C * G));
+    DSM_TRY(gs->gamma.resize((size_t)S * G)); DSM_TRY(gs->eps.resize(16)); DSM_TRY(gs->delta.resize((size_t)G * S));
+    DSM_TRY(gs->prior.resize(DSM_MAX_ETA)); DSM_TRY(gs->cov_const.resize(C)); DSM_TRY(gs->mult_const.resize(C));
+    DSM_TRY(gs->eta.resize((size_t)C * G)); DSM_TRY(gs->eta_star.resize((size_t)C * G));
     HIP_TRY(hipMemcpyAsync(gs->gamma, gamma, (size_t)S * G * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(gs->eps, epsilon, 16 * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(gs->delta, delta, (size_t)G * S * sizeof(double), hipMemcpyHostToDevice, st));
@@ -838,7 +829,7 @@ extern "C" int dsm_genes_set_model(dsm_genes *gs, const double *gamma, const dou
 
 extern "C" int dsm_genes_set_state(dsm_genes *gs, const int32_t *eta, const int64_t *tau)
 {
-    TRY(genes_need(gs, true, false));
+    DSM_TRY(genes_need(gs, true, false));
     GBIND(gs);
     hipStream_t st = gs->base->stream;
     const int C = gs->C, G = gs->G, V = gs->Vtot;
@@ -851,7 +842,7 @@ extern "C" int dsm_genes_set_state(dsm_genes *gs, const int32_t *eta, const int6
     }
     if (tau && V > 0) {
         DBuf<int64_t> raw;
-        TRY(raw.resize((size_t)V * G * 4));
+        DSM_TRY(raw.resize((size_t)V * G * 4));
         HIP_TRY(hipMemcpyAsync(raw, tau, (size_t)V * G * 4 * sizeof(int64_t), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemsetAsync(gs->cur, 0, C * sizeof(int32_t), st));
         hipLaunchKernelGGL(gene_pack_kernel, dim3((V + 255) / 256), dim3(256), 0, st, raw, gs->tau0, V, G);
@@ -865,7 +856,7 @@ extern "C" int dsm_genes_set_state(dsm_genes *gs, const int32_t *eta, const int6
 
 extern "C" int dsm_genes_get_state(dsm_genes *gs, int32_t *eta, int64_t *tau)
 {
-    TRY(genes_need(gs, true, true));
+    DSM_TRY(genes_need(gs, true, true));
     GBIND(gs);
     hipStream_t st = gs->base->stream;
     const int C = gs->C, G = gs->G, V = gs->Vtot;
@@ -873,7 +864,7 @@ extern "C" int dsm_genes_get_state(dsm_genes *gs, int32_t *eta, int64_t *tau)
     if (tau && V > 0) {
         DBuf<int64_t> raw;
         const size_t n = (size_t)V * G;
-        TRY(raw.resize(n * 4));
+        DSM_TRY(raw.resize(n * 4));
         hipLaunchKernelGGL(gene_unpack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gs->tau0, gs->tau1, gs->tau2,
                            gs->cur, gs->gene_of, raw, V, G);
         HIP_TRY(hipGetLastError());
@@ -964,11 +955,11 @@ static int launch_sweep(dsm_genes *gs, const GeneSweepParams &p, bool sweep, int
     if (ntask <= 0) return DSM_OK;
     int block = 256;
     size_t sh = 0;
-    TRY(sweep_geometry(gs, &block, &sh));
+    DSM_TRY(sweep_geometry(gs, &block, &sh));
     const int gpb = block / gs->LPV, nb = (ntask + gpb - 1) / gpb;
     hipStream_t st = gs->base->stream;
     // one case per tile pick_tile can return; a tile without a case is an error, not an empty launch
-#define GS_CASE(L, N) if (gs->LPV == L && gs->NSL == N) TRY((launch_sweep_t<L, N>(p, sweep, nb, ncand, block, sh, st))); else
+#define GS_CASE(L, N) if (gs->LPV == L && gs->NSL == N) DSM_TRY((launch_sweep_t<L, N>(p, sweep, nb, ncand, block, sh, st))); else
     GS_CASE(16, 1) GS_CASE(16, 2) GS_CASE(16, 3) GS_CASE(32, 2) GS_CASE(32, 3)
     GS_CASE(64, 2) GS_CASE(64, 3) GS_CASE(64, 4) GS_CASE(64, 6) GS_CASE(64, 8)
     { dsm_set_error("gene sweep: no kernel for the tile %d x %d (S=%d)", gs->LPV, gs->NSL, gs->S); return DSM_ERR_UNSUPPORTED; }
@@ -983,7 +974,7 @@ extern "C" int dsm_genes_debug_tile(const dsm_genes *gs, int *lpv, int *nsl, int
     if (!gs || !gs->have_data || !gs->have_model) { dsm_set_error("debug_tile: needs set_data and set_model"); return DSM_ERR_ARG; }
     int block = 0;
     size_t lds = 0;
-    TRY(sweep_geometry(gs, &block, &lds));
+    DSM_TRY(sweep_geometry(gs, &block, &lds));
     if (lpv) *lpv = gs->LPV;
     if (nsl) *nsl = gs->NSL;
     if (groups_per_block) *groups_per_block = block / gs->LPV;
@@ -1016,7 +1007,7 @@ static int mask_source(dsm_genes *gs, const int32_t *eta_mask, DBuf<int32_t> &tm
 {
     const size_t n = (size_t)gs->C * gs->G;
     if (eta_mask) {
-        TRY(tmp.resize(n));
+        DSM_TRY(tmp.resize(n));
         HIP_TRY(hipMemcpyAsync(tmp, eta_mask, n * sizeof(int32_t), hipMemcpyHostToDevice, gs->base->stream));
         host.assign(eta_mask, eta_mask + n);
         *d_eta = tmp;
@@ -1039,7 +1030,7 @@ static bool row_active(const std::vector<int32_t> &eta, int c, int G)
 extern "C" int dsm_genes_nmft_tau(dsm_genes *gs, const int32_t *eta_mask, const double *tau_init, int max_iter,
                                   double min_change, int32_t *n_iter)
 {
-    TRY(genes_need(gs, true, true));
+    DSM_TRY(genes_need(gs, true, true));
     if (!tau_init) { dsm_set_error("nmft_tau: null tau_init"); return DSM_ERR_ARG; }
     GBIND(gs);
     hipStream_t st = gs->base->stream;
@@ -1048,10 +1039,10 @@ extern "C" int dsm_genes_nmft_tau(dsm_genes *gs, const int32_t *eta_mask, const 
     DBuf<int32_t> tmp;
     const int32_t *d_eta = nullptr;
     std::vector<int32_t> host;
-    TRY(mask_source(gs, eta_mask, tmp, &d_eta, host));
+    DSM_TRY(mask_source(gs, eta_mask, tmp, &d_eta, host));
     DBuf<double> tauf, F;
-    TRY(tauf.resize((size_t)V * 4 * G));
-    TRY(F.resize((size_t)V * 4 * S));
+    DSM_TRY(tauf.resize((size_t)V * 4 * G));
+    DSM_TRY(F.resize((size_t)V * 4 * S));
     HIP_TRY(hipMemcpyAsync(tauf, tau_init, (size_t)V * 4 * G * sizeof(double), hipMemcpyHostToDevice, st));
     GeneNmftParams p;
     p.cnt_vs = gs->cnt_vs; p.gene_off = gs->gene_off; p.eta = d_eta; p.gamma = gs->gamma; p.tauf = tauf; p.F = F;
@@ -1076,14 +1067,14 @@ extern "C" int dsm_genes_nmft_tau(dsm_genes *gs, const int32_t *eta_mask, const 
 extern "C" int dsm_genes_sweep_all(dsm_genes *gs, const int32_t *eta_mask, int sweep, int32_t *nchange, double *logvar,
                                    double *v_ll)
 {
-    TRY(genes_need(gs, true, true));
+    DSM_TRY(genes_need(gs, true, true));
     GBIND(gs);
     hipStream_t st = gs->base->stream;
     const int C = gs->C, G = gs->G;
     DBuf<int32_t> tmp;
     const int32_t *d_eta = nullptr;
     std::vector<int32_t> host;
-    TRY(mask_source(gs, eta_mask, tmp, &d_eta, host));
+    DSM_TRY(mask_source(gs, eta_mask, tmp, &d_eta, host));
     const uint32_t *u = nullptr;
     if (sweep == 1 && gs->ntask > 0) {
         // GSL stream in gene order, genes without variants or with an empty mask draw nothing
@@ -1095,16 +1086,16 @@ extern "C" int dsm_genes_sweep_all(dsm_genes *gs, const int32_t *eta_mask, int s
             if (n > 0 && row_active(host, c, G)) pos += n;
         }
         if (!gs->base->mt_seeded) { dsm_set_error("tau RNG not seeded: call dsm_genes_seed"); return DSM_ERR_STATE; }
-        TRY(gs->u_raw.resize((size_t)pos));
+        DSM_TRY(gs->u_raw.resize((size_t)pos));
         HIP_TRY(hipMemcpyAsync(gs->u_off, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        TRY(k_mt_fill(gs->base, gs->u_raw, (size_t)pos, st));
+        DSM_TRY(k_mt_fill(gs->base, gs->u_raw, (size_t)pos, st));
         u = gs->u_raw;
         HIP_TRY(hipMemsetAsync(gs->nchange, 0, (size_t)C * 2 * sizeof(int32_t), st));
     }
     if (sweep == 2 && gs->ntask > 0) HIP_TRY(hipMemsetAsync(gs->nchange, 0, (size_t)C * 2 * sizeof(int32_t), st));
     const uint32_t iter = (sweep == 2) ? gs->iter_ctr++ : 0u;     // counter-based draws: a fresh iteration index per sweep
     const GeneSweepParams p = sweep_params(gs, d_eta, u, -1, 0, gs->ntask, iter);
-    TRY(launch_sweep(gs, p, sweep != 0, 1));
+    DSM_TRY(launch_sweep(gs, p, sweep != 0, 1));
     std::vector<double> vl((size_t)(gs->Vtot ? gs->Vtot : 1));
     std::vector<int32_t> nch((size_t)C * 2, 0);
     if (gs->Vtot > 0) HIP_TRY(hipMemcpyAsync(vl.data(), gs->v_ll, gs->Vtot * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1128,7 +1119,7 @@ extern "C" int dsm_genes_sweep_all(dsm_genes *gs, const int32_t *eta_mask, int s
 // ---------------------------------------------------------------- reference-order single step
 extern "C" int dsm_genes_step_candidates(dsm_genes *gs, int c, int g, double *logvar, int *swept)
 {
-    TRY(genes_need(gs, true, true));
+    DSM_TRY(genes_need(gs, true, true));
     if (c < 0 || c >= gs->C || g < 0 || g >= gs->G || !logvar) { dsm_set_error("step_candidates: bad arguments"); return DSM_ERR_ARG; }
     GBIND(gs);
     hipStream_t st = gs->base->stream;
@@ -1144,11 +1135,11 @@ extern "C" int dsm_genes_step_candidates(dsm_genes *gs, int c, int g, double *lo
     const int64_t n = (int64_t)Vc * G;
     const int64_t off[2] = {0, any0 ? n : 0};          // candidate 0 draws first, only if it sweeps (update:237-238)
     const size_t words = (size_t)(any0 ? 2 * n : n);
-    TRY(gs->u_raw.resize(words));
+    DSM_TRY(gs->u_raw.resize(words));
     HIP_TRY(hipMemcpyAsync(gs->u_off.p + (size_t)c * 2, off, sizeof off, hipMemcpyHostToDevice, st));
-    TRY(k_mt_fill(gs->base, gs->u_raw, words, st));
+    DSM_TRY(k_mt_fill(gs->base, gs->u_raw, words, st));
     const GeneSweepParams p = sweep_params(gs, gs->eta, gs->u_raw, g, gs->task_off_h[c], gs->task_off_h[c + 1], 0);
-    TRY(launch_sweep(gs, p, true, 2));
+    DSM_TRY(launch_sweep(gs, p, true, 2));
     const int lo = gs->gene_off_h[c];
     std::vector<double> vl((size_t)2 * Vc);
     HIP_TRY(hipMemcpyAsync(vl.data(), gs->v_ll.p + lo, Vc * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1166,7 +1157,7 @@ extern "C" int dsm_genes_step_candidates(dsm_genes *gs, int c, int g, double *lo
 
 extern "C" int dsm_genes_step_choose(dsm_genes *gs, int c, int g, int eta_value)
 {
-    TRY(genes_need(gs, true, true));
+    DSM_TRY(genes_need(gs, true, true));
     if (c < 0 || c >= gs->C || g < 0 || g >= gs->G || eta_value < 0 || eta_value >= gs->max_eta) {
         dsm_set_error("step_choose: bad arguments"); return DSM_ERR_ARG;
     }
@@ -1182,24 +1173,24 @@ extern "C" int dsm_genes_step_choose(dsm_genes *gs, int c, int g, int eta_value)
 static int eval_genes(dsm_genes *gs, int reset_star)
 {
     const GeneSweepParams sp = sweep_params(gs, gs->eta, nullptr, -1, 0, gs->ntask, 0);
-    TRY(launch_sweep(gs, sp, false, 1));
+    DSM_TRY(launch_sweep(gs, sp, false, 1));
     const GeneChooseParams cp = choose_params(gs, -1, 1, reset_star, 0);
     return launch_choose(gs, cp);
 }
 
 extern "C" int dsm_genes_loglik(dsm_genes *gs, double *gene_ll)
 {
-    TRY(genes_need(gs, true, true));
+    DSM_TRY(genes_need(gs, true, true));
     GBIND(gs);
     hipStream_t st = gs->base->stream;
     DBuf<double> keep_ll;
     DBuf<int32_t> keep_eta;
     // the evaluation must not disturb the MAP record: run it against scratch copies
-    TRY(keep_ll.resize(gs->C));
-    TRY(keep_eta.resize((size_t)gs->C * gs->G));
+    DSM_TRY(keep_ll.resize(gs->C));
+    DSM_TRY(keep_eta.resize((size_t)gs->C * gs->G));
     HIP_TRY(hipMemcpyAsync(keep_ll, gs->gene_llstar, gs->C * sizeof(double), hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(keep_eta, gs->eta_star, (size_t)gs->C * gs->G * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    TRY(eval_genes(gs, 1));
+    DSM_TRY(eval_genes(gs, 1));
     HIP_TRY(hipMemcpyAsync(gs->gene_llstar, keep_ll, gs->C * sizeof(double), hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(gs->eta_star, keep_eta, (size_t)gs->C * gs->G * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     if (gene_ll) HIP_TRY(hipMemcpyAsync(gene_ll, gs->gene_ll, gs->C * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1210,7 +1201,7 @@ extern "C" int dsm_genes_loglik(dsm_genes *gs, double *gene_ll)
 extern "C" int dsm_genes_update(dsm_genes *gs, int n_iter, int reset_star, int32_t *eta_store, double *gene_ll_trace,
                                 const uint32_t *u_tau_ext, const double *u_eta_ext)
 {
-    TRY(genes_need(gs, true, true));
+    DSM_TRY(genes_need(gs, true, true));
     if (n_iter < 0) { dsm_set_error("update: n_iter < 0"); return DSM_ERR_ARG; }
     GBIND(gs);
     hipStream_t st = gs->base->stream;
@@ -1219,14 +1210,14 @@ extern "C" int dsm_genes_update(dsm_genes *gs, int n_iter, int reset_star, int32
     DBuf<int32_t> d_store;
     DBuf<double> d_trace, d_ue;
     DBuf<uint32_t> d_ut;
-    TRY(d_store.resize(cg * (n_iter ? n_iter : 1)));
-    TRY(d_trace.resize((size_t)C * (n_iter ? n_iter : 1)));
+    DSM_TRY(d_store.resize(cg * (n_iter ? n_iter : 1)));
+    DSM_TRY(d_trace.resize((size_t)C * (n_iter ? n_iter : 1)));
     if (u_eta_ext) {
-        TRY(d_ue.resize(cg * n_iter));
+        DSM_TRY(d_ue.resize(cg * n_iter));
         HIP_TRY(hipMemcpyAsync(d_ue, u_eta_ext, cg * n_iter * sizeof(double), hipMemcpyHostToDevice, st));
     }
     if (u_tau_ext && vg > 0) {
-        TRY(d_ut.resize((size_t)n_iter * G * 2 * vg));
+        DSM_TRY(d_ut.resize((size_t)n_iter * G * 2 * vg));
         HIP_TRY(hipMemcpyAsync(d_ut, u_tau_ext, (size_t)n_iter * G * 2 * vg * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         std::vector<int64_t> off((size_t)C * 2);
         for (int c = 0; c < C; ++c) {                      // test layout: [it][g][k][Vtot*G], gene rows in place
@@ -1236,17 +1227,17 @@ extern "C" int dsm_genes_update(dsm_genes *gs, int n_iter, int reset_star, int32
         HIP_TRY(hipMemcpyAsync(gs->u_off, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    if (reset_star) TRY(eval_genes(gs, 1));
+    if (reset_star) DSM_TRY(eval_genes(gs, 1));
     for (int it = 0; it < n_iter; ++it) {
         const uint32_t iter = gs->iter_ctr++;
         for (int g = 0; g < G; ++g) {
             const uint32_t *u = (u_tau_ext && vg > 0) ? d_ut.p + ((size_t)it * G + g) * 2 * vg : nullptr;
             const GeneSweepParams sp = sweep_params(gs, gs->eta, u, g, 0, gs->ntask, iter);
-            TRY(launch_sweep(gs, sp, true, 2));
+            DSM_TRY(launch_sweep(gs, sp, true, 2));
             GeneChooseParams cp = choose_params(gs, g, g == G - 1, 0, iter);
             if (u_eta_ext) cp.u_ext = d_ue.p + (size_t)it * cg;
             if (g == G - 1) { cp.eta_store = d_store.p + (size_t)it * cg; cp.gene_ll_trace = d_trace.p + (size_t)it * C; }
-            TRY(launch_choose(gs, cp));
+            DSM_TRY(launch_choose(gs, cp));
         }
     }
     if (eta_store && n_iter) HIP_TRY(hipMemcpyAsync(eta_store, d_store, cg * n_iter * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -1259,7 +1250,7 @@ extern "C" int dsm_genes_update(dsm_genes *gs, int n_iter, int reset_star, int32
 
 extern "C" int dsm_genes_get_star(dsm_genes *gs, int32_t *eta_star, double *gene_llstar)
 {
-    TRY(genes_need(gs, true, true));
+    DSM_TRY(genes_need(gs, true, true));
     GBIND(gs);
     hipStream_t st = gs->base->stream;
     if (eta_star) HIP_TRY(hipMemcpyAsync(eta_star, gs->eta_star, (size_t)gs->C * gs->G * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -1270,7 +1261,7 @@ extern "C" int dsm_genes_get_star(dsm_genes *gs, int32_t *eta_star, double *gene
 
 extern "C" int dsm_genes_set_star(dsm_genes *gs, const int32_t *eta_star, const double *gene_llstar)
 {
-    TRY(genes_need(gs, true, true));
+    DSM_TRY(genes_need(gs, true, true));
     GBIND(gs);
     hipStream_t st = gs->base->stream;
     if (eta_star) HIP_TRY(hipMemcpyAsync(gs->eta_star, eta_star, (size_t)gs->C * gs->G * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -1295,8 +1286,8 @@ extern "C" int dsm_kl_assign(int device, const double *cov, const double *delta,
     for (int c = 0; c < C; ++c) for (int g = 0; g < G; ++g) etaT[(size_t)g * C + c] = eta[(size_t)c * G + g];
     const int grid = (C + 255) / 256;
     DBuf<double> d_cov, d_delta, d_eta, d_part, d_ctl;
-    TRY(d_cov.resize(covT.size())); TRY(d_delta.resize(deltaT.size())); TRY(d_eta.resize(etaT.size()));
-    TRY(d_part.resize(grid)); TRY(d_ctl.resize(4));
+    DSM_TRY(d_cov.resize(covT.size())); DSM_TRY(d_delta.resize(deltaT.size())); DSM_TRY(d_eta.resize(etaT.size()));
+    DSM_TRY(d_part.resize(grid)); DSM_TRY(d_ctl.resize(4));
     hipStream_t st = nullptr;
     HIP_TRY(hipStreamCreate(&st));
     struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } guard{st};

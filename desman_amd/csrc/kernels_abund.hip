@@ -33,6 +33,7 @@
 
 #include "dsm_device.h"
 #include "dsm_host.h"
+#include "dsm_host_util.h"
 #include "log_table.h"
 
 #define DSM_ABUND_TILE 2048          // positions per LDS tile: 32 KB of counts + 16 KB of tau words
@@ -227,27 +228,8 @@ static int g_abund_chunk = 0;      // dsm_abund_debug_set_chunk: samples per lau
 
 extern "C" int dsm_abund_debug_set_chunk(int samples)
 {
-    if (samples < 0) { dsm_set_error("abund: chunk %d", samples); return DSM_ERR_ARG; }
-    g_abund_chunk = samples;
-    return DSM_OK;
+    return dsm_set_knob(&g_abund_chunk, samples, "abund", "chunk");
 }
-
-namespace {
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n)
-    {
-        hipError_t e = hipMalloc((void **)&p, (n ? n : 1) * sizeof(T));
-        if (e != hipSuccess) { p = nullptr; dsm_set_error("abund: hipMalloc(%zu B) failed: %s", n * sizeof(T), hipGetErrorString(e)); return DSM_ERR_NOMEM; }
-        return DSM_OK;
-    }
-    operator T *() const { return p; }
-};
-}  // namespace
-
-#define ABTRY(x) do { int _r = (x); if (_r != DSM_OK) return _r; } while (0)
 
 template <int GP, int NWMAX>
 static void abund_launch(const AbundParams &q, int n, int groups)
@@ -259,29 +241,18 @@ static int abund_check_model(int V, int G, const double *eta, int max_iter, doub
 {
     if (V < 1 || G < 1 || G > DSM_MAX_G) { dsm_set_error("fit_gamma: V=%d, G=%d (1 <= G <= DSM_MAX_G=%d)", V, G, DSM_MAX_G); return DSM_ERR_ARG; }
     if (max_iter < 0 || !(tol >= 0.0) || !std::isfinite(tol)) { dsm_set_error("fit_gamma: max_iter=%d, tol=%g", max_iter, tol); return DSM_ERR_ARG; }
-    for (int i = 0; i < 16; ++i)
-        if (!(eta[i] >= 0.0) || !std::isfinite(eta[i])) { dsm_set_error("fit_gamma: eta[%d] is negative or not finite", i); return DSM_ERR_ARG; }
-    return DSM_OK;
+    return dsm_check_eta("fit_gamma", eta);
 }
 
-// the count rules of dsm_ctx_set_counts: no negative count, no cell above 2^31 - 1 reads
-static int abund_check_counts(const int64_t *counts, int V, int S)
+// The tau of a call, host half (argument checks only: it runs before the device is touched).  tau digits [V][G] -> packed words,
+// DSM_ERR_ARG on a digit outside 0..3; tau null -- the context form `who` on the resident state, which must have G haplotypes -- leaves
+// `out` empty.
+static int abund_tau_words(const char *who, const dsm_ctx *c, const int64_t *tau, int V, int G, std::vector<uint64_t> &out)
 {
-    for (size_t i = 0; i < (size_t)V * S; ++i) {
-        int64_t tot = 0;
-        for (int b = 0; b < 4; ++b) {
-            const int64_t x = counts[i * 4 + b];
-            if (x < 0 || x > 2147483647ll) { dsm_set_error("fit_gamma: count %lld at position %zu, sample %zu", (long long)x, i / S, i % S); return DSM_ERR_ARG; }
-            tot += x;
-        }
-        if (tot > 2147483647ll) { dsm_set_error("fit_gamma: depth above 2^31-1 at position %zu, sample %zu", i / S, i % S); return DSM_ERR_ARG; }
+    if (!tau) {
+        if (!c->have_state || c->G != G) { dsm_set_error("%s: no tau given and no resident state of G=%d haplotypes", who, G); return DSM_ERR_STATE; }
+        return DSM_OK;
     }
-    return DSM_OK;
-}
-
-// tau digits [V][G] -> packed words; DSM_ERR_ARG on a digit outside 0..3
-static int abund_pack_tau(const int64_t *tau, int V, int G, std::vector<uint64_t> &out)
-{
     out.assign((size_t)V, 0ull);
     for (int v = 0; v < V; ++v) {
         uint64_t t = 0;
@@ -292,6 +263,16 @@ static int abund_pack_tau(const int64_t *tau, int V, int G, std::vector<uint64_t
         }
         out[(size_t)v] = t;
     }
+    return DSM_OK;
+}
+
+// ... device half, once the device is current: the words of abund_tau_words uploaded into `own`, or the context's resident tau
+static int abund_tau_on_device(const dsm_ctx *c, const std::vector<uint64_t> &words, DevBuf<uint64_t> &own, const uint64_t **d_tau)
+{
+    if (words.empty()) { *d_tau = c->tau; return DSM_OK; }
+    DSM_TRY(own.alloc(words.size()));
+    HIP_TRY(hipMemcpy(own, words.data(), words.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    *d_tau = own;
     return DSM_OK;
 }
 
@@ -333,16 +314,16 @@ static int abund_run(const int32_t *d_cnt, const int64_t *h_cnt, int V, int S, i
     const int groups = (F + NWMAX - 1) / NWMAX, NW = (F + groups - 1) / groups;
     const int NC = abund_chunk(V, S);
     DevBuf<int32_t> d_x, d_iters, d_conv; DevBuf<double> d_eta, d_ltab, d_gamma, d_ll, d_dev;
-    ABTRY(d_x.alloc((size_t)NC * V * 4)); ABTRY(d_eta.alloc(16)); ABTRY(d_ltab.alloc(2 * DSM_LOG_TAB_N));
-    ABTRY(d_gamma.alloc((size_t)NC * G)); ABTRY(d_ll.alloc((size_t)NC * F)); ABTRY(d_dev.alloc(NC));
-    ABTRY(d_iters.alloc(NC)); ABTRY(d_conv.alloc(NC));
+    DSM_TRY(d_x.alloc((size_t)NC * V * 4)); DSM_TRY(d_eta.alloc(16)); DSM_TRY(d_ltab.alloc(2 * DSM_LOG_TAB_N));
+    DSM_TRY(d_gamma.alloc((size_t)NC * G)); DSM_TRY(d_ll.alloc((size_t)NC * F)); DSM_TRY(d_dev.alloc(NC));
+    DSM_TRY(d_iters.alloc(NC)); DSM_TRY(d_conv.alloc(NC));
     HIP_TRY(hipMemcpy(d_eta, eta, 16 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_ltab, dsm_log_table_host, sizeof dsm_log_table_host, hipMemcpyHostToDevice));
+    DSM_TRY(dsm_upload_log_table(d_ltab));
     std::vector<int32_t> x32;
     std::vector<double> ll((size_t)NC * F);
     for (int s0 = 0; s0 < S; s0 += NC) {
         const int n = std::min(NC, S - s0);
-        ABTRY(abund_stage_chunk(d_cnt, h_cnt, V, S, s0, n, d_x, x32));
+        DSM_TRY(abund_stage_chunk(d_cnt, h_cnt, V, S, s0, n, d_x, x32));
         AbundParams q{d_x, d_tau, d_eta, d_ltab, V, G, F, NW, max_iter, tol, d_gamma, d_ll, d_dev, d_iters, d_conv};
         switch (GP) {
         case 4: abund_launch<4, 12>(q, n, groups); break;
@@ -370,15 +351,6 @@ static int abund_run(const int32_t *d_cnt, const int64_t *h_cnt, int V, int S, i
     return DSM_OK;
 }
 
-static int abund_bind_device(int device)
-{
-    const int nd = dsm_device_count();
-    if (nd <= 0) { dsm_set_error("no HIP device visible"); return DSM_ERR_NODEVICE; }
-    if (device < 0 || device >= nd) { dsm_set_error("device %d out of range (0..%d)", device, nd - 1); return DSM_ERR_ARG; }
-    HIP_TRY(hipSetDevice(device));
-    return DSM_OK;
-}
-
 extern "C" int dsm_fit_gamma(int device, const int64_t *counts, int V, int S, int G, const int64_t *tau, const double *eta,
                              int max_iter, double tol, int presence, double *gamma, double *loglik, double *deviance,
                              int32_t *iters, int32_t *converged, double *lr_absent)
@@ -387,39 +359,30 @@ extern "C" int dsm_fit_gamma(int device, const int64_t *counts, int V, int S, in
         dsm_set_error("fit_gamma: bad arguments");
         return DSM_ERR_ARG;
     }
-    ABTRY(abund_check_model(V, G, eta, max_iter, tol));
-    ABTRY(abund_check_counts(counts, V, S));
-    std::vector<uint64_t> packed;
-    ABTRY(abund_pack_tau(tau, V, G, packed));
+    DSM_TRY(abund_check_model(V, G, eta, max_iter, tol));
+    DSM_TRY(dsm_check_counts("fit_gamma", counts, (size_t)V, S));
+    std::vector<uint64_t> words;
+    DSM_TRY(abund_tau_words("fit_gamma", nullptr, tau, V, G, words));
     if (S == 0) return DSM_OK;
-    ABTRY(abund_bind_device(device));
-    DevBuf<uint64_t> d_tau;
-    ABTRY(d_tau.alloc((size_t)V));
-    HIP_TRY(hipMemcpy(d_tau, packed.data(), (size_t)V * sizeof(uint64_t), hipMemcpyHostToDevice));
+    DSM_TRY(dsm_bind_device(device));
+    DevBuf<uint64_t> own;
+    const uint64_t *d_tau = nullptr;
+    DSM_TRY(abund_tau_on_device(nullptr, words, own, &d_tau));
     return abund_run(nullptr, counts, V, S, G, d_tau, eta, max_iter, tol, presence, gamma, loglik, deviance, iters, converged, lr_absent);
 }
 
 extern "C" int dsm_ctx_fit_gamma(dsm_ctx *c, int G, const int64_t *tau, const double *eta, int max_iter, double tol, int presence,
                                  double *gamma, double *loglik, double *deviance, int32_t *iters, int32_t *converged, double *lr_absent)
 {
-    if (!c) { dsm_set_error("null context"); return DSM_ERR_ARG; }
-    if (!c->cnt_vs) { dsm_set_error("no count tensor: call dsm_ctx_set_counts first"); return DSM_ERR_STATE; }
+    DSM_TRY(dsm_ctx_enter(c, true));
     if (!eta || !gamma || !loglik || !deviance || !iters || !converged) { dsm_set_error("ctx_fit_gamma: null pointer"); return DSM_ERR_ARG; }
-    ABTRY(abund_check_model(c->V, G, eta, max_iter, tol));
-    if (!tau && (!c->have_state || c->G != G)) {
-        dsm_set_error("ctx_fit_gamma: no tau given and no resident state of G=%d haplotypes", G);
-        return DSM_ERR_STATE;
-    }
-    std::vector<uint64_t> packed;
-    if (tau) ABTRY(abund_pack_tau(tau, c->V, G, packed));
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));           // the resident tensors are read from the default stream below
-    DevBuf<uint64_t> d_tau;
-    if (tau) {
-        ABTRY(d_tau.alloc((size_t)c->V));
-        HIP_TRY(hipMemcpy(d_tau, packed.data(), (size_t)c->V * sizeof(uint64_t), hipMemcpyHostToDevice));
-    }
-    return abund_run(c->cnt_vs, nullptr, c->V, c->S, G, tau ? d_tau.p : c->tau, eta, max_iter, tol, presence, gamma, loglik, deviance,
+    DSM_TRY(abund_check_model(c->V, G, eta, max_iter, tol));
+    std::vector<uint64_t> words;
+    DSM_TRY(abund_tau_words("ctx_fit_gamma", c, tau, c->V, G, words));
+    DevBuf<uint64_t> own;
+    const uint64_t *d_tau = nullptr;
+    DSM_TRY(abund_tau_on_device(c, words, own, &d_tau));
+    return abund_run(c->cnt_vs, nullptr, c->V, c->S, G, d_tau, eta, max_iter, tol, presence, gamma, loglik, deviance,
                      iters, converged, lr_absent);
 }
 
@@ -635,15 +598,15 @@ static int abund_interval_run(const int32_t *d_cnt, const int64_t *h_cnt, int V,
     const int groups = (K + NWMAX - 1) / NWMAX, NW = (K + groups - 1) / groups;
     const int NC = abund_chunk(V, S);
     DevBuf<int32_t> d_x, d_fl; DevBuf<double> d_eta, d_ltab, d_ghat, d_res;
-    ABTRY(d_x.alloc((size_t)NC * V * 4)); ABTRY(d_eta.alloc(16)); ABTRY(d_ltab.alloc(2 * DSM_LOG_TAB_N));
-    ABTRY(d_ghat.alloc((size_t)NC * G)); ABTRY(d_res.alloc((size_t)NC * K)); ABTRY(d_fl.alloc((size_t)NC * K));
+    DSM_TRY(d_x.alloc((size_t)NC * V * 4)); DSM_TRY(d_eta.alloc(16)); DSM_TRY(d_ltab.alloc(2 * DSM_LOG_TAB_N));
+    DSM_TRY(d_ghat.alloc((size_t)NC * G)); DSM_TRY(d_res.alloc((size_t)NC * K)); DSM_TRY(d_fl.alloc((size_t)NC * K));
     HIP_TRY(hipMemcpy(d_eta, eta, 16 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_ltab, dsm_log_table_host, sizeof dsm_log_table_host, hipMemcpyHostToDevice));
+    DSM_TRY(dsm_upload_log_table(d_ltab));
     std::vector<int32_t> x32, fl((size_t)NC * K);
     std::vector<double> res((size_t)NC * K);
     for (int s0 = 0; s0 < S; s0 += NC) {
         const int n = std::min(NC, S - s0);
-        ABTRY(abund_stage_chunk(d_cnt, h_cnt, V, S, s0, n, d_x, x32));
+        DSM_TRY(abund_stage_chunk(d_cnt, h_cnt, V, S, s0, n, d_x, x32));
         HIP_TRY(hipMemcpy(d_ghat, gamma_hat + (size_t)s0 * G, (size_t)n * G * sizeof(double), hipMemcpyHostToDevice));
         AbundIvParams a{d_x, d_tau, d_eta, d_ltab, d_ghat, V, G, NW, max_iter, tol, ctol, q, d_res, d_fl};
         switch (GP) {
@@ -672,41 +635,32 @@ extern "C" int dsm_fit_gamma_interval(int device, const int64_t *counts, int V, 
         dsm_set_error("fit_gamma_interval: bad arguments");
         return DSM_ERR_ARG;
     }
-    ABTRY(abund_check_model(V, G, eta, max_iter, tol));
-    ABTRY(abund_check_counts(counts, V, S));
-    ABTRY(abund_check_interval(S, G, gamma_hat, q, ctol));
-    std::vector<uint64_t> packed;
-    ABTRY(abund_pack_tau(tau, V, G, packed));
+    DSM_TRY(abund_check_model(V, G, eta, max_iter, tol));
+    DSM_TRY(dsm_check_counts("fit_gamma", counts, (size_t)V, S));
+    DSM_TRY(abund_check_interval(S, G, gamma_hat, q, ctol));
+    std::vector<uint64_t> words;
+    DSM_TRY(abund_tau_words("fit_gamma_interval", nullptr, tau, V, G, words));
     if (S == 0) return DSM_OK;
-    ABTRY(abund_bind_device(device));
-    DevBuf<uint64_t> d_tau;
-    ABTRY(d_tau.alloc((size_t)V));
-    HIP_TRY(hipMemcpy(d_tau, packed.data(), (size_t)V * sizeof(uint64_t), hipMemcpyHostToDevice));
+    DSM_TRY(dsm_bind_device(device));
+    DevBuf<uint64_t> own;
+    const uint64_t *d_tau = nullptr;
+    DSM_TRY(abund_tau_on_device(nullptr, words, own, &d_tau));
     return abund_interval_run(nullptr, counts, V, S, G, d_tau, eta, gamma_hat, q, max_iter, tol, ctol, lo, hi, flags);
 }
 
 extern "C" int dsm_ctx_fit_gamma_interval(dsm_ctx *c, int G, const int64_t *tau, const double *eta, const double *gamma_hat, double q,
                                           int max_iter, double tol, double ctol, double *lo, double *hi, int32_t *flags)
 {
-    if (!c) { dsm_set_error("null context"); return DSM_ERR_ARG; }
-    if (!c->cnt_vs) { dsm_set_error("no count tensor: call dsm_ctx_set_counts first"); return DSM_ERR_STATE; }
+    DSM_TRY(dsm_ctx_enter(c, true));
     if (!eta || !gamma_hat || !lo || !hi || !flags) { dsm_set_error("ctx_fit_gamma_interval: null pointer"); return DSM_ERR_ARG; }
-    ABTRY(abund_check_model(c->V, G, eta, max_iter, tol));
-    ABTRY(abund_check_interval(c->S, G, gamma_hat, q, ctol));
-    if (!tau && (!c->have_state || c->G != G)) {
-        dsm_set_error("ctx_fit_gamma_interval: no tau given and no resident state of G=%d haplotypes", G);
-        return DSM_ERR_STATE;
-    }
-    std::vector<uint64_t> packed;
-    if (tau) ABTRY(abund_pack_tau(tau, c->V, G, packed));
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));           // the resident tensors are read from the default stream below
-    DevBuf<uint64_t> d_tau;
-    if (tau) {
-        ABTRY(d_tau.alloc((size_t)c->V));
-        HIP_TRY(hipMemcpy(d_tau, packed.data(), (size_t)c->V * sizeof(uint64_t), hipMemcpyHostToDevice));
-    }
-    return abund_interval_run(c->cnt_vs, nullptr, c->V, c->S, G, tau ? d_tau.p : c->tau, eta, gamma_hat, q, max_iter, tol, ctol, lo, hi, flags);
+    DSM_TRY(abund_check_model(c->V, G, eta, max_iter, tol));
+    DSM_TRY(abund_check_interval(c->S, G, gamma_hat, q, ctol));
+    std::vector<uint64_t> words;
+    DSM_TRY(abund_tau_words("ctx_fit_gamma_interval", c, tau, c->V, G, words));
+    DevBuf<uint64_t> own;
+    const uint64_t *d_tau = nullptr;
+    DSM_TRY(abund_tau_on_device(c, words, own, &d_tau));
+    return abund_interval_run(c->cnt_vs, nullptr, c->V, c->S, G, d_tau, eta, gamma_hat, q, max_iter, tol, ctol, lo, hi, flags);
 }
 
 // ---------------------------------------------------------------- the error matrix of new samples, fitted with gamma
@@ -885,9 +839,7 @@ static size_t g_abund_eta_stage_max = 0;     // dsm_abund_debug_set_eta_stage_ma
 
 extern "C" int dsm_abund_debug_set_eta_batch(int steps)
 {
-    if (steps < 0) { dsm_set_error("abund: eta batch %d", steps); return DSM_ERR_ARG; }
-    g_abund_eta_batch = steps;
-    return DSM_OK;
+    return dsm_set_knob(&g_abund_eta_batch, steps, "abund", "eta batch");
 }
 
 extern "C" int dsm_abund_debug_set_eta_stage_max(long long bytes)
@@ -939,22 +891,22 @@ static int abund_eta_run(const int32_t *d_cnt, const int64_t *h_cnt, int V, int 
     {
         std::vector<double> g0((size_t)S * G), dev0((size_t)S);
         std::vector<int32_t> it0((size_t)S), cv0((size_t)S);
-        ABTRY(abund_run(d_cnt, h_cnt, V, S, G, d_tau, eta0, max_iter, tol, 0, g0.data(), loglik0, dev0.data(), it0.data(), cv0.data(), nullptr));
+        DSM_TRY(abund_run(d_cnt, h_cnt, V, S, G, d_tau, eta0, max_iter, tol, 0, g0.data(), loglik0, dev0.data(), it0.data(), cv0.data(), nullptr));
     }
     const int GP = G <= 4 ? 4 : G <= 8 ? 8 : G <= 16 ? 16 : 32;
     DevBuf<int32_t> d_x, d_bad, d_ctrl; DevBuf<double> d_eta, d_ltab, d_gamma, d_N, d_Lsat, d_ll, d_part, d_delta;
-    ABTRY(d_x.alloc((size_t)S * V * 4)); ABTRY(d_bad.alloc(S)); ABTRY(d_ctrl.alloc(AE_NCTRL)); ABTRY(d_eta.alloc(16));
-    ABTRY(d_ltab.alloc(2 * DSM_LOG_TAB_N)); ABTRY(d_gamma.alloc((size_t)S * G)); ABTRY(d_N.alloc(S)); ABTRY(d_Lsat.alloc(S));
-    ABTRY(d_ll.alloc(S)); ABTRY(d_part.alloc((size_t)S * 16)); ABTRY(d_delta.alloc(S));
+    DSM_TRY(d_x.alloc((size_t)S * V * 4)); DSM_TRY(d_bad.alloc(S)); DSM_TRY(d_ctrl.alloc(AE_NCTRL)); DSM_TRY(d_eta.alloc(16));
+    DSM_TRY(d_ltab.alloc(2 * DSM_LOG_TAB_N)); DSM_TRY(d_gamma.alloc((size_t)S * G)); DSM_TRY(d_N.alloc(S)); DSM_TRY(d_Lsat.alloc(S));
+    DSM_TRY(d_ll.alloc(S)); DSM_TRY(d_part.alloc((size_t)S * 16)); DSM_TRY(d_delta.alloc(S));
     HIP_TRY(hipMemcpy(d_eta, eta0, 16 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_ltab, dsm_log_table_host, sizeof dsm_log_table_host, hipMemcpyHostToDevice));
+    DSM_TRY(dsm_upload_log_table(d_ltab));
     int32_t ctrl[AE_NCTRL] = {0};
     ctrl[AE_STOP] = max_iter == 0 ? 1 : 0;
     HIP_TRY(hipMemcpy(d_ctrl, ctrl, sizeof ctrl, hipMemcpyHostToDevice));
     std::vector<int32_t> x32;
     for (int s0 = 0; s0 < S; s0 += 1 << 15) {              // (the repack kernel's grid holds 65535 samples at the most)
         const int n = std::min(1 << 15, S - s0);
-        ABTRY(abund_stage_chunk(d_cnt, h_cnt, V, S, s0, n, d_x.p + (size_t)s0 * V * 4, x32));
+        DSM_TRY(abund_stage_chunk(d_cnt, h_cnt, V, S, s0, n, d_x.p + (size_t)s0 * V * 4, x32));
     }
     std::vector<int32_t>().swap(x32);
     AbundEtaParams q{d_x, d_tau, d_ltab, V, G, S, max_iter, tol, d_gamma, d_eta, d_N, d_Lsat, d_ll, d_part, d_delta, d_bad, d_ctrl};
@@ -1007,15 +959,15 @@ extern "C" int dsm_fit_gamma_eta(int device, const int64_t *counts, int V, int S
         dsm_set_error("fit_gamma_eta: bad arguments");
         return DSM_ERR_ARG;
     }
-    ABTRY(abund_check_model(V, G, eta0, max_iter, tol));
-    ABTRY(abund_eta_check(V, S, eta0));
-    ABTRY(abund_check_counts(counts, V, S));
-    std::vector<uint64_t> packed;
-    ABTRY(abund_pack_tau(tau, V, G, packed));
-    ABTRY(abund_bind_device(device));
-    DevBuf<uint64_t> d_tau;
-    ABTRY(d_tau.alloc((size_t)V));
-    HIP_TRY(hipMemcpy(d_tau, packed.data(), (size_t)V * sizeof(uint64_t), hipMemcpyHostToDevice));
+    DSM_TRY(abund_check_model(V, G, eta0, max_iter, tol));
+    DSM_TRY(abund_eta_check(V, S, eta0));
+    DSM_TRY(dsm_check_counts("fit_gamma", counts, (size_t)V, S));
+    std::vector<uint64_t> words;
+    DSM_TRY(abund_tau_words("fit_gamma_eta", nullptr, tau, V, G, words));
+    DSM_TRY(dsm_bind_device(device));
+    DevBuf<uint64_t> own;
+    const uint64_t *d_tau = nullptr;
+    DSM_TRY(abund_tau_on_device(nullptr, words, own, &d_tau));
     return abund_eta_run(nullptr, counts, V, S, G, d_tau, eta0, max_iter, tol, gamma, eta, loglik, loglik0, deviance, iters, converged,
                          dead_rows, lr_eta);
 }
@@ -1024,27 +976,18 @@ extern "C" int dsm_ctx_fit_gamma_eta(dsm_ctx *c, int G, const int64_t *tau, cons
                                      double *eta, double *loglik, double *loglik0, double *deviance, int32_t *iters, int32_t *converged,
                                      int32_t *dead_rows, double *lr_eta)
 {
-    if (!c) { dsm_set_error("null context"); return DSM_ERR_ARG; }
-    if (!c->cnt_vs) { dsm_set_error("no count tensor: call dsm_ctx_set_counts first"); return DSM_ERR_STATE; }
+    DSM_TRY(dsm_ctx_enter(c, true));
     if (!eta0 || !gamma || !eta || !loglik || !loglik0 || !deviance || !iters || !converged || !dead_rows || !lr_eta) {
         dsm_set_error("ctx_fit_gamma_eta: null pointer");
         return DSM_ERR_ARG;
     }
-    ABTRY(abund_check_model(c->V, G, eta0, max_iter, tol));
-    ABTRY(abund_eta_check(c->V, c->S, eta0));
-    if (!tau && (!c->have_state || c->G != G)) {
-        dsm_set_error("ctx_fit_gamma_eta: no tau given and no resident state of G=%d haplotypes", G);
-        return DSM_ERR_STATE;
-    }
-    std::vector<uint64_t> packed;
-    if (tau) ABTRY(abund_pack_tau(tau, c->V, G, packed));
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));           // the resident tensors are read from the default stream below
-    DevBuf<uint64_t> d_tau;
-    if (tau) {
-        ABTRY(d_tau.alloc((size_t)c->V));
-        HIP_TRY(hipMemcpy(d_tau, packed.data(), (size_t)c->V * sizeof(uint64_t), hipMemcpyHostToDevice));
-    }
-    return abund_eta_run(c->cnt_vs, nullptr, c->V, c->S, G, tau ? d_tau.p : c->tau, eta0, max_iter, tol, gamma, eta, loglik, loglik0,
+    DSM_TRY(abund_check_model(c->V, G, eta0, max_iter, tol));
+    DSM_TRY(abund_eta_check(c->V, c->S, eta0));
+    std::vector<uint64_t> words;
+    DSM_TRY(abund_tau_words("ctx_fit_gamma_eta", c, tau, c->V, G, words));
+    DevBuf<uint64_t> own;
+    const uint64_t *d_tau = nullptr;
+    DSM_TRY(abund_tau_on_device(c, words, own, &d_tau));
+    return abund_eta_run(c->cnt_vs, nullptr, c->V, c->S, G, d_tau, eta0, max_iter, tol, gamma, eta, loglik, loglik0,
                          deviance, iters, converged, dead_rows, lr_eta);
 }

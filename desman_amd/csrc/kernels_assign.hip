@@ -33,6 +33,7 @@
 
 #include "dsm_device.h"
 #include "dsm_host.h"
+#include "dsm_host_util.h"
 #include "log_table.h"
 
 #define DSM_STREAM_ASGN 0x4153474Eu   // 'ASGN'  the posterior draw of dsm_assign_tau
@@ -48,13 +49,6 @@ struct AssignParams {
     const double *dr;           // draw: target inside that partial, in units of exp(-max of the partial)
     uint32_t *didx;             // draw: the state
 };
-
-__device__ __forceinline__ double wave_max_f64(double x)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x = fmax(x, __shfl_xor(x, off, 64));
-    return x;
-}
 
 static size_t assign_lds_bytes(int S, int G)
 {
@@ -293,27 +287,8 @@ static int g_assign_chunk = 0;      // dsm_assign_debug_set_chunk: positions per
 
 extern "C" int dsm_assign_debug_set_chunk(int positions)
 {
-    if (positions < 0) { dsm_set_error("assign: chunk %d", positions); return DSM_ERR_ARG; }
-    g_assign_chunk = positions;
-    return DSM_OK;
+    return dsm_set_knob(&g_assign_chunk, positions, "assign", "chunk");
 }
-
-namespace {
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n)
-    {
-        hipError_t e = hipMalloc((void **)&p, (n ? n : 1) * sizeof(T));
-        if (e != hipSuccess) { p = nullptr; dsm_set_error("assign: hipMalloc(%zu B) failed: %s", n * sizeof(T), hipGetErrorString(e)); return DSM_ERR_NOMEM; }
-        return DSM_OK;
-    }
-    operator T *() const { return p; }
-};
-}  // namespace
-
-#define ATRY(x) do { int _r = (x); if (_r != DSM_OK) return _r; } while (0)
 
 static int assign_check_model(int S, int G, const double *gamma, const double *eta)
 {
@@ -323,37 +298,32 @@ static int assign_check_model(int S, int G, const double *gamma, const double *e
         dsm_set_error("assign: G=%d exceeds DSM_ASSIGN_MAX_G=%d (all 4^G joint states are evaluated)", G, DSM_ASSIGN_MAX_G);
         return DSM_ERR_UNSUPPORTED;
     }
-    for (size_t i = 0; i < (size_t)S * G; ++i)
-        if (!(gamma[i] >= 0.0) || !std::isfinite(gamma[i])) { dsm_set_error("assign: gamma[%zu] is negative or not finite", i); return DSM_ERR_ARG; }
-    for (int i = 0; i < 16; ++i)
-        if (!(eta[i] >= 0.0) || !std::isfinite(eta[i])) { dsm_set_error("assign: eta[%d] is negative or not finite", i); return DSM_ERR_ARG; }
-    return DSM_OK;
+    DSM_TRY(dsm_check_gamma("assign", gamma, (size_t)S * G));
+    return dsm_check_eta("assign", eta);
 }
 
 // d_cnt: the whole tensor on the device (context form), or null with h_cnt = the caller's int64 tensor (uploaded chunk by chunk)
 static int assign_run(const int32_t *d_cnt, const int64_t *h_cnt, int N, int S, int G, const double *gamma, const double *eta,
                       uint64_t seed, uint8_t *map_state, double *conf, double *logz, double *marg, uint8_t *draw_state)
 {
-    const int GO = G > 3 ? G - 3 : 0, NB = 1 << (2 * GO), P = std::min(NB, 64), bpp = NB / P, R = 4 + 4 * G;
+    const JointSplit js(G);
+    const int P = js.P, bpp = js.bpp, R = 4 + 4 * G;
     // positions per launch: the scratch rows stay below 32 MB whatever N is
     int NC = (int)std::max<size_t>(1, std::min<size_t>((size_t)1 << 16, ((size_t)32 << 20) / ((size_t)P * R * sizeof(double))));
     if (g_assign_chunk > 0) NC = g_assign_chunk;
     NC = std::min(NC, N);
     const size_t lds = assign_lds_bytes(S, G);
-    if (lds > 160 * 1024) { dsm_set_error("assign: %zu B of LDS", lds); return DSM_ERR_UNSUPPORTED; }
-    if (lds > 48 * 1024) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&assign_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&assign_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
+    DSM_TRY(dsm_allow_lds(reinterpret_cast<const void *>(&assign_kernel<0>), lds, "assign"));
+    DSM_TRY(dsm_allow_lds(reinterpret_cast<const void *>(&assign_kernel<1>), lds, "assign"));
     DevBuf<int32_t> d_x; DevBuf<double> d_gamma, d_eta, d_ltab, d_part, d_conf, d_logz, d_marg, d_dr;
     DevBuf<uint32_t> d_map, d_didx; DevBuf<int> d_dj;
-    if (!d_cnt) ATRY(d_x.alloc((size_t)NC * S * 4));
-    ATRY(d_gamma.alloc((size_t)S * G)); ATRY(d_eta.alloc(16)); ATRY(d_ltab.alloc(2 * DSM_LOG_TAB_N));
-    ATRY(d_part.alloc((size_t)NC * P * R)); ATRY(d_conf.alloc(NC)); ATRY(d_logz.alloc(NC)); ATRY(d_marg.alloc((size_t)NC * 4 * G));
-    ATRY(d_map.alloc(NC)); ATRY(d_dj.alloc(NC)); ATRY(d_dr.alloc(NC)); ATRY(d_didx.alloc(NC));
+    if (!d_cnt) DSM_TRY(d_x.alloc((size_t)NC * S * 4));
+    DSM_TRY(d_gamma.alloc((size_t)S * G)); DSM_TRY(d_eta.alloc(16)); DSM_TRY(d_ltab.alloc(2 * DSM_LOG_TAB_N));
+    DSM_TRY(d_part.alloc((size_t)NC * P * R)); DSM_TRY(d_conf.alloc(NC)); DSM_TRY(d_logz.alloc(NC)); DSM_TRY(d_marg.alloc((size_t)NC * 4 * G));
+    DSM_TRY(d_map.alloc(NC)); DSM_TRY(d_dj.alloc(NC)); DSM_TRY(d_dr.alloc(NC)); DSM_TRY(d_didx.alloc(NC));
     HIP_TRY(hipMemcpy(d_gamma, gamma, (size_t)S * G * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_eta, eta, 16 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_ltab, dsm_log_table_host, sizeof dsm_log_table_host, hipMemcpyHostToDevice));
+    DSM_TRY(dsm_upload_log_table(d_ltab));
     std::vector<int32_t> x32;
     std::vector<uint32_t> idx((size_t)NC);
     auto unpack = [&](uint8_t *dst, int n0, int n) {
@@ -363,12 +333,7 @@ static int assign_run(const int32_t *d_cnt, const int64_t *h_cnt, int N, int S, 
     for (int n0 = 0; n0 < N; n0 += NC) {
         const int n = std::min(NC, N - n0);
         const int32_t *cnt = d_cnt ? d_cnt + (size_t)n0 * S * 4 : d_x.p;
-        if (!d_cnt) {
-            x32.resize((size_t)n * S * 4);
-            const int64_t *src = h_cnt + (size_t)n0 * S * 4;
-            for (size_t i = 0; i < x32.size(); ++i) x32[i] = (int32_t)src[i];
-            HIP_TRY(hipMemcpy(d_x, x32.data(), x32.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
+        if (!d_cnt) DSM_TRY(dsm_stage_counts(h_cnt + (size_t)n0 * S * 4, (size_t)n * S * 4, d_x, x32, nullptr));
         AssignParams q{cnt, d_gamma, d_eta, d_ltab, n, S, G, P, bpp, d_part, d_dj, d_dr, d_didx};
         hipLaunchKernelGGL(assign_kernel<0>, dim3((unsigned)n * (unsigned)P), dim3(64), lds, 0, q);
         HIP_TRY(hipGetLastError());
@@ -392,15 +357,6 @@ static int assign_run(const int32_t *d_cnt, const int64_t *h_cnt, int N, int S, 
     return DSM_OK;
 }
 
-static int assign_bind_device(int device)
-{
-    const int nd = dsm_device_count();
-    if (nd <= 0) { dsm_set_error("no HIP device visible"); return DSM_ERR_NODEVICE; }
-    if (device < 0 || device >= nd) { dsm_set_error("device %d out of range (0..%d)", device, nd - 1); return DSM_ERR_ARG; }
-    HIP_TRY(hipSetDevice(device));
-    return DSM_OK;
-}
-
 extern "C" int dsm_assign_tau(int device, const int64_t *counts, int N, int S, int G, const double *gamma, const double *eta,
                               uint64_t seed, uint8_t *map_state, double *conf, double *logz, double *marg, uint8_t *draw_state)
 {
@@ -408,30 +364,18 @@ extern "C" int dsm_assign_tau(int device, const int64_t *counts, int N, int S, i
         dsm_set_error("assign_tau: bad arguments");
         return DSM_ERR_ARG;
     }
-    ATRY(assign_check_model(S, G, gamma, eta));
-    // the count rules of dsm_ctx_set_counts: no negative count, no cell above 2^31 - 1 reads
-    for (size_t i = 0; i < (size_t)N * S; ++i) {
-        int64_t tot = 0;
-        for (int b = 0; b < 4; ++b) {
-            const int64_t x = counts[i * 4 + b];
-            if (x < 0 || x > 2147483647ll) { dsm_set_error("assign_tau: count %lld at position %zu, sample %zu", (long long)x, i / S, i % S); return DSM_ERR_ARG; }
-            tot += x;
-        }
-        if (tot > 2147483647ll) { dsm_set_error("assign_tau: depth above 2^31-1 at position %zu, sample %zu", i / S, i % S); return DSM_ERR_ARG; }
-    }
+    DSM_TRY(assign_check_model(S, G, gamma, eta));
+    DSM_TRY(dsm_check_counts("assign_tau", counts, (size_t)N, S));
     if (N == 0) return DSM_OK;
-    ATRY(assign_bind_device(device));
+    DSM_TRY(dsm_bind_device(device));
     return assign_run(nullptr, counts, N, S, G, gamma, eta, seed, map_state, conf, logz, marg, draw_state);
 }
 
 extern "C" int dsm_ctx_assign_tau(dsm_ctx *c, const double *gamma, const double *eta, int G, uint64_t seed, uint8_t *map_state,
                                   double *conf, double *logz, double *marg, uint8_t *draw_state)
 {
-    if (!c) { dsm_set_error("null context"); return DSM_ERR_ARG; }
-    if (!c->cnt_vs) { dsm_set_error("no count tensor: call dsm_ctx_set_counts first"); return DSM_ERR_STATE; }
+    DSM_TRY(dsm_ctx_enter(c, true));
     if (!gamma || !eta || !map_state || !conf || !logz || !marg) { dsm_set_error("ctx_assign_tau: null pointer"); return DSM_ERR_ARG; }
-    ATRY(assign_check_model(c->S, G, gamma, eta));
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));           // the resident tensor is read from the default stream below
+    DSM_TRY(assign_check_model(c->S, G, gamma, eta));
     return assign_run(c->cnt_vs, nullptr, c->V, c->S, G, gamma, eta, seed, map_state, conf, logz, marg, draw_state);
 }

@@ -54,6 +54,7 @@
 
 #include "dsm_device.h"
 #include "dsm_host.h"
+#include "dsm_host_util.h"
 #include "log_table.h"
 
 #define ASMP_LDS_GAMMA 4096         // doubles of LDS a chunk of gamma columns may take (32 KiB)
@@ -387,29 +388,12 @@ static int g_asmp_chunk = 0;        // dsm_assign_sampled_debug_set_chunk: posit
 
 extern "C" int dsm_assign_sampled_debug_set_chunk(int positions)
 {
-    if (positions < 0) { dsm_set_error("assign_sampled: chunk %d", positions); return DSM_ERR_ARG; }
-    g_asmp_chunk = positions;
-    return DSM_OK;
+    return dsm_set_knob(&g_asmp_chunk, positions, "assign_sampled", "chunk");
 }
 
 namespace {
 struct SampledPlan { int inst, lpv, lpv_log2, nsl, gc, ppw; size_t lds; };
-
-template <typename T>
-struct SBuf {
-    T *p = nullptr;
-    ~SBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n)
-    {
-        hipError_t e = hipMalloc((void **)&p, (n ? n : 1) * sizeof(T));
-        if (e != hipSuccess) { p = nullptr; dsm_set_error("assign_sampled: hipMalloc(%zu B) failed: %s", n * sizeof(T), hipGetErrorString(e)); return DSM_ERR_NOMEM; }
-        return DSM_OK;
-    }
-    operator T *() const { return p; }
-};
 }  // namespace
-
-#define STRY(x) do { int _r = (x); if (_r != DSM_OK) return _r; } while (0)
 
 static int asmp_plan(int S, int G, SampledPlan *pl)
 {
@@ -438,7 +422,7 @@ extern "C" int dsm_assign_sampled_debug_path(int S, int G, int *out)
 {
     if (!out) { dsm_set_error("assign_sampled_debug_path: null pointer"); return DSM_ERR_ARG; }
     SampledPlan pl;
-    STRY(asmp_plan(S, G, &pl));
+    DSM_TRY(asmp_plan(S, G, &pl));
     out[0] = pl.inst; out[1] = pl.lpv; out[2] = pl.nsl; out[3] = pl.gc; out[4] = pl.ppw;
     return DSM_OK;
 }
@@ -446,7 +430,7 @@ extern "C" int dsm_assign_sampled_debug_path(int S, int G, int *out)
 static int asmp_check_model(int S, int G, const double *gamma, const double *eta, long long burn, long long kept, long long pair_every)
 {
     SampledPlan pl;
-    STRY(asmp_plan(S, G, &pl));
+    DSM_TRY(asmp_plan(S, G, &pl));
     if (kept < 1 || burn < 0) { dsm_set_error("assign_sampled: burn=%lld, kept=%lld", burn, kept); return DSM_ERR_ARG; }
     if (pair_every < 0) { dsm_set_error("assign_sampled: pair_every=%lld", pair_every); return DSM_ERR_ARG; }
     if (pair_every > ASMP_MAX_SWEEPS) {
@@ -457,18 +441,15 @@ static int asmp_check_model(int S, int G, const double *gamma, const double *eta
         dsm_set_error("assign_sampled: burn + kept = %lld exceeds %d sweeps", burn + kept, ASMP_MAX_SWEEPS);
         return DSM_ERR_UNSUPPORTED;
     }
-    for (size_t i = 0; i < (size_t)S * G; ++i)
-        if (!(gamma[i] >= 0.0) || !std::isfinite(gamma[i])) { dsm_set_error("assign_sampled: gamma[%zu] is negative or not finite", i); return DSM_ERR_ARG; }
-    for (int i = 0; i < 16; ++i)
-        if (!(eta[i] >= 0.0) || !std::isfinite(eta[i])) { dsm_set_error("assign_sampled: eta[%d] is negative or not finite", i); return DSM_ERR_ARG; }
-    return DSM_OK;
+    DSM_TRY(dsm_check_gamma("assign_sampled", gamma, (size_t)S * G));
+    return dsm_check_eta("assign_sampled", eta);
 }
 
 template <int NSL, bool ONE, bool PAIRS>
 static int asmp_launch_as(const SampledPlan &pl, const SampledParams &q)
 {
     const void *fn = reinterpret_cast<const void *>(&assign_sampled_kernel<NSL, ONE, PAIRS>);
-    if (pl.lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+    DSM_TRY(dsm_allow_lds(fn, pl.lds, "assign_sampled"));      // (asmp_plan keeps the tile below 64 KB: only the upper half of the gate can act)
     const unsigned blocks = (unsigned)((q.N + pl.ppw - 1) / pl.ppw), threads = (unsigned)(pl.ppw * 4 * pl.lpv);
     hipLaunchKernelGGL((assign_sampled_kernel<NSL, ONE, PAIRS>), dim3(blocks), dim3(threads), pl.lds, 0, q);
     HIP_TRY(hipGetLastError());
@@ -487,8 +468,7 @@ static int asmp_run(const int32_t *d_cnt, const int64_t *h_cnt, int N, int S, in
                     uint8_t *draw_state)
 {
     SampledPlan pl;
-    STRY(asmp_plan(S, G, &pl));
-    if (pl.lds > 160 * 1024) { dsm_set_error("assign_sampled: %zu B of LDS", pl.lds); return DSM_ERR_UNSUPPORTED; }
+    DSM_TRY(asmp_plan(S, G, &pl));
     // positions per launch: everything sized by it -- the kept states, the uploaded counts, the outputs -- stays below 32 MB together
     // whatever N, S, G and T are
     const size_t per_pos = (size_t)4 * kept * sizeof(uint64_t) + (d_cnt ? 0 : (size_t)S * 4 * sizeof(int32_t)) + (size_t)4 * G * sizeof(double) +
@@ -496,15 +476,15 @@ static int asmp_run(const int32_t *d_cnt, const int64_t *h_cnt, int N, int S, in
     int NC = (int)std::max<size_t>(1, std::min<size_t>((size_t)1 << 16, ((size_t)32 << 20) / per_pos));
     if (g_asmp_chunk > 0) NC = g_asmp_chunk;
     NC = std::min(NC, N);
-    SBuf<int32_t> d_x; SBuf<double> d_gamma, d_eta, d_ltab, d_ll, d_conf, d_marg, d_spread;
-    SBuf<uint64_t> d_kept, d_map, d_draw;
-    if (!d_cnt) STRY(d_x.alloc((size_t)NC * S * 4));
-    STRY(d_gamma.alloc((size_t)S * G)); STRY(d_eta.alloc(16)); STRY(d_ltab.alloc(2 * DSM_LOG_TAB_N));
-    STRY(d_kept.alloc((size_t)NC * 4 * kept)); STRY(d_map.alloc(NC)); STRY(d_draw.alloc(NC));
-    STRY(d_ll.alloc(NC)); STRY(d_conf.alloc(NC)); STRY(d_marg.alloc((size_t)NC * 4 * G)); STRY(d_spread.alloc(NC));
+    DevBuf<int32_t> d_x; DevBuf<double> d_gamma, d_eta, d_ltab, d_ll, d_conf, d_marg, d_spread;
+    DevBuf<uint64_t> d_kept, d_map, d_draw;
+    if (!d_cnt) DSM_TRY(d_x.alloc((size_t)NC * S * 4));
+    DSM_TRY(d_gamma.alloc((size_t)S * G)); DSM_TRY(d_eta.alloc(16)); DSM_TRY(d_ltab.alloc(2 * DSM_LOG_TAB_N));
+    DSM_TRY(d_kept.alloc((size_t)NC * 4 * kept)); DSM_TRY(d_map.alloc(NC)); DSM_TRY(d_draw.alloc(NC));
+    DSM_TRY(d_ll.alloc(NC)); DSM_TRY(d_conf.alloc(NC)); DSM_TRY(d_marg.alloc((size_t)NC * 4 * G)); DSM_TRY(d_spread.alloc(NC));
     HIP_TRY(hipMemcpy(d_gamma, gamma, (size_t)S * G * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_eta, eta, 16 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_ltab, dsm_log_table_host, sizeof dsm_log_table_host, hipMemcpyHostToDevice));
+    DSM_TRY(dsm_upload_log_table(d_ltab));
     std::vector<int32_t> x32;
     std::vector<uint64_t> word((size_t)NC);
     auto unpack = [&](uint8_t *dst, int n0, int n) {
@@ -514,26 +494,21 @@ static int asmp_run(const int32_t *d_cnt, const int64_t *h_cnt, int N, int S, in
     for (int n0 = 0; n0 < N; n0 += NC) {
         const int n = std::min(NC, N - n0);
         const int32_t *cnt = d_cnt ? d_cnt + (size_t)n0 * S * 4 : d_x.p;
-        if (!d_cnt) {
-            x32.resize((size_t)n * S * 4);
-            const int64_t *src = h_cnt + (size_t)n0 * S * 4;
-            for (size_t i = 0; i < x32.size(); ++i) x32[i] = (int32_t)src[i];
-            HIP_TRY(hipMemcpy(d_x, x32.data(), x32.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
+        if (!d_cnt) DSM_TRY(dsm_stage_counts(h_cnt + (size_t)n0 * S * 4, (size_t)n * S * 4, d_x, x32, nullptr));
         SampledParams q;
         q.cnt = cnt; q.gamma = d_gamma; q.eta = d_eta; q.log_tab = d_ltab;
         q.N = n; q.S = S; q.G = G; q.lpv_log2 = pl.lpv_log2; q.gc = pl.gc; q.ppw = pl.ppw; q.B = burn; q.T = kept; q.E = pair_every;
         q.k0 = (uint32_t)seed; q.k1 = (uint32_t)(seed >> 32); q.pos0 = (unsigned long long)n0;
         q.kept = d_kept; q.map_state = d_map; q.draw_state = d_draw; q.map_ll = d_ll; q.conf = d_conf; q.marg = d_marg; q.spread = d_spread;
         switch (pl.inst) {
-        case 0: STRY((asmp_launch<1, true>(pl, q))); break;
-        case 1: STRY((asmp_launch<1, false>(pl, q))); break;
-        case 2: STRY((asmp_launch<2, true>(pl, q))); break;
-        case 3: STRY((asmp_launch<2, false>(pl, q))); break;
-        case 4: STRY((asmp_launch<4, true>(pl, q))); break;
-        case 5: STRY((asmp_launch<4, false>(pl, q))); break;
-        case 6: STRY((asmp_launch<8, true>(pl, q))); break;
-        default: STRY((asmp_launch<8, false>(pl, q))); break;
+        case 0: DSM_TRY((asmp_launch<1, true>(pl, q))); break;
+        case 1: DSM_TRY((asmp_launch<1, false>(pl, q))); break;
+        case 2: DSM_TRY((asmp_launch<2, true>(pl, q))); break;
+        case 3: DSM_TRY((asmp_launch<2, false>(pl, q))); break;
+        case 4: DSM_TRY((asmp_launch<4, true>(pl, q))); break;
+        case 5: DSM_TRY((asmp_launch<4, false>(pl, q))); break;
+        case 6: DSM_TRY((asmp_launch<8, true>(pl, q))); break;
+        default: DSM_TRY((asmp_launch<8, false>(pl, q))); break;
         }
         HIP_TRY(hipMemcpy(word.data(), d_map, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
         unpack(map_state, n0, n);
@@ -557,22 +532,10 @@ extern "C" int dsm_assign_tau_sampled_pairs(int device, const int64_t *counts, i
         dsm_set_error("assign_tau_sampled: bad arguments");
         return DSM_ERR_ARG;
     }
-    STRY(asmp_check_model(S, G, gamma, eta, burn, kept, pair_every));
-    // the count rules of dsm_ctx_set_counts: no negative count, no cell above 2^31 - 1 reads
-    for (size_t i = 0; i < (size_t)N * S; ++i) {
-        int64_t tot = 0;
-        for (int b = 0; b < 4; ++b) {
-            const int64_t x = counts[i * 4 + b];
-            if (x < 0 || x > 2147483647ll) { dsm_set_error("assign_tau_sampled: count %lld at position %zu, sample %zu", (long long)x, i / S, i % S); return DSM_ERR_ARG; }
-            tot += x;
-        }
-        if (tot > 2147483647ll) { dsm_set_error("assign_tau_sampled: depth above 2^31-1 at position %zu, sample %zu", i / S, i % S); return DSM_ERR_ARG; }
-    }
+    DSM_TRY(asmp_check_model(S, G, gamma, eta, burn, kept, pair_every));
+    DSM_TRY(dsm_check_counts("assign_tau_sampled", counts, (size_t)N, S));
     if (N == 0) return DSM_OK;
-    const int nd = dsm_device_count();
-    if (nd <= 0) { dsm_set_error("no HIP device visible"); return DSM_ERR_NODEVICE; }
-    if (device < 0 || device >= nd) { dsm_set_error("device %d out of range (0..%d)", device, nd - 1); return DSM_ERR_ARG; }
-    HIP_TRY(hipSetDevice(device));
+    DSM_TRY(dsm_bind_device(device));
     return asmp_run(nullptr, counts, N, S, G, gamma, eta, seed, burn, kept, pair_every, map_state, map_ll, conf, marg, spread, draw_state);
 }
 
@@ -588,12 +551,9 @@ extern "C" int dsm_ctx_assign_tau_sampled_pairs(dsm_ctx *c, const double *gamma,
                                                 int pair_every, uint8_t *map_state, double *map_ll, double *conf, double *marg,
                                                 double *spread, uint8_t *draw_state)
 {
-    if (!c) { dsm_set_error("null context"); return DSM_ERR_ARG; }
-    if (!c->cnt_vs) { dsm_set_error("no count tensor: call dsm_ctx_set_counts first"); return DSM_ERR_STATE; }
+    DSM_TRY(dsm_ctx_enter(c, true));
     if (!gamma || !eta || !map_state || !marg) { dsm_set_error("ctx_assign_tau_sampled: null pointer"); return DSM_ERR_ARG; }
-    STRY(asmp_check_model(c->S, G, gamma, eta, burn, kept, pair_every));
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));           // the resident tensor is read from the default stream below
+    DSM_TRY(asmp_check_model(c->S, G, gamma, eta, burn, kept, pair_every));
     return asmp_run(c->cnt_vs, nullptr, c->V, c->S, G, gamma, eta, seed, burn, kept, pair_every, map_state, map_ll, conf, marg, spread,
                     draw_state);
 }

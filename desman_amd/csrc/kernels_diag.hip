@@ -10,6 +10,7 @@
 #include <algorithm>
 
 #include "dsm_host.h"
+#include "dsm_host_util.h"
 
 #define DG_BLOCKS 2048          // workgroups a launch aims at (256 compute units x 8)
 
@@ -72,9 +73,7 @@ static int g_diag_parts = 0;      // dsm_diag_debug_set_parts: iteration parts p
 
 extern "C" int dsm_diag_debug_set_parts(int parts)
 {
-    if (parts < 0) { dsm_set_error("diag: parts %d", parts); return DSM_ERR_ARG; }
-    g_diag_parts = parts;
-    return DSM_OK;
+    return dsm_set_knob(&g_diag_parts, parts, "diag", "parts");
 }
 
 // d_sum, d_first, d_bsq [V][G][4] int64 and d_flips [V][G] int32, zeroed here; d_inv [B * L][G]: inv[t][perm[t][g]] = g; B even

@@ -16,6 +16,7 @@
 #include <math.h>
 
 #include "dsm_host.h"
+#include "dsm_host_util.h"
 
 #define FIT_BLOCKS 2048         // workgroups a launch aims at (256 compute units x 8)
 #define FIT_LDS_GAMMA 4096      // doubles of LDS a chunk of gamma columns may take (32 KiB): the chunk is min(G, FIT_LDS_GAMMA / sample slots)
@@ -197,9 +198,7 @@ static int g_fit_parts = 0;       // dsm_fit_debug_set_parts: iteration parts pe
 
 extern "C" int dsm_fit_debug_set_parts(int parts)
 {
-    if (parts < 0) { dsm_set_error("fit: parts %d", parts); return DSM_ERR_ARG; }
-    g_fit_parts = parts;
-    return DSM_OK;
+    return dsm_set_knob(&g_fit_parts, parts, "fit", "parts");
 }
 
 // the tile, the gamma chunk and the grid of a launch over n_it iterations of this context's table; nothing is launched

@@ -30,6 +30,7 @@
 
 #include "dsm_device.h"
 #include "dsm_host.h"
+#include "dsm_host_util.h"
 #include "log_table.h"
 
 #define PRED_WAVES 4096                     // wavefronts a launch aims at (256 compute units x 16) before iterations are cut into parts
@@ -46,13 +47,6 @@ struct PredParams {
     int nt, tpp;                // used iterations of this launch, iterations per part
     double *part;               // [nt][n][P][2]: max, sum exp(L - max)
 };
-
-__device__ __forceinline__ double pred_wave_max(double x)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x = fmax(x, __shfl_xor(x, off, 64));
-    return x;
-}
 
 static size_t pred_lds_bytes(int S, int G)
 {
@@ -151,7 +145,7 @@ __global__ __launch_bounds__(64) void pred_kernel(const PredParams p)
             if (!lane_on) L = NINF;
             if (GO > 0) __syncthreads();      // the next block rewrites `base`
 
-            const double mB = pred_wave_max(L);
+            const double mB = wave_max_f64(L);
             if (mB > m) {                       // wave-uniform
                 Wl *= (m == NINF) ? 0.0 : exp(m - mB);
                 m = mB;
@@ -223,40 +217,18 @@ static int g_pred_parts = 0;        // dsm_pred_debug_set_parts: iteration parts
 
 extern "C" int dsm_pred_debug_set_chunk(int positions)
 {
-    if (positions < 0) { dsm_set_error("pred: chunk %d", positions); return DSM_ERR_ARG; }
-    g_pred_chunk = positions;
-    return DSM_OK;
+    return dsm_set_knob(&g_pred_chunk, positions, "pred", "chunk");
 }
 
 extern "C" int dsm_pred_debug_set_parts(int parts)
 {
-    if (parts < 0) { dsm_set_error("pred: parts %d", parts); return DSM_ERR_ARG; }
-    g_pred_parts = parts;
-    return DSM_OK;
+    return dsm_set_knob(&g_pred_parts, parts, "pred", "parts");
 }
-
-namespace {
-template <typename T>
-struct PredBuf {
-    T *p = nullptr;
-    ~PredBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n)
-    {
-        hipError_t e = hipMalloc((void **)&p, (n ? n : 1) * sizeof(T));
-        if (e != hipSuccess) { p = nullptr; dsm_set_error("pred: hipMalloc(%zu B) failed: %s", n * sizeof(T), hipGetErrorString(e)); return DSM_ERR_NOMEM; }
-        return DSM_OK;
-    }
-    operator T *() const { return p; }
-};
-}  // namespace
-
-#define PTRY(x) do { int _r = (x); if (_r != DSM_OK) return _r; } while (0)
 
 extern "C" int dsm_ctx_trace_predictive(dsm_ctx *c, const int64_t *counts, int N, int it0, int n_it, int stride, double *lppd,
                                         double *mean, double *var, double *logz_it)
 {
-    if (!c) { dsm_set_error("null context"); return DSM_ERR_ARG; }
-    if (!c->cnt_vs) { dsm_set_error("no count tensor: call dsm_ctx_set_counts first"); return DSM_ERR_STATE; }
+    DSM_TRY(dsm_ctx_enter(c, false));                  // everything below runs on c->stream
     if (!c->have_state) { dsm_set_error("no chain state: call dsm_ctx_set_state first"); return DSM_ERR_STATE; }
     if (!c->tau_trace) { dsm_set_error("trace_predictive: no update has run"); return DSM_ERR_STATE; }
     if (it0 < 0 || n_it < 0 || it0 > c->n_trace || n_it > c->n_trace - it0) {
@@ -271,26 +243,15 @@ extern "C" int dsm_ctx_trace_predictive(dsm_ctx *c, const int64_t *counts, int N
     }
     if (counts) {
         if (N < 0) { dsm_set_error("trace_predictive: N=%d", N); return DSM_ERR_ARG; }
-        // the count rules of dsm_ctx_set_counts: no negative count, no depth above 2^31 - 1 reads
-        for (size_t i = 0; i < (size_t)N * S; ++i) {
-            int64_t tot = 0;
-            for (int b = 0; b < 4; ++b) {
-                const int64_t x = counts[i * 4 + b];
-                if (x < 0 || x > 2147483647ll) { dsm_set_error("trace_predictive: count %lld at position %zu, sample %zu", (long long)x, i / S, i % S); return DSM_ERR_ARG; }
-                tot += x;
-            }
-            if (tot > 2147483647ll) { dsm_set_error("trace_predictive: depth above 2^31-1 at position %zu, sample %zu", i / S, i % S); return DSM_ERR_ARG; }
-        }
+        DSM_TRY(dsm_check_counts("trace_predictive", counts, (size_t)N, S));
     } else N = c->V;
     if (n_it == 0 || N == 0) return DSM_OK;
 
     const int nu = (n_it + stride - 1) / stride;
-    const int GO = G > 3 ? G - 3 : 0, NB = 1 << (2 * GO), P = std::min(NB, 64), bpp = NB / P;
+    const JointSplit js(G);
+    const int P = js.P, bpp = js.bpp;
     const size_t lds = pred_lds_bytes(S, G);
-    if (lds > 160 * 1024) { dsm_set_error("trace_predictive: %zu B of LDS", lds); return DSM_ERR_UNSUPPORTED; }
-    HIP_TRY(hipSetDevice(c->device));
-    if (lds > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&pred_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    DSM_TRY(dsm_allow_lds(reinterpret_cast<const void *>(&pred_kernel), lds, "trace_predictive"));
     // positions per chunk: the logz matrix [nu][NC] stays below PRED_LOGZ_BYTES; iterations per launch: the rows [TC][NC][P][2] below
     // PRED_PART_BYTES -- one position's column and one iteration's rows at the least
     int NC = (int)std::max<size_t>(1, std::min<size_t>((size_t)1 << 16, PRED_LOGZ_BYTES / ((size_t)nu * sizeof(double))));
@@ -298,22 +259,16 @@ extern "C" int dsm_ctx_trace_predictive(dsm_ctx *c, const int64_t *counts, int N
     NC = std::min(NC, N);
     const int TC = (int)std::max<size_t>(1, std::min<size_t>((size_t)nu, PRED_PART_BYTES / ((size_t)NC * P * 2 * sizeof(double))));
 
-    PredBuf<int32_t> d_x; PredBuf<double> d_part, d_logz, d_lppd, d_mean, d_var;
-    if (counts) PTRY(d_x.alloc((size_t)NC * S * 4));
-    PTRY(d_part.alloc((size_t)TC * NC * P * 2)); PTRY(d_logz.alloc((size_t)nu * NC));
-    PTRY(d_lppd.alloc(NC)); PTRY(d_mean.alloc(NC)); PTRY(d_var.alloc(NC));
+    DevBuf<int32_t> d_x; DevBuf<double> d_part, d_logz, d_lppd, d_mean, d_var;
+    if (counts) DSM_TRY(d_x.alloc((size_t)NC * S * 4));
+    DSM_TRY(d_part.alloc((size_t)TC * NC * P * 2)); DSM_TRY(d_logz.alloc((size_t)nu * NC));
+    DSM_TRY(d_lppd.alloc(NC)); DSM_TRY(d_mean.alloc(NC)); DSM_TRY(d_var.alloc(NC));
     const size_t sg = (size_t)S * G;
     std::vector<int32_t> x32;
     for (int n0 = 0; n0 < N; n0 += NC) {
         const int n = std::min(NC, N - n0);
         const int32_t *cnt = counts ? d_x.p : c->cnt_vs + (size_t)n0 * S * 4;
-        if (counts) {
-            x32.resize((size_t)n * S * 4);
-            const int64_t *src = counts + (size_t)n0 * S * 4;
-            for (size_t i = 0; i < x32.size(); ++i) x32[i] = (int32_t)src[i];
-            HIP_TRY(hipMemcpyAsync(d_x, x32.data(), x32.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));       // x32 is refilled for the next chunk
-        }
+        if (counts) DSM_TRY(dsm_stage_counts(counts + (size_t)n0 * S * 4, (size_t)n * S * 4, d_x, x32, c->stream));
         for (int u0 = 0; u0 < nu; u0 += TC) {
             const int nt = std::min(TC, nu - u0);
             int parts = g_pred_parts > 0 ? g_pred_parts : (int)((PRED_WAVES + (long long)n * P - 1) / ((long long)n * P));

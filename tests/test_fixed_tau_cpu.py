@@ -149,4 +149,4 @@ def test_bad_arguments_come_back_as_error_codes_without_a_device():
     lib = _lib.load()
     assert lib.dsm_ctx_gibbs_update_fixed_tau(None, -1, 0, 0) == -2
     assert lib.dsm_ctx_gibbs_update_fixed_tau(None, 1, 0, 2) == -2
-    assert lib.dsm_ctx_gibbs_update_fixed_tau(None, 1, 0, 0) == -2                # null context (need())
+    assert lib.dsm_ctx_gibbs_update_fixed_tau(None, 1, 0, 0) == -2                # null context (dsm_ctx_need())
