@@ -434,7 +434,11 @@ __device__ __forceinline__ bool sweep_screen(const double (&pre)[NSL][4], const 
     return screen_certify<NSL>(c32, xtot, G, uw, best);
 }
 
-// the same from a prefix carried in fp32 ([sample slot][base pair]): the register-lean form of the sweep (kernels_gibbs.hip: tau_body, LEAN)
+// the same from a prefix carried in fp32 ([sample slot][base pair]): the register-lean form of the sweep (kernels_gibbs.hip: tau_body, LEAN).
+// screen_certify's budget covers it as it stands: the (G + 4) roundings per mixture value are two for the fp32 inputs (eta, gamma: all
+// terms are positive, so the sum is off by no more than its worst term) and one per fma link, G - 1 links of the rest mixture and the
+// candidate's own -- G + 2 when EVERY link is made in fp32, which is what step g = 0 of the fp64-prefix form does already (its prefix is
+// empty).  A prefix carried in fp32 makes every step look like that one; no step has more links.
 typedef float dsm_f2 __attribute__((ext_vector_type(2)));
 template <int LPV, int NSL>
 __device__ __forceinline__ bool sweep_screen32(const dsm_f2 (&pre32)[NSL][2], const float (&xi)[NSL][4], uint64_t t, int g, int G, int lig,
@@ -443,12 +447,30 @@ __device__ __forceinline__ bool sweep_screen32(const dsm_f2 (&pre32)[NSL][2], co
     constexpr int SP = LPV * NSL;
     typedef dsm_f2 f2;
     f2 s32[NSL][2];
+    int h = g + 1;
+    // Two samples per lane: the first link is made straight from the carried prefix (the same fma, the same order) instead of copying
+    // the prefix and entering the unrolled loop with it -- 32.7 vs 34.2 us per sweep at 10k x 64 x 8 (profiles/tau_lean2_bench.txt).
+    // The wider lean tilings (three, six, eight samples per lane) keep the copy: they were not measured with it.
+    if (NSL == 2 && h < G) {
+        const f2 *er = reinterpret_cast<const f2 *>(eS32 + (int)((t >> (2 * h)) & 3) * 4);
+        const f2 e01 = er[0], e23 = er[1];
 #pragma unroll
-    for (int j = 0; j < NSL; ++j)
+        for (int j = 0; j < NSL; ++j) {
+            const float gm = gT32[h * SP + lig + j * LPV];
+            const f2 gm2 = (f2){gm, gm};
+            s32[j][0] = __builtin_elementwise_fma(e01, gm2, pre32[j][0]);
+            s32[j][1] = __builtin_elementwise_fma(e23, gm2, pre32[j][1]);
+        }
+        ++h;
+    } else {
 #pragma unroll
-        for (int bp = 0; bp < 2; ++bp) s32[j][bp] = pre32[j][bp];
+        for (int j = 0; j < NSL; ++j)
+#pragma unroll
+            for (int bp = 0; bp < 2; ++bp) s32[j][bp] = pre32[j][bp];
+    }
+    ISA_MARK("screen_links");
 #pragma unroll 4
-    for (int h = g + 1; h < G; ++h) {
+    for (; h < G; ++h) {
         const f2 *er = reinterpret_cast<const f2 *>(eS32 + (int)((t >> (2 * h)) & 3) * 4);
         const f2 e01 = er[0], e23 = er[1];
 #pragma unroll
@@ -459,6 +481,7 @@ __device__ __forceinline__ bool sweep_screen32(const dsm_f2 (&pre32)[NSL][2], co
             s32[j][1] = __builtin_elementwise_fma(e23, gm2, s32[j][1]);
         }
     }
+    ISA_MARK("screen_candidates");
     const f2 *e2 = reinterpret_cast<const f2 *>(eS32);               // [a][bp], then the column minima [bp]
     f2 acc2[4] = {(f2){0.0f, 0.0f}, (f2){0.0f, 0.0f}, (f2){0.0f, 0.0f}, (f2){0.0f, 0.0f}};
     float lbmin = 1.0f;
@@ -482,8 +505,10 @@ __device__ __forceinline__ bool sweep_screen32(const dsm_f2 (&pre32)[NSL][2], co
     float c32[4];
 #pragma unroll
     for (int a = 0; a < 4; ++a) c32[a] = acc2[a].x + acc2[a].y;
+    ISA_MARK("screen_reduce");
     if (!(lbmin >= 1.0e-30f)) c32[0] = __builtin_nanf("");          // poisons the totals of the whole group
     group_allreduce_sum4_f32<LPV>(c32[0], c32[1], c32[2], c32[3]);    // log2 units
+    ISA_MARK("screen_certify");
     return screen_certify<NSL>(c32, xtot, G, uw, best);
 }
 

@@ -886,18 +886,16 @@ struct TauParams {
     FinalParams fin;          // two sweeps could carry it); it reads the other parity of ll_partial / nchange
 };
 
-// which shapes of the sweep run its register-lean form (tau_body: LEAN): three, six and eight samples per lane of a 32- or 64-lane group.
+// which shapes of the sweep run its register-lean form (tau_body: LEAN): two, three, six and eight samples per lane of a 32- or 64-lane group.
 // Measured against the fp64-prefix form on one box (scripts/dbg/lean_ab.sh), ms per iteration: 32 x 3 0.722 vs 0.744 (50k x 96 x 12),
 // 64 x 3 0.237 vs 0.243, 64 x 6 0.711 vs 0.819 (10k x 300 x 8), 64 x 8 0.570 vs 0.626 (5k x 512 x 8); it loses at 16 x 3 (0.167 vs 0.163)
-// and 64 x 4 (0.551 vs 0.530), and at two samples per lane.
+// and 64 x 4 (0.551 vs 0.530).  Two samples per lane at THREE wavefronts per SIMD (profiles/tau_lean2_bench.txt; the trial at four
+// wavefronts, 128 VGPRs, spilled and lost: DESIGN.md sec. 3d): 32 x 2 0.0970 vs 0.0990 (10k x 64 x 8), 64 x 2 0.1607 vs 0.1640 (10k x 128 x 8).
+// -DTAU_NO_LEAN builds every tiling in the fp64-prefix form (the A/B switch of scripts/dbg/lean_ab.sh).
 #ifdef TAU_NO_LEAN
 #define TAU_LEAN(LPV, NSL) false
 #else
-#ifdef TAU_LEAN2          /* experiment: the lean form at two samples per lane too, four wavefronts per SIMD */
 #define TAU_LEAN(LPV, NSL) ((LPV) >= 32 && ((NSL) == 2 || (NSL) == 3 || (NSL) == 6 || (NSL) == 8))
-#else
-#define TAU_LEAN(LPV, NSL) ((LPV) >= 32 && ((NSL) == 3 || (NSL) == 6 || (NSL) == 8))
-#endif
 #endif
 
 // NT: the instantiation with the near-tie screen (dsm_device.h: sweep_neartie_core) for chains that carry haplotypes rare in every
@@ -914,6 +912,8 @@ __device__ __forceinline__ void tau_body(const TauParams &p)
         return;
     }
     constexpr bool LEAN = TAU_LEAN(LPV, NSL) && SWEEP;       // the register-lean form of the sweep (below)
+    constexpr bool KEEPX = LEAN && NSL == 2;                 // ... which at two samples per lane has room for the integer counts as well
+    constexpr bool REFORM = LEAN && NSL >= 3;                // ... and from three on forms its addresses afresh instead of keeping them (below)
     const int bid = p.order ? (int)p.order[blockIdx.x] : (int)blockIdx.x;       // the block of variants this workgroup works on
     constexpr int SP = LPV * NSL;
     constexpr int GPB = 256 / LPV;
@@ -961,19 +961,22 @@ __device__ __forceinline__ void tau_body(const TauParams &p)
         // screening pass multiplies by exactly that, the rare fp64 step by (double)(float)count, c_sample_tau.c:164) and the
         // likelihood epilogue, which needs the integers, loads the slab again -- an L2 hit a few microseconds after the first
         // load.  With both forms live across the haplotype loop the compiler spilled per variant (round 3: 94 MB of scratch
-        // write-back per sweep at 50k x 96 x 12).
-        int xi[LEAN ? 1 : NSL][4];
+        // write-back per sweep at 50k x 96 x 12).  Two samples per lane (KEEPX) have room for the eight integers next to the floats
+        // (151 of the 168 VGPRs of three wavefronts per SIMD, no scratch: profiles/tau_lean2_resources.txt) and the epilogue reads
+        // them -- the same bits; the sweep at 10k x 64 x 8 runs 34.2 us with them kept, 35.5 us with the second load.
+        int xi[(LEAN && !KEEPX) ? 1 : NSL][4];
         float xs[LEAN ? NSL : 1][4];
         double xf[LEAN ? 1 : NSL][4];
 #pragma unroll
         for (int j = 0; j < NSL; ++j) {
             int ligl = lig;
-            if constexpr (LEAN) asm volatile("" : "+v"(ligl));      // the slab's address is formed afresh, not kept in a register pair
+            if constexpr (REFORM) asm volatile("" : "+v"(ligl));      // the slab's address is formed afresh, not kept in a register pair
             const int s = ligl + j * LPV;
             int4 c = make_int4(0, 0, 0, 0);
             if (s < S) c = reinterpret_cast<const int4 *>(p.cnt_vs)[(size_t)v * S + s];
             if constexpr (LEAN) {
                 xs[j][0] = (float)c.x; xs[j][1] = (float)c.y; xs[j][2] = (float)c.z; xs[j][3] = (float)c.w;
+                if constexpr (KEEPX) { xi[j][0] = c.x; xi[j][1] = c.y; xi[j][2] = c.z; xi[j][3] = c.w; }
             } else {
                 xi[j][0] = c.x; xi[j][1] = c.y; xi[j][2] = c.z; xi[j][3] = c.w;
 #pragma unroll
@@ -994,10 +997,12 @@ __device__ __forceinline__ void tau_body(const TauParams &p)
             // unrolled fp64 step live, three samples per lane need 219 VGPRs = two wavefronts per SIMD; lean they fit 160 = three, with
             // NO scratch (round 3's form spilled 23 registers and stored two of them per variant: 94 MB of scratch write-back per sweep
             // at 50k x 96 x 12; profiles/r04_kernel_regs.txt).  Same box, lean vs not, ms per iteration: 50k x 96 x 12 0.683 (round 3's
-            // lean form 0.722) vs 0.744, x 96 x 6 0.480 vs 0.508, 10k x 192 x 8 0.225 vs 0.243.  At two samples per lane the lean form at
-            // FOUR wavefronts per SIMD (-DTAU_LEAN2: 128 VGPRs, the loop's accumulators spilled per variant) measures 104.2 vs 103.1 us
-            // per iteration at config 3 (sweep 39.2 vs 37.7 us): not used; at 16 lanes per variant (S <= 48: 0.167 vs 0.163) the same
-            // trade loses as well.
+            // lean form 0.722) vs 0.744, x 96 x 6 0.480 vs 0.508, 10k x 192 x 8 0.225 vs 0.243.  Two samples per lane run it at THREE
+            // wavefronts per SIMD as well (143-153 VGPRs): what it saves there is not registers but the per-step work only the fp64 step
+            // needs -- eight fp64 fma of the prefix, eight fp64 -> fp32 conversions of it, eight int -> fp32 conversions of the counts.
+            // The address re-forming asm below (REFORM) is for three samples per lane and more: at two it only adds instructions
+            // (35.3 us without it vs 35.5 us with it).  At 16 lanes per variant (S <= 48: 0.167 vs 0.163) the lean form loses
+            // (DESIGN.md sec. 3d).
             double pre[LEAN ? 1 : NSL][4];
             dsm_f2 pre32[LEAN ? NSL : 1][2];
 #pragma unroll
@@ -1210,7 +1215,7 @@ __device__ __forceinline__ void tau_body(const TauParams &p)
             }
             if constexpr (LEAN) {
                 int vv = v;
-                asm volatile("" : "+v"(vv));                 // &tau[v] formed afresh: it was spilled across the haplotype loop
+                if constexpr (REFORM) asm volatile("" : "+v"(vv));                 // &tau[v] formed afresh: it was spilled across the haplotype loop
                 if (lig == 0) p.tau[vv] = t;
             } else if (lig == 0) p.tau[v] = t;
         }
@@ -1220,9 +1225,9 @@ __device__ __forceinline__ void tau_body(const TauParams &p)
 #pragma unroll
             for (int j = 0; j < NSL; ++j) {
                 int xl[4];                                   // this slab's counts as integers
-                if constexpr (LEAN) {
+                if constexpr (LEAN && !KEEPX) {
                     int vv = v, ligl = lig;
-                    asm volatile("" : "+v"(vv), "+v"(ligl)); // a second load, not the first one (or its address) kept alive across the sweep
+                    if constexpr (REFORM) asm volatile("" : "+v"(vv), "+v"(ligl)); // a second load, not the first one (or its address) kept alive across the sweep
                     const int s = ligl + j * LPV;
                     int4 c = make_int4(0, 0, 0, 0);
                     if (s < S) c = reinterpret_cast<const int4 *>(p.cnt_vs)[(size_t)vv * S + s];
@@ -1268,8 +1273,8 @@ __device__ __forceinline__ void tau_body(const TauParams &p)
     }
 }
 
-// three samples per lane, 32 or 64 lanes per variant: the lean form of the sweep at three wavefronts per SIMD (tau_body: LEAN)
-#define TAU_MIN_WGS(LPV, NSL) (TAU_LEAN(LPV, NSL) ? ((NSL) == 2 ? 4 : (NSL) == 3 ? 3 : 2) : 1)
+// two and three samples per lane, 32 or 64 lanes per variant: the lean form of the sweep at three wavefronts per SIMD (tau_body: LEAN)
+#define TAU_MIN_WGS(LPV, NSL) (TAU_LEAN(LPV, NSL) ? ((NSL) <= 3 ? 3 : 2) : 1)
 template <int LPV, int NSL, bool SWEEP, bool LL>
 __global__ __launch_bounds__(256, TAU_MIN_WGS(LPV, NSL)) void tau_kernel(TauParams p) { tau_body<LPV, NSL, SWEEP, LL>(p); }
 template <int LPV, int NSL>
