@@ -19,6 +19,7 @@ from . import _lib
 from . import fixed_tau as _fixed_tau
 from . import check as _check
 from . import diagnose as _diagnose
+from . import marginals as _marginals
 from . import predictive as _predictive
 from . import relabel as _relabel
 from . import sampletau as _sampletau
@@ -525,6 +526,29 @@ class HaploSNP_Sampler:
             d["names"] = ["lp", "ll"] + ["gamma_%d_%d" % (s, h) for s in range(g.shape[1]) for h in range(g.shape[2])]
             return d
         return self._diagnosed("scalars", batch_len, make)
+
+    # ---- Rao-Blackwellised tau marginals of the last update() from the resident traces (desman_amd/marginals.py)
+    def _star_labelled(self):
+        """tau_star as [V, G] digits under the labels of the relabelling in force: with ``relabel_ref`` set tau_star is matched to the
+        reference like any iteration (sndPosterior does the same), otherwise its labels are the stored ones"""
+        star = _marginals.tau_digits(self.tau_star)
+        if self.relabel_ref is None:
+            return star
+        ref = _relabel._reference(self, self.relabel_ref)[1]
+        own, _ = _relabel.min_cost_assignment(self.compSND(self.tau_star, self._onehot(ref)))       # tau_star's haplotype g is label own[g]
+        return star[:, np.argsort(own)]
+
+    def tauMarginals(self, batch_len=None):
+        """dict of p, mcse [V, G, 4] -- the average over the last N = B L stored iterations of the exact full conditional of every
+        tau[v][g], and its batch-means Monte Carlo standard error (L = batch_len, default floor(sqrt(max_iter))) --, calls (per
+        position and haplotype: call, prob, star, agree, entropy; marginals.calls), summary (marginals.summary) and dead; under the
+        relabelling the diagnostics are made under; kept until the next update"""
+        def make(L, perm):
+            m = _marginals.rb_marginals(self._trace_ctx().trace_rb_marginals(L, perm=perm))
+            m["calls"] = _marginals.calls(m["p"], self._star_labelled())
+            m["summary"] = _marginals.summary(m["calls"], m["dead"])
+            return m
+        return self._diagnosed("rb", batch_len, make)
 
     # ---- posterior predictive fit of the last update() from the resident traces (desman_amd/check.py, DESIGN.md sec. 8g)
     def fitCheck(self, cells=False):

@@ -242,6 +242,30 @@ class Output_Results:
         frame.to_csv(self._path("Diag_scalars.csv"))
         logging.info("Diag_scalars.csv written")
 
+    # ---- `desman --marginals`: Rao-Blackwellised tau marginals of the stored iterations (desman_amd/marginals.py)
+    def output_Tau_marginals(self, marg, relabelled=False):
+        """Tau_Mean_rb.csv (Tau_Mean_rb_relabelled.csv under a relabelling, as Tau_Mean.csv has Tau_Mean_relabelled.csv): the layout and
+        row order of Tau_Mean.csv, every cell the average conditional probability of that base; Tau_rb_MCSE.csv: the layout of
+        Tau_MCSE.csv, its Monte Carlo standard error; Tau_calls.csv: one row per (position, haplotype), position-major -- Contig, Position,
+        haplotype, call, prob, star, agree, entropy (HaploSNP_Sampler.tauMarginals); and one log line with the expected number of wrong calls, the
+        cells whose call has a probability below marginals.PROB_LOW and the dead cell-iterations"""
+        from . import marginals
+        V, G = self.haplo_SNP.V, self.haplo_SNP.G
+        mean_name = "Tau_Mean_rb_relabelled.csv" if relabelled else "Tau_Mean_rb.csv"
+        self._haplotype_table(mean_name, np.reshape(marg["p"], (V, G, 4)), self.filtered_contig_names, self.filtered_position)
+        self._haplotype_table("Tau_rb_MCSE.csv", np.reshape(marg["mcse"], (V, G, 4)), self.filtered_contig_names, self.filtered_position)
+        cells = marg["calls"]
+        cols = {"Position": np.repeat(np.asarray(self.filtered_position), G), "haplotype": np.tile(np.arange(G), V)}
+        for k in ("call", "prob", "star", "agree", "entropy"):
+            cols[k] = np.reshape(cells[k], -1)
+        frame = pd.DataFrame(cols, index=np.repeat(np.asarray(self.filtered_contig_names), G))
+        frame.index.name = "Contig"
+        frame.to_csv(self._path("Tau_calls.csv"))
+        s = marg["summary"]
+        logging.info("%s, Tau_rb_MCSE.csv, Tau_calls.csv written: %.2f of %d calls expected wrong, %d with probability below %g, "
+                     "%d disagree with Tau_star, %d dead cell-iterations"
+                     % (mean_name, s["expected_wrong"], s["cells"], s["low"], marginals.PROB_LOW, s["disagree"], s["dead"]))
+
     # ---- `desman --check`: posterior predictive fit per sample and per position (desman_amd/check.py)
     _FIT_COLUMNS = (("cells", "cells"), ("X2", "X2"), ("expected", "expected"), ("z", "z"), ("deviance", "deviance"))
 

@@ -124,6 +124,8 @@ SIGNATURES = {
     "dsm_fit_debug_set_parts": (_i, [_i]),
     "dsm_fit_debug_path": (_i, [_vp, _i, C.POINTER(_i)]),
     "dsm_ctx_debug_set_param_trace": (_i, [_vp, _vp, _vp, _i]),
+    "dsm_ctx_trace_rb_marginals": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, C.POINTER(C.c_longlong)]),
+    "dsm_rbtau_debug_path": (_i, [_i, _i, C.POINTER(_i)]),
     "dsm_nmft_set": (_i, [_vp, _f64p, _f64p, _i]),
     "dsm_nmft_get": (_i, [_vp, _vp, _vp]),
     "dsm_nmft_factorize": (_i, [_vp, _i, _d, _i, C.POINTER(_i), _vp]),
@@ -364,6 +366,14 @@ def pairtau_debug_path(S, G):
     """test hook: (lanes per position, sample slots per lane) of the pair-pass kernel for S samples; nothing is launched"""
     out = (C.c_int * 2)()
     check(load().dsm_pairtau_debug_path(int(S), int(G), out))
+    return int(out[0]), int(out[1])
+
+
+def rbtau_debug_path(S, G):
+    """test hook: (lanes per position, sample slots per lane) of the kernel of Context.trace_rb_marginals for S samples; nothing is
+    launched"""
+    out = (C.c_int * 2)()
+    check(load().dsm_rbtau_debug_path(int(S), int(G), out))
     return int(out[0]), int(out[1])
 
 
@@ -966,6 +976,29 @@ class Context:
         check(self.lib.dsm_ctx_trace_fit_stats(self._h, int(it0), n_it, _ptr(out.get("sample")), _ptr(out.get("position")),
                                                _ptr(out.get("cell"))))
         out["n_it"] = n_it
+        return out
+
+    def trace_rb_marginals(self, batch_len, perm=None, it0=0, n_it=None, want=("sum", "bsq")):
+        """Rao-Blackwellised tau marginals of the positions of the fit (include/desman_hip.h: dsm_ctx_trace_rb_marginals;
+        desman_amd/marginals.py): the full conditional q of every tau[v][g] under (tau_t, gamma_t, eta_t), over the LAST N = B L of the
+        iterations it0 .. it0 + n_it - 1 (L = batch_len, B = 2 (n_it // (2 L))) under the labels of ``perm`` ([n_it, G], rows counted from
+        it0; None = identity): a dict of sum and bsq [V, G, 4] float64 (those named in ``want``), dead, B, N and L"""
+        n_it = self.n_trace - int(it0) if n_it is None else int(n_it)
+        L = int(batch_len)
+        p = None
+        if perm is not None:
+            p = np.ascontiguousarray(perm, dtype=np.uint8)
+            if p.ndim != 2 or p.shape != (max(n_it, 0), self.G) or not np.array_equal(p, np.asarray(perm)):
+                raise ValueError("trace_rb_marginals: perm must be [n_it=%d, G=%d] labels 0..G-1" % (n_it, self.G))
+        bad = [k for k in want if k not in ("sum", "bsq")]
+        if bad:
+            raise ValueError("trace_rb_marginals: unknown output %r (sum, bsq)" % bad[0])
+        out = {k: np.zeros((self.V, self.G, 4), dtype=np.float64) for k in ("sum", "bsq") if k in want}
+        dead = C.c_longlong(0)
+        check(self.lib.dsm_ctx_trace_rb_marginals(self._h, _ptr(p), int(it0), n_it, L, _ptr(out.get("sum")), _ptr(out.get("bsq")),
+                                                  C.byref(dead)))
+        B = 2 * (n_it // (2 * L)) if L >= 1 else 0
+        out.update(dead=int(dead.value), B=B, N=B * L, L=L)
         return out
 
     def trace_predictive(self, counts=None, it0=0, n_it=None, stride=1, want=("lppd", "mean", "var")):

@@ -79,6 +79,13 @@ def build_parser():
                          "positions, with -r also kind `heldout` = the log predictive density of the positions left out of the fit) and "
                          "Predictive_summary.csv; from N evenly spaced stored iterations (default 50, a convention); -g up to 10; "
                          "compare runs with `python -m desman_amd.predictive compare` (extension)")
+    ap.add_argument('--marginals', action='store_true',
+                    help="also write the Rao-Blackwellised posterior of the haplotype bases from the stored iterations: Tau_Mean_rb.csv "
+                         "(the layout of Tau_Mean.csv; the average of each base's exact conditional probability instead of the average "
+                         "of the sampled bases: finer than 1/iterations, and not 0 or 1 merely because a base never flipped), "
+                         "Tau_rb_MCSE.csv (its Monte Carlo standard error by batch means; batch length as --diagnose [L]) and "
+                         "Tau_calls.csv (per position and haplotype: the most probable base, its probability, the base of Tau_star, "
+                         "whether they agree, the entropy); with --relabel / --relabel-ref under that relabelling (extension)")
     ap.add_argument('--pair-moves', dest='pair_moves', nargs='?', const=PAIR_MOVES, default=None, type=int, metavar='E',
                     help="add joint moves of two haplotypes to the Gibbs chain, burn-in and sampling alike: the sweep of every E-th "
                          "iteration (default %d: a convention, not tuned) is followed by a pass that redraws the bases of every pair of "
@@ -241,6 +248,28 @@ def _report_diagnose(report, chain, L):
     report.output_Diag_scalars(chain.scalarDiagnostics(L))
 
 
+def _marginals_batch_len(opts):
+    """--marginals: the batch length of Tau_rb_MCSE.csv -- the L of --diagnose [L] where one is given, else floor(sqrt(iterations)) --
+    checked against the iterations a chain will store; refused here, before any chain, where it cannot be served.  None without the
+    option."""
+    if not opts.marginals:
+        return None
+    from . import diagnose
+    n = 250 if opts.no_iter is None else opts.no_iter            # the sampler's own default
+    L = opts.diagnose if isinstance(opts.diagnose, int) and opts.diagnose is not True else diagnose.default_batch_len(n)
+    if L < 1:
+        sys.exit("desman: --marginals: the batch length must be at least 1; got %d" % L)
+    if n < 2 * L:
+        sys.exit("desman: --marginals: %d stored iterations (-i) are fewer than two batches of %d" % (n, L))
+    return L
+
+
+def _report_marginals(report, chain, L):
+    """--marginals: the Rao-Blackwellised tau marginals of the fitted chain, next to the usual files (which do not change); under the
+    relabelling of --relabel / --relabel-ref where one was made"""
+    report.output_Tau_marginals(chain.tauMarginals(L), relabelled=chain._diag_perm() is not None)
+
+
 def _check_options(opts):
     """--check / --check-cells: refused here, before any chain, where they cannot be served"""
     if opts.check_cells and not opts.check:
@@ -361,6 +390,7 @@ def main(argv=None):
         sys.exit(-1)
     _pair_moves_options(opts)
     diag_len = _diagnose_batch_len(opts)
+    marg_len = _marginals_batch_len(opts)
     _check_options(opts)
     _predictive_options(opts)
     report = Output_Results(opts.output_dir)
@@ -372,6 +402,8 @@ def main(argv=None):
         _report_relabel(report, chain, ref)
     if diag_len is not None:
         _report_diagnose(report, chain, diag_len)
+    if marg_len is not None:
+        _report_marginals(report, chain, marg_len)
     if opts.check:
         _report_check(report, chain, opts.check_cells)
     if opts.predictive is not None:
@@ -398,6 +430,7 @@ def main_replicates(argv_list, on_chain=None):
             sys.exit('desman: -a/--assign_file is not supported (dead in the reference: bin/desman:213-214)')
         _pair_moves_options(opts, replicates=True)
         diag_len = _diagnose_batch_len(opts)
+        marg_len = _marginals_batch_len(opts)
         _check_options(opts)
         _predictive_options(opts, replicates=True)
         report = Output_Results(opts.output_dir)
@@ -406,7 +439,7 @@ def main_replicates(argv_list, on_chain=None):
         rng = RandomState(opts.random_seed)
         nmft = Init_NMFT(flt.snps_filter, opts.genomes, rng, device=opts.device)
         runs.append(dict(opts=opts, report=report, table=table, flt=flt, subsample=subsample, rng=rng, nmft=nmft,
-                         ref=_relabel_reference(opts, table, flt), diag_len=diag_len))
+                         ref=_relabel_reference(opts, table, flt), diag_len=diag_len, marg_len=marg_len))
     # the NMF starts: together where the batched kernels apply (one shape, S <= 128, G <= 16), else one by one
     nm = [r["nmft"] for r in runs]
     done = False
@@ -464,6 +497,8 @@ def main_replicates(argv_list, on_chain=None):
             _report_relabel(r["report"], r["chain"], r["ref"])
         if r["diag_len"] is not None:
             _report_diagnose(r["report"], r["chain"], r["diag_len"])
+        if r["marg_len"] is not None:
+            _report_marginals(r["report"], r["chain"], r["marg_len"])
         if r["opts"].check:
             _report_check(r["report"], r["chain"], r["opts"].check_cells)
     # -r: the positions left out of the fit -- batched where the replicates still agree in shape

@@ -1727,6 +1727,55 @@ extern "C" int dsm_ctx_trace_fit_stats(dsm_ctx *c, int it0, int n_it, double *sa
     return DSM_OK;
 }
 
+// Rao-Blackwellised tau marginals over stored iterations (kernels_rbtau.hip): the range, perm and batch rules of
+// dsm_ctx_trace_batch_stats; the counts and the three traces are read where they lie and nothing of the chain is written
+extern "C" int dsm_ctx_trace_rb_marginals(dsm_ctx *c, const uint8_t *perm, int it0, int n_it, int batch_len, double *sum, double *bsq,
+                                          long long *dead)
+{
+    DSM_TRY(trace_range(c, "trace_rb_marginals", it0, n_it));
+    if (batch_len < 1) { dsm_set_error("trace_rb_marginals: batch_len=%d, at least 1 is needed", batch_len); return DSM_ERR_ARG; }
+    if (n_it > 0 && n_it / 2 < batch_len) {
+        dsm_set_error("trace_rb_marginals: %d iterations are fewer than two batches of %d", n_it, batch_len);
+        return DSM_ERR_ARG;
+    }
+    const int G = c->G, L = batch_len, B = n_it > 0 ? 2 * (n_it / (2 * L)) : 0, skip = n_it - B * L;
+    std::vector<uint8_t> inv;
+    DSM_TRY(perm_inverse("trace_rb_marginals", perm, n_it, G, inv));          // the rows of skipped iterations are validated too
+    const size_t V = (size_t)c->V, nt = V * G * 4, sg = (size_t)c->S * G, used = (size_t)B * L * G;
+    if (n_it == 0) {
+        if (sum) std::fill(sum, sum + nt, 0.0);
+        if (bsq) std::fill(bsq, bsq + nt, 0.0);
+        if (dead) *dead = 0;
+        return DSM_OK;
+    }
+    { int lpv, nsl; DSM_TRY(tau_shape(c->S, &lpv, &nsl)); }                     // S <= DSM_MAX_S, before anything is allocated
+    std::vector<uint8_t> lab(used);                                           // the used rows of perm as they are (NULL: identity)
+    for (size_t i = 0; i < used; ++i) lab[i] = perm ? perm[(size_t)skip * G + i] : (uint8_t)(i % G);
+    BIND(c);
+    DevBuf<double> d_bs, d_sum, d_bsq;
+    DevBuf<unsigned long long> d_dead;
+    DevBuf<uint8_t> d_perm;
+    DSM_TRY(d_bs.alloc(nt));
+    DSM_TRY(d_sum.alloc(nt));
+    DSM_TRY(d_bsq.alloc(nt));
+    DSM_TRY(d_dead.alloc(1));
+    DSM_TRY(d_perm.alloc(used));
+    HIP_TRY(hipMemsetAsync(d_sum, 0, nt * sizeof(double), c->stream));
+    HIP_TRY(hipMemsetAsync(d_bsq, 0, nt * sizeof(double), c->stream));
+    HIP_TRY(hipMemsetAsync(d_dead, 0, sizeof(unsigned long long), c->stream));
+    HIP_TRY(hipMemcpyAsync(d_perm, lab.data(), used, hipMemcpyHostToDevice, c->stream));
+    const int t0 = it0 + skip;
+    DSM_TRY(k_rb_tau(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(t0 + 1) * V), c->tau_fixed_trace ? 0 : V,
+                     c->gamma_trace + (size_t)t0 * sg, c->eta_trace + (size_t)t0 * 16, d_perm, B * L, L, d_bs, d_sum, d_bsq, d_dead));
+    unsigned long long nd = 0;
+    if (sum) HIP_TRY(hipMemcpyAsync(sum, d_sum, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (bsq) HIP_TRY(hipMemcpyAsync(bsq, d_bsq, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&nd, d_dead, sizeof nd, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (dead) *dead = (long long)nd;
+    return DSM_OK;
+}
+
 // test hook: which instantiation of the fit kernel, and which grid, a call over n_it iterations would launch (nothing is launched)
 extern "C" int dsm_fit_debug_path(dsm_ctx *c, int n_it, int out[5])
 {

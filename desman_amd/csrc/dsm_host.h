@@ -293,6 +293,11 @@ int k_held_sweep(dsm_ctx *c, int n_held, const double *gamma, const double *eta,
 // every tau RNG mode; the changed digits are added to *c->nchange
 int k_pair_sweep(dsm_ctx *c, const double *gamma, const double *eta, uint32_t iter);
 
+// ---- launcher (kernels_rbtau.hip): the full conditionals of tau over n_it >= 1 stored iterations in batches of L (n_it a multiple of L),
+// d_perm [n_it][G] labels, trace_stride as below; d_sum / d_bsq / *d_dead zeroed by the caller, d_bs scratch of d_sum's size
+int k_rb_tau(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const double *gamma, const double *eta, const uint8_t *d_perm, int n_it,
+             int L, double *d_bs, double *d_sum, double *d_bsq, unsigned long long *d_dead);
+
 // ---- the 4^G joint states of a position as assign_kernel and pred_kernel walk them (kernels_assign.hip): the GO outer haplotypes are
 // NB = 4^GO blocks of 64 states, cut into P = min(NB, 64) partials of bpp consecutive blocks, one wavefront each.  P depends on G only.
 struct JointSplit {

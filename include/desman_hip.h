@@ -348,6 +348,31 @@ int dsm_fit_debug_path(dsm_ctx *ctx, int n_it, int out[5]);
  * exceeds the trace's length (0 before any update or dsm_ctx_debug_set_trace).                                                      */
 int dsm_ctx_debug_set_param_trace(dsm_ctx *ctx, const double *gamma /*[n][S][G]*/, const double *eta /*[n][16]*/, int n);
 
+/* Rao-Blackwellised marginals of tau for the positions of the fit (desman_amd/marginals.py): one device pass over
+ * the resident counts and the tau, gamma and eta traces.  Iteration numbering, and which (tau_t, gamma_t, eta_t) belongs to iteration t,
+ * are those of dsm_ctx_trace_fit_stats.  For a stored iteration t, a position v and a haplotype g
+ *     rest[s][b] = fma chain from 0 over h != g, h ascending, of eta_t[tau_t[v][h]][b] * gamma_t[s][h]          (G = 1: 0)
+ *     L_a        = sum over s, b with x[v][s][b] > 0 of x ln(rest[s][b] + eta_t[a][b] gamma_t[s][g]),  a = 0..3   (x exact in fp64; a zero
+ *                  count adds 0; p = 0 under a positive count makes L_a = -inf)
+ *     q_a        = exp(L_a - max) / (((e_0 + e_1) + e_2) + e_3)
+ * is the exact full conditional of tau_vg; where all four L_a are -inf, q is the one-hot of the current base tau_t[v][g] and the
+ * cell-iteration is counted in *dead.  Nothing is ever NaN for a finite, non-negative trace.  No random number is drawn.
+ * Range, perm (validation of skipped rows included) and the batch rule are those of dsm_ctx_trace_batch_stats: L = batch_len,
+ * B = 2 floor(n_it / (2 L)) batches, only the LAST B L iterations are used.  With l = perm[t][g]:
+ *     sum  [V][G][4] double   sum over the batches, ascending, of the batch sums; a batch sum is the sum of q from 0 over the batch's
+ *                             iterations, t ascending
+ *     bsq  [V][G][4] double   sum over the batches, ascending, of (batch sum)^2
+ *     dead [1]                cell-iterations without a live base
+ * One order of summation per cell, no floating-point atomics: the same bits from call to call and for any grid.  Any output pointer may
+ * be NULL.  n_it = 0 succeeds and writes zeros.  DSM_ERR_STATE when no update has run; DSM_ERR_ARG for a range outside the trace,
+ * batch_len < 1, 0 < n_it < 2 batch_len, a perm row that is no permutation.  After dsm_ctx_gibbs_update_fixed_tau every iteration is
+ * the held tau.  The chain state, both RNG streams, every trace and the MAP record are only read.  Limits: one context,
+ * 1 <= G <= DSM_MAX_G, S <= DSM_MAX_S (DSM_ERR_UNSUPPORTED beyond).
+ *   dsm_rbtau_debug_path: test hook, out = {lanes per position, sample slots per lane} of the kernel instantiation for S samples.   */
+int dsm_ctx_trace_rb_marginals(dsm_ctx *ctx, const uint8_t *perm /*[n_it][G] or NULL*/, int it0, int n_it, int batch_len,
+                               double *sum /*[V][G][4]*/, double *bsq /*[V][G][4]*/, long long *dead /*[1]*/);
+int dsm_rbtau_debug_path(int S, int G, int out[2]);
+
 /* A8-A12: Init_NMFT (desman/Init_NMFT.py).  F is derived from the resident
  * counts (:49-60).  tau [4V][G] row v + a*V, gamma [G][S] as in the reference.
  * Every shape up to S = DSM_MAX_S, G = DSM_MAX_G has a kernel (tests/test_gpu_nmft_forms.py
