@@ -23,7 +23,7 @@ _u64p = np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")
 def build(force=False):
     if os.environ.get("DESMAN_ORACLE_SO"):          # e.g. the sanitizer build (`make -C oracle asan-test`)
         return os.environ["DESMAN_ORACLE_SO"]
-    srcs = [os.path.join(_HERE, f) for f in ("desman_oracle.c", "stats_agg.c", "orc_log_table.h")]
+    srcs = [os.path.join(_HERE, f) for f in ("desman_oracle.c", "stats_agg.c", "orc_log_table.h", "orc_mt.h")]
     if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(f) for f in srcs):
         subprocess.check_call(["make", "-C", _HERE, "-s"] + (["-B"] if force else []))
     return _SO
@@ -140,6 +140,82 @@ def freeRNG():
 def sample_tau(tau, pi, eta, variants):
     V, G, _ = tau.shape
     return lib().orc_sample_tau(tau, pi, eta, variants, V, G, pi.shape[0])
+
+
+# the reference tree: present in the development container only (tests/golden/make_golden.py reads it there too)
+REFERENCE_DIR = os.environ.get("DESMAN_REFERENCE_DIR", "/root/reference")
+_REF_SO = os.path.join(_HERE, "_ref", "libref_sampletau.so")
+
+
+class RefSampleTau:
+    """The reference's OWN sweep: sampletau/c_sample_tau.c compiled unmodified into oracle/_ref/libref_sampletau.so (oracle/Makefile:
+    ref), its five GSL generator calls forwarded to the oracle's MT19937 (oracle/gsl_shim).  The four entry points keep the reference's
+    names and arguments.  The library is built here when the reference tree is present (a failed build raises); where the tree is absent
+    -- the GPU machine -- a library built earlier is loaded as it is.
+
+    The generator is process-global inside the library (`static gsl_rng *`, c_sample_tau.c:24) and the file checks nothing: c_setRNG or
+    c_sample_tau before c_initRNG, or after c_freeRNG, dereference a wild pointer.  This wrapper refuses those calls instead."""
+    _L = None
+    _live = False
+
+    @staticmethod
+    def why_unavailable():
+        """None when the library can be had (it exists, or the reference tree to build it from does), else the reason -- the only case in
+        which a test may skip.  With either one present a missing or failed build is an error of the constructor, not a skip."""
+        if os.path.exists(_REF_SO) or os.path.isfile(os.path.join(REFERENCE_DIR, "sampletau", "c_sample_tau.c")):
+            return None
+        return ("both missing: oracle/_ref/libref_sampletau.so is not built, and the reference tree it is built from (%s; "
+                "DESMAN_REFERENCE_DIR) is absent" % REFERENCE_DIR)
+
+    @staticmethod
+    def build():
+        """`make -C oracle ref` when the reference tree is present; returns the library's path"""
+        if os.path.isfile(os.path.join(REFERENCE_DIR, "sampletau", "c_sample_tau.c")):
+            build()                                              # liboracle.so holds the generator behind the stand-in
+            subprocess.check_call(["make", "-C", _HERE, "-s", "ref", "REF=" + REFERENCE_DIR])
+        if not os.path.exists(_REF_SO):
+            raise RuntimeError(RefSampleTau.why_unavailable() or "oracle/_ref/libref_sampletau.so: `make ref` left no library")
+        return _REF_SO
+
+    def __init__(self):
+        cls = RefSampleTau
+        if cls._L is None:
+            lib()                                                # resolve liboracle.so first: the one the tests compare against
+            L = C.CDLL(cls.build())
+            L.c_initRNG.argtypes, L.c_initRNG.restype = [], None
+            L.c_setRNG.argtypes, L.c_setRNG.restype = [C.c_ulong], None
+            L.c_freeRNG.argtypes, L.c_freeRNG.restype = [], None
+            L.c_sample_tau.argtypes = [_i64p, _f64p, _f64p, _i64p, C.c_int, C.c_int, C.c_int]     # `long` is 64 bits on LP64
+            L.c_sample_tau.restype = C.c_int
+            assert C.sizeof(C.c_long) == 8, "c_sample_tau takes `long *`: an LP64 platform is assumed"
+            cls._L = L
+
+    def c_initRNG(self):
+        if RefSampleTau._live:                                   # the reference would leak the first generator: free it
+            self.c_freeRNG()
+        RefSampleTau._L.c_initRNG()
+        RefSampleTau._live = True
+
+    def c_setRNG(self, seed):
+        if not RefSampleTau._live:
+            raise RuntimeError("c_setRNG before c_initRNG: the reference dereferences a null pointer here")
+        RefSampleTau._L.c_setRNG(int(seed))
+
+    def c_freeRNG(self):
+        if RefSampleTau._live:
+            RefSampleTau._L.c_freeRNG()
+            RefSampleTau._live = False
+
+    def c_sample_tau(self, tau, pi, eta, variants, V=None, G=None, S=None):
+        """in place on tau [V,G,4] int64; returns nchange.  V, G, S default to the arrays' shapes"""
+        if not RefSampleTau._live:
+            raise RuntimeError("c_sample_tau without a live generator: the reference dereferences a wild pointer here")
+        V = tau.shape[0] if V is None else V
+        G = tau.shape[1] if G is None else G
+        S = pi.shape[0] if S is None else S
+        if tau.size != V * G * 4 or pi.size != S * G or eta.size != 16 or variants.size != V * S * 4:
+            raise ValueError("c_sample_tau: array sizes do not match V, G, S (the reference checks nothing)")
+        return RefSampleTau._L.c_sample_tau(tau, pi, eta, variants, int(V), int(G), int(S))
 
 
 def loglik(tau_idx, gamma, eta, variants):

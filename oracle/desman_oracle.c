@@ -14,9 +14,12 @@
  *     own pure-Python sampler (desman/HaploSNP_Sampler.py:148-183) through
  *     tests/golden/tau_sweep_*.npz; the uniform stream is the published
  *     MT19937 (GSL gsl_rng_mt19937: genrand_int32()/2^32, seed 0 -> 4357) and
- *     is pinned against numpy's legacy MT19937 raw stream.  The reference's
- *     sampletau/c_sample_tau.c itself is UNBUILDABLE in this image (it needs
- *     the GSL headers/library, which are absent, and no stand-in is written).
+ *     is pinned against numpy's legacy MT19937 raw stream.  The sweep itself
+ *     (orc_sample_tau_u / orc_sample_tau and the global generator's calls) is
+ *     pinned, exactly, against the reference's own sampletau/c_sample_tau.c
+ *     compiled unmodified into oracle/_ref (oracle/Makefile: ref; GSL's
+ *     generator calls forwarded to orc_mt by oracle/gsl_shim):
+ *     tests/test_ref_sweep_cpu.py.
  *   - log-likelihood / log-posterior / NMFT / get_tau: pinned against the
  *     imported Python reference through the tests/golden fixtures.
  *
@@ -33,10 +36,7 @@
 /* unpinned system library; algorithm = Matsumoto & Nishimura 2002 version). */
 /* Used by the reference at sampletau/c_sample_tau.c:26-45 and :174.         */
 /* ------------------------------------------------------------------------ */
-typedef struct {
-    uint32_t mt[624];
-    int pos;
-} orc_mt;
+#include "orc_mt.h"      /* orc_mt: shared with gsl_shim/shim_rng.c, which serves the reference's own sweep */
 
 void orc_mt_seed(orc_mt *r, unsigned long seed)
 {
