@@ -562,6 +562,22 @@ class HaploSNP_Sampler:
         f = self._fit
         return (f["sample"], f["position"], f["cell"]) if cells else (f["sample"], f["position"])
 
+    def fitReplicates(self, reps=_check.REPS, stride=None, salt=0):
+        """(per-sample table, per-position table) of posterior predictive p-values from ``reps`` replicate tables per used iteration
+        (every ``stride``-th stored one; default: about check.N_USE of them): each a dict of T_obs, T_rep, T_rep_sd, p and p_mcse
+        (check.ppp_table), the positions' also q, the Benjamini-Hochberg q-value over positions.  Invariant to the haplotype labels."""
+        if reps < 1:
+            raise ValueError("fitReplicates: at least 1 replicate is needed; got %d" % reps)
+        stride = _check.default_stride(self.max_iter) if stride is None else int(stride)
+        if stride < 1:
+            raise ValueError("fitReplicates: the stride must be at least 1; got %d" % stride)
+        ctx = self._trace_ctx()
+        calls, _ = _check.ppp_batches(self.max_iter, stride)
+        parts = [(ctx.trace_ppc(reps, it0=it0, n_it=n_it, stride=stride, salt=salt), counted) for it0, n_it, counted in calls]
+        samples, positions = _check.ppp_table(parts, "sample"), _check.ppp_table(parts, "position")
+        positions["q"] = _check.bh_qvalues(positions["p"])
+        return samples, positions
+
     # ---- position-marginal predictive density of the last update() (desman_amd/predictive.py, DESIGN.md sec. 8h)
     def predictive(self, n_use=_predictive.N_USE, counts=None):
         """The pointwise table (predictive.pointwise: lppd, p_waic, elpd_waic per position) of about ``n_use`` evenly spaced stored

@@ -284,6 +284,24 @@ class Output_Results:
         logging.info("Fit_samples.csv / Fit_positions.csv written: %d of %d samples and %d of %d positions have z > %g"
                      % (check.flagged(samples), len(samples["z"]), check.flagged(positions), len(positions["z"]), check.Z_HIGH))
 
+    def output_Fit_ppp(self, samples, positions):
+        """Fit_samples_ppp.csv: sample, T_obs, T_rep, T_rep_sd, p, p_mcse; Fit_positions_ppp.csv: Contig, Position, the same columns and q
+        (keyed as Fit_samples.csv / Fit_positions.csv); and one log line (check.ppp_summary)"""
+        from . import check
+        frame = pd.DataFrame({col: samples[col] for col in check.PPP_COLUMNS}, index=self._kept_sample_names())
+        frame.index.name = "sample"
+        frame.to_csv(self._path("Fit_samples_ppp.csv"))
+        cols = {"Position": self.filtered_position}
+        cols.update({col: positions[col] for col in check.PPP_COLUMNS + ("q",)})
+        frame = pd.DataFrame(cols, index=self.filtered_contig_names)
+        frame.index.name = "Contig"
+        frame.to_csv(self._path("Fit_positions_ppp.csv"))
+        s = check.ppp_summary(samples, positions)
+        logging.info("Fit_samples_ppp.csv / Fit_positions_ppp.csv written: %d of %d samples and %d of %d positions have p < %g (a model "
+                     "that fits expects at most %.2g and %.2g); %d positions have q < %g"
+                     % (s["samples_low"], s["samples"], s["positions_low"], s["positions"], check.P_LOW, s["samples_expected"],
+                        s["positions_expected"], s["positions_q"], check.Q_LOW))
+
     def output_Fit_cells(self, cell):
         """Fit_cells.csv: V x S, the posterior mean of Pearson's X per cell; rows keyed as Tau_Mean.csv's, one column per sample"""
         frame = pd.DataFrame(np.asarray(cell), index=self.filtered_contig_names, columns=self._kept_sample_names())

@@ -123,6 +123,10 @@ SIGNATURES = {
     "dsm_ctx_trace_fit_stats": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "dsm_fit_debug_set_parts": (_i, [_i]),
     "dsm_fit_debug_path": (_i, [_vp, _i, C.POINTER(_i)]),
+    "dsm_ctx_trace_ppc": (_i, [_vp, _i, _i, _i, _i, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dsm_ppc_debug_set_parts": (_i, [_i]),
+    "dsm_ppc_debug_set_chunk": (_i, [_i, _i]),
+    "dsm_ppc_debug_path": (_i, [_vp, _i, _i, C.POINTER(_i)]),
     "dsm_ctx_debug_set_param_trace": (_i, [_vp, _vp, _vp, _i]),
     "dsm_ctx_trace_rb_marginals": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, C.POINTER(C.c_longlong)]),
     "dsm_rbtau_debug_path": (_i, [_i, _i, C.POINTER(_i)]),
@@ -389,7 +393,19 @@ def fit_debug_set_parts(parts=0):
     check(load().dsm_fit_debug_set_parts(int(parts)))
 
 
-FIT_MAX_ITER, FIT_TOL = 20000, 1.0e-9     # defaults of fit_gamma: plain EM is slow near the boundary
+def ppc_debug_set_parts(parts=0):
+    """test hook: the parts a launch of Context.trace_ppc splits its iterations into across workgroups (0 = the library's own choice);
+    no result depends on it"""
+    check(load().dsm_ppc_debug_set_parts(int(parts)))
+
+
+def ppc_debug_set_chunk(iterations=0, replicates=0):
+    """test hook: the iterations and replicates per launch of Context.trace_ppc (0 = by the library's scratch bound); no result depends
+    on them"""
+    check(load().dsm_ppc_debug_set_chunk(int(iterations), int(replicates)))
+
+
+FIT_MAX_ITER, FIT_TOL = 20000, 1.0e-9    # defaults of fit_gamma: plain EM is slow near the boundary (DESIGN.md sec. 8b)
 
 
 def _fit_tau(tau, V):
@@ -1026,6 +1042,35 @@ class Context:
                                                 _ptr(out.get("var")), _ptr(out.get("logz_it"))))
         out["n_used"] = n_used
         return out
+
+    def trace_ppc(self, R, it0=0, n_it=None, stride=1, salt=0, want=("ge_sample", "ge_position", "rep_sample", "rep_position",
+                                                                     "obs_sample", "obs_position")):
+        """Posterior predictive p-values from R replicate tables per used iteration it0, it0 + stride, ... below it0 + n_it (include/
+        desman_hip.h: dsm_ctx_trace_ppc; desman_amd/check.py): a dict of ge_sample [S] and ge_position [V] (int64: the (t, r) with
+        T_rep >= T_obs), rep_sample [S, 2] and rep_position [V, 2] (the sums of T_rep and T_rep^2 over (t, r)), obs_sample [S] and
+        obs_position [V] (the sum of T_obs over t); only those named in ``want`` are allocated and fetched.  n_used and R are in the
+        dict; p = ge / (n_used R)."""
+        n_it = self.n_trace - int(it0) if n_it is None else int(n_it)
+        stride, R = int(stride), int(R)
+        shapes = dict(ge_sample=(self.S,), ge_position=(self.V,), rep_sample=(self.S, 2), rep_position=(self.V, 2),
+                      obs_sample=(self.S,), obs_position=(self.V,))
+        bad = [k for k in want if k not in shapes]
+        if bad:
+            raise ValueError("trace_ppc: unknown output %r (%s)" % (bad[0], ", ".join(shapes)))
+        out = {k: np.zeros(shapes[k], dtype=np.int64 if k.startswith("ge_") else np.float64) for k in shapes if k in want}
+        check(self.lib.dsm_ctx_trace_ppc(self._h, int(it0), n_it, stride, R, C.c_uint64(int(salt) & 0xFFFFFFFFFFFFFFFF),
+                                         *(_ptr(out.get(k)) for k in shapes)))
+        out["n_used"] = -(-n_it // stride) if stride >= 1 and n_it > 0 else 0
+        out["R"] = R
+        return out
+
+    def ppc_debug_path(self, n_used=None, R=1):
+        """test hook: what trace_ppc over n_used used iterations (default: the whole trace) and R replicates would launch: dict of nsl
+        (the kernel's instantiation: sample slots per lane), lpv, gc, tiles, parts, ct and cr (iterations and replicates per launch) and
+        C (cells of up to C reads are drawn read by read)"""
+        out = (_i * 8)()
+        check(self.lib.dsm_ppc_debug_path(self._h, int(self.n_trace if n_used is None else n_used), int(R), out))
+        return dict(zip(("nsl", "lpv", "gc", "tiles", "parts", "ct", "cr", "C"), (int(x) for x in out)))
 
     def fit_debug_path(self, n_it=None):
         """test hook: what trace_fit_stats over n_it iterations (default: the whole trace) would launch: dict of nsl (the kernel's

@@ -111,3 +111,77 @@ def fit_scores(sums, n_it, counts):
 def flagged(scores):
     """the number of rows of a fit_scores table with z > Z_HIGH"""
     return int((scores["z"] > Z_HIGH).sum())
+
+
+# ---- posterior predictive p-values from replicate tables (DESIGN.md sec. 8k; _lib.Context.trace_ppc)
+REPS = 20             # replicates per used iteration of a bare `--check-reps`: a convention, not tuned
+N_USE = 50            # about this many evenly spaced stored iterations are used unless --check-stride says otherwise (as --predictive)
+P_LOW = 0.01          # the thresholds of the one summary line `desman --check --check-reps` logs: conventions
+Q_LOW = 0.1
+PPP_COLUMNS = ("T_obs", "T_rep", "T_rep_sd", "p", "p_mcse")
+
+
+def default_stride(n_stored, n_use=N_USE):
+    """the stride that uses about n_use of n_stored iterations"""
+    return max(1, int(n_stored) // int(n_use))
+
+
+def bh_qvalues(p):
+    """Benjamini-Hochberg q-values of the p-values p [n]: q_(i) = min over j >= i of n p_(j) / j in ascending order of p, at most 1;
+    NaN stays NaN and does not count"""
+    p = np.asarray(p, dtype=np.float64)
+    q = np.full(p.shape, np.nan)
+    ok = np.flatnonzero(~np.isnan(p))
+    n = ok.size
+    if n == 0:
+        return q
+    order = ok[np.argsort(p[ok], kind="stable")]
+    scaled = p[order] * n / np.arange(1, n + 1)
+    q[order] = np.minimum(np.minimum.accumulate(scaled[::-1])[::-1], 1.0)
+    return q
+
+
+def ppp_batches(n_stored, stride):
+    """The used iterations 0, stride, ... below n_stored cut for the batch-means error of a p-value (diagnose.batch_range over the used
+    iterations, L = floor(sqrt(n_used))): a list of (it0, n_it, counts) -- one trace_ppc call each, `counts` false for the iterations before
+    the first batch -- and B.  The calls together use every used iteration once."""
+    from . import diagnose
+    n_used = -(-int(n_stored) // int(stride)) if n_stored > 0 else 0
+    L = diagnose.default_batch_len(n_used)
+    B, N, skip = diagnose.batch_range(n_used, L)
+    calls = []
+    if skip > 0:
+        calls.append((0, min(n_stored, skip * stride), False))
+    for b in range(B):
+        k0 = skip + b * L
+        calls.append((k0 * stride, min(n_stored - k0 * stride, L * stride), True))
+    return calls, B
+
+
+def ppp_table(parts, kind):
+    """From the trace_ppc results of the calls of ppp_batches, ``parts`` = [(result, counts)], for kind = "sample" or "position": dict of
+    T_obs, T_rep (means over t and over (t, r)), T_rep_sd, p = ge / (n_used R) and p_mcse (the standard error of the mean of the B batch
+    p-values; NaN below two batches)"""
+    n = sum(r["n_used"] * r["R"] for r, _ in parts)
+    n_t = sum(r["n_used"] for r, _ in parts)
+    ge = sum(np.asarray(r["ge_" + kind], dtype=np.float64) for r, _ in parts)
+    rep = sum(np.asarray(r["rep_" + kind], dtype=np.float64) for r, _ in parts)
+    obs = sum(np.asarray(r["obs_" + kind], dtype=np.float64) for r, _ in parts)
+    if n < 1:
+        nan = np.full(ge.shape, np.nan)
+        return dict(T_obs=nan, T_rep=nan.copy(), T_rep_sd=nan.copy(), p=nan.copy(), p_mcse=nan.copy())
+    mean = rep[:, 0] / n
+    with np.errstate(invalid="ignore"):
+        sd = np.sqrt(np.maximum(rep[:, 1] / n - mean * mean, 0.0))
+    bp = np.array([np.asarray(r["ge_" + kind], dtype=np.float64) / (r["n_used"] * r["R"]) for r, c in parts if c and r["n_used"] > 0])
+    mcse = bp.std(axis=0, ddof=1) / np.sqrt(bp.shape[0]) if bp.shape[0] >= 2 else np.full(ge.shape, np.nan)
+    return dict(T_obs=obs / n_t, T_rep=mean, T_rep_sd=sd, p=ge / n, p_mcse=mcse)
+
+
+def ppp_summary(samples, positions):
+    """what the one log line of `desman --check --check-reps` says: the samples and positions with p < P_LOW against the number a
+    well-specified model expects at most (P_LOW times their number: posterior predictive p-values are conservative), and the positions
+    with q < Q_LOW"""
+    return dict(samples_low=int((samples["p"] < P_LOW).sum()), samples=len(samples["p"]), samples_expected=P_LOW * len(samples["p"]),
+                positions_low=int((positions["p"] < P_LOW).sum()), positions=len(positions["p"]),
+                positions_expected=P_LOW * len(positions["p"]), positions_q=int((positions["q"] < Q_LOW).sum()))

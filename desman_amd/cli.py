@@ -41,7 +41,9 @@ _FLAGS = [
 ]
 
 
-PAIR_MOVES = 5              # a bare --pair-moves: a pair pass after every fifth iteration -- the convention of `desman-assign --pairs`
+from .check import REPS as CHECK_REPS, N_USE as CHECK_N_USE        # a bare --check-reps; the used iterations --check-stride defaults to
+CHECK_MAX_REPS = 1024       # DSM_PPC_MAX_R (include/desman_hip.h)
+PAIR_MOVES = 5            # a bare --pair-moves: a pair pass after every fifth iteration -- the convention of `desman-assign --pairs`
 
 
 def build_parser():
@@ -70,7 +72,19 @@ def build_parser():
                     help="also write the posterior predictive fit of the stored iterations: Fit_samples.csv and Fit_positions.csv "
                          "(per sample / per position: non-empty cells, posterior mean of Pearson's X2, its expectation under the "
                          "model, the standardised discrepancy z and the deviance); a large z marks a sample or a position the "
-                         "haplotypes do not explain; z is a conservative score, not a p-value (extension)")
+                         "haplotypes do not explain; z is a conservative score, not a p-value: --check-reps gives one (extension)")
+    ap.add_argument('--check-reps', dest='check_reps', nargs='?', const=CHECK_REPS, default=None, type=int, metavar='R',
+                    help="with --check: also write posterior predictive p-values, Fit_samples_ppp.csv and Fit_positions_ppp.csv (per "
+                         "sample / per position: T_obs, the posterior mean of Pearson's X2 summed over the other index; T_rep and "
+                         "T_rep_sd, the same on R replicate tables drawn from the model at every used iteration (default %d: a "
+                         "convention, not tuned); p, the share of replicates at least as extreme as the data; p_mcse, its Monte Carlo "
+                         "standard error by batch means over iterations; for positions also q, the Benjamini-Hochberg q-value).  "
+                         "Unlike z, p is on a probability scale, and uniform when the parameters are known; at fitted parameters "
+                         "posterior predictive p-values are themselves conservative, because the data are used twice (extension)"
+                         % CHECK_REPS)
+    ap.add_argument('--check-stride', dest='check_stride', default=None, type=int, metavar='K',
+                    help="with --check-reps: use every K-th stored iteration (default: about %d evenly spaced ones, as --predictive "
+                         "does) (extension)" % CHECK_N_USE)
     ap.add_argument('--check-cells', dest='check_cells', action='store_true',
                     help="with --check: also write Fit_cells.csv, positions x samples, the posterior mean X2 of every cell (extension)")
     ap.add_argument('--predictive', nargs='?', const=50, default=None, type=int, metavar='N',
@@ -270,12 +284,23 @@ def _report_marginals(report, chain, L):
     report.output_Tau_marginals(chain.tauMarginals(L), relabelled=chain._diag_perm() is not None)
 
 
-def _check_options(opts):
-    """--check / --check-cells: refused here, before any chain, where they cannot be served"""
+def _check_options(opts, replicates=False):
+    """--check / --check-cells / --check-reps / --check-stride: refused here, before any chain, where they cannot be served"""
     if opts.check_cells and not opts.check:
         sys.exit("desman: --check-cells needs --check")
+    if opts.check_reps is not None and not opts.check:
+        sys.exit("desman: --check-reps needs --check")
+    if opts.check_stride is not None and opts.check_reps is None:
+        sys.exit("desman: --check-stride needs --check-reps")
     if opts.check and opts.no_iter is not None and opts.no_iter < 1:
         sys.exit("desman: --check: %d stored iterations (-i): at least 1 is needed" % opts.no_iter)
+    if opts.check_reps is not None:
+        if replicates:
+            sys.exit("desman: --check-reps is not available for replicate chains that share their launches: run the chains one by one")
+        if opts.check_reps < 1 or opts.check_reps > CHECK_MAX_REPS:
+            sys.exit("desman: --check-reps: 1 to %d replicates per iteration; got %d" % (CHECK_MAX_REPS, opts.check_reps))
+        if opts.check_stride is not None and opts.check_stride < 1:
+            sys.exit("desman: --check-stride: at least 1; got %d" % opts.check_stride)
 
 
 def _report_check(report, chain, cells):
@@ -285,6 +310,13 @@ def _report_check(report, chain, cells):
     report.output_Fit(fit[0], fit[1])
     if cells:
         report.output_Fit_cells(fit[2])
+
+
+def _report_check_reps(report, chain, reps, stride):
+    """--check --check-reps: posterior predictive p-values per sample and per position from replicate tables, next to the files of
+    --check (which do not change); p_b does not depend on the haplotype labels, so --relabel changes nothing here either"""
+    samples, positions = chain.fitReplicates(reps=reps, stride=stride)
+    report.output_Fit_ppp(samples, positions)
 
 
 def _predictive_options(opts, replicates=False):
@@ -406,6 +438,8 @@ def main(argv=None):
         _report_marginals(report, chain, marg_len)
     if opts.check:
         _report_check(report, chain, opts.check_cells)
+    if opts.check_reps is not None:
+        _report_check_reps(report, chain, opts.check_reps, opts.check_stride)
     if opts.predictive is not None:
         _report_predictive(report, flt, chain, opts.predictive, subsample)
     if subsample is not None:
@@ -431,7 +465,7 @@ def main_replicates(argv_list, on_chain=None):
         _pair_moves_options(opts, replicates=True)
         diag_len = _diagnose_batch_len(opts)
         marg_len = _marginals_batch_len(opts)
-        _check_options(opts)
+        _check_options(opts, replicates=True)
         _predictive_options(opts, replicates=True)
         report = Output_Results(opts.output_dir)
         table, flt, subsample = _load(opts, report)

@@ -1787,6 +1787,75 @@ extern "C" int dsm_fit_debug_path(dsm_ctx *c, int n_it, int out[5])
     return DSM_OK;
 }
 
+// posterior predictive p-values per sample and position from replicate tables drawn at the stored iterations (kernels_ppc.hip; DESIGN.md
+// sec. 8k): the counts and the three traces are read where they lie, the uniforms are the call's own, nothing of the chain is written
+static int ppc_args(dsm_ctx *c, const char *who, int it0, int n_it, int stride, int R)
+{
+    DSM_TRY(trace_range(c, who, it0, n_it));
+    if (stride < 1 || R < 1) { dsm_set_error("%s: stride=%d, R=%d: at least 1 is needed", who, stride, R); return DSM_ERR_ARG; }
+    if (R > DSM_PPC_MAX_R) { dsm_set_error("%s: R=%d above DSM_PPC_MAX_R=%d", who, R, DSM_PPC_MAX_R); return DSM_ERR_UNSUPPORTED; }
+    if ((long long)it0 + n_it > (1LL << 32) / DSM_PPC_MAX_R) {
+        dsm_set_error("%s: iteration %lld does not fit the counter word", who, (long long)it0 + n_it);
+        return DSM_ERR_UNSUPPORTED;
+    }
+    return DSM_OK;
+}
+
+extern "C" int dsm_ctx_trace_ppc(dsm_ctx *c, int it0, int n_it, int stride, int R, uint64_t salt, int64_t *ge_sample, int64_t *ge_position,
+                                 double *rep_sample, double *rep_position, double *obs_sample, double *obs_position)
+{
+    DSM_TRY(ppc_args(c, "trace_ppc", it0, n_it, stride, R));
+    const size_t V = (size_t)c->V, S = (size_t)c->S, sg = S * c->G;
+    const int n_used = (int)(((long long)n_it + stride - 1) / stride);
+    if (n_used == 0) {
+        if (ge_sample) std::fill(ge_sample, ge_sample + S, (int64_t)0);
+        if (ge_position) std::fill(ge_position, ge_position + V, (int64_t)0);
+        if (rep_sample) std::fill(rep_sample, rep_sample + S * 2, 0.0);
+        if (rep_position) std::fill(rep_position, rep_position + V * 2, 0.0);
+        if (obs_sample) std::fill(obs_sample, obs_sample + S, 0.0);
+        if (obs_position) std::fill(obs_position, obs_position + V, 0.0);
+        return DSM_OK;
+    }
+    PpcPlan pl;
+    DSM_TRY(ppc_plan(c, n_used, R, &pl));
+    BIND(c);
+    DevBuf<unsigned long long> d_ge_s, d_ge_v;
+    DevBuf<double> d_rep_s, d_rep_v, d_obs_s, d_obs_v;
+    DSM_TRY(d_ge_s.alloc(S)); DSM_TRY(d_ge_v.alloc(V));
+    DSM_TRY(d_rep_s.alloc(S * 2)); DSM_TRY(d_rep_v.alloc(V * 2));
+    DSM_TRY(d_obs_s.alloc(S)); DSM_TRY(d_obs_v.alloc(V));
+    HIP_TRY(hipMemsetAsync(d_ge_s, 0, S * sizeof(unsigned long long), c->stream));
+    HIP_TRY(hipMemsetAsync(d_ge_v, 0, V * sizeof(unsigned long long), c->stream));
+    HIP_TRY(hipMemsetAsync(d_rep_s, 0, S * 2 * sizeof(double), c->stream));
+    HIP_TRY(hipMemsetAsync(d_rep_v, 0, V * 2 * sizeof(double), c->stream));
+    HIP_TRY(hipMemsetAsync(d_obs_s, 0, S * sizeof(double), c->stream));
+    HIP_TRY(hipMemsetAsync(d_obs_v, 0, V * sizeof(double), c->stream));
+    const uint64_t key = c->ctr_seed ^ salt;
+    DSM_TRY(k_trace_ppc(c, pl, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it0 + 1) * V), c->tau_fixed_trace ? 0 : V,
+                        c->gamma_trace + (size_t)it0 * sg, c->eta_trace + (size_t)it0 * 16, it0, stride, n_used, R, (uint32_t)key,
+                        (uint32_t)(key >> 32), d_ge_s, d_ge_v, d_rep_s, d_rep_v, d_obs_s, d_obs_v));
+    if (ge_sample) HIP_TRY(hipMemcpyAsync(ge_sample, d_ge_s, S * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    if (ge_position) HIP_TRY(hipMemcpyAsync(ge_position, d_ge_v, V * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    if (rep_sample) HIP_TRY(hipMemcpyAsync(rep_sample, d_rep_s, S * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (rep_position) HIP_TRY(hipMemcpyAsync(rep_position, d_rep_v, V * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (obs_sample) HIP_TRY(hipMemcpyAsync(obs_sample, d_obs_s, S * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (obs_position) HIP_TRY(hipMemcpyAsync(obs_position, d_obs_v, V * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DSM_OK;
+}
+
+// test hook: which instantiation, chunks and grid a dsm_ctx_trace_ppc call would launch (nothing is launched)
+extern "C" int dsm_ppc_debug_path(dsm_ctx *c, int n_used, int R, int out[8])
+{
+    DSM_TRY(dsm_ctx_need(c, true, true));
+    if (!out || n_used < 1 || R < 1 || R > DSM_PPC_MAX_R) { dsm_set_error("ppc_debug_path: bad arguments"); return DSM_ERR_ARG; }
+    PpcPlan pl;
+    DSM_TRY(ppc_plan(c, n_used, R, &pl));
+    out[0] = pl.nsl; out[1] = pl.lpv; out[2] = pl.gc; out[3] = pl.tiles; out[4] = pl.parts; out[5] = pl.ct; out[6] = pl.cr;
+    out[7] = DSM_PPC_READS;
+    return DSM_OK;
+}
+
 // test hook: the first n rows of the gamma and eta traces (the companion of dsm_ctx_debug_set_trace, called after it)
 extern "C" int dsm_ctx_debug_set_param_trace(dsm_ctx *c, const double *gamma, const double *eta, int n)
 {

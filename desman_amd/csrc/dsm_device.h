@@ -14,6 +14,7 @@
 #define DSM_STREAM_ASMP  0x41534D50u   // 'ASMP'  dsm_assign_tau_sampled: chain c of a position draws from stream 'ASMP' + c
 #define DSM_STREAM_APAR  0x41504152u   // 'APAR'  dsm_assign_tau_sampled_pairs: the pair steps of chain c draw from stream 'APAR' + c
 #define DSM_STREAM_TPAR  0x54504152u   // 'TPAR'  pair moves of the Gibbs chain (kernels_pairtau.hip): the uniforms of the pair steps
+#define DSM_STREAM_PPCR  0x50504352u   // 'PPCR'  replicate tables of the posterior predictive p-values (kernels_ppc.hip)
 
 #define DSM_EPS 2.220446049250313e-16
 

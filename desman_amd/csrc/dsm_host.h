@@ -320,6 +320,14 @@ int k_trace_fit_stats(dsm_ctx *c, const FitPlan &pl, const uint64_t *trace, size
                       int n_it, double *d_samp_part, double *d_pos_part, double *d_cell_part, double *d_sample, double *d_position,
                       double *d_cell);
 
+// ---- launcher (kernels_ppc.hip): posterior predictive p-values from replicate tables over n_used stored iterations (the trace, gamma and
+// eta pointers are those of iteration it0; used iteration k is it0 + k stride); the six outputs are device buffers the launcher fills
+struct PpcPlan { int nsl, lpv, gc, tiles, parts, ct, cr; size_t lds; };   // as FitPlan, then the iterations and replicates per launch and its LDS bytes
+int ppc_plan(const dsm_ctx *c, int n_used, int R, PpcPlan *pl);
+int k_trace_ppc(dsm_ctx *c, const PpcPlan &pl, const uint64_t *trace, size_t trace_stride, const double *gamma, const double *eta, int it0,
+                int stride, int n_used, int R, uint32_t key0, uint32_t key1, unsigned long long *d_ge_s, unsigned long long *d_ge_v,
+                double *d_rep_s, double *d_rep_v, double *d_obs_s, double *d_obs_v);
+
 // ---- launchers (kernels_nmft.hip)
 int k_nmft_freq(dsm_ctx *c);
 int k_nmft_clamp(dsm_ctx *c);

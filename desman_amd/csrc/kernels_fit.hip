@@ -17,6 +17,7 @@
 
 #include "dsm_host.h"
 #include "dsm_host_util.h"
+#include "dsm_fit_cell.h"
 
 #define FIT_BLOCKS 2048         // workgroups a launch aims at (256 compute units x 8)
 #define FIT_LDS_GAMMA 4096      // doubles of LDS a chunk of gamma columns may take (32 KiB): the chunk is min(G, FIT_LDS_GAMMA / sample slots)
@@ -72,29 +73,7 @@ __global__ __launch_bounds__(256) void trace_fit_kernel(const FitParams p)
         const uint64_t word = vin ? p.trace[(size_t)t * p.trace_stride + (size_t)v] : 0ull;
         const double *gam_t = p.gamma + (size_t)t * sg;
         double m0[NSL], m1[NSL], m2[NSL], m3[NSL];
-#pragma unroll
-        for (int j = 0; j < NSL; ++j) { m0[j] = 0.0; m1[j] = 0.0; m2[j] = 0.0; m3[j] = 0.0; }
-        for (int g0 = 0; g0 < G; g0 += gc) {
-            const int gn = min(gc, G - g0);
-            __syncthreads();                                    // the readers of the previous chunk are done
-            for (int i = tid; i < gn * SP; i += 256) {
-                const int gg = i / SP, s = i - gg * SP;
-                lgam[i] = s < S ? gam_t[(size_t)s * G + g0 + gg] : 0.0;
-            }
-            if (g0 == 0 && tid < 16) leta[tid] = p.eta[(size_t)t * 16 + tid];
-            __syncthreads();
-            for (int gg = 0; gg < gn; ++gg) {
-                const int d = (int)(word >> (2 * (g0 + gg))) & 3;
-#pragma unroll
-                for (int j = 0; j < NSL; ++j) {
-                    const double ga = lgam[gg * SP + l + j * LPV];
-                    m0[j] += d == 0 ? ga : 0.0;
-                    m1[j] += d == 1 ? ga : 0.0;
-                    m2[j] += d == 2 ? ga : 0.0;
-                    m3[j] += d == 3 ? ga : 0.0;
-                }
-            }
-        }
+        fit_cell_mixture<NSL>(gam_t, p.eta + (size_t)t * 16, word, S, G, gc, p.lpv_log2, lgam, leta, m0, m1, m2, m3);      // (dsm_fit_cell.h)
 #pragma unroll
         for (int j = 0; j < NSL; ++j) {
             const int Ni = c0[j] + c1[j] + c2[j] + c3[j];
@@ -103,7 +82,7 @@ __global__ __launch_bounds__(256) void trace_fit_kernel(const FitParams p)
             int k = 0;
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
-                const double pb = ((m0[j] * leta[b] + m1[j] * leta[4 + b]) + m2[j] * leta[8 + b]) + m3[j] * leta[12 + b];
+                const double pb = fit_cell_p(m0[j], m1[j], m2[j], m3[j], leta, b);
                 const int ni = b == 0 ? c0[j] : (b == 1 ? c1[j] : (b == 2 ? c2[j] : c3[j]));     // (b is a constant after unrolling)
                 const double nb = (double)ni;
                 const bool pos = pb > 0.0, seen = ni > 0;

@@ -348,6 +348,57 @@ int dsm_fit_debug_path(dsm_ctx *ctx, int n_it, int out[5]);
  * exceeds the trace's length (0 before any update or dsm_ctx_debug_set_trace).                                                      */
 int dsm_ctx_debug_set_param_trace(dsm_ctx *ctx, const double *gamma /*[n][S][G]*/, const double *eta /*[n][16]*/, int n);
 
+/* Posterior predictive p-values of the chain per sample and per position from replicate tables (desman_amd/check.py):
+ * the realised-discrepancy check of Gelman, Meng and Stern (1996) with Pearson's X of dsm_ctx_trace_fit_stats as the discrepancy.
+ *
+ * Iterations.  The used iterations are t = it0, it0 + stride, ... below it0 + n_it: n_used = ceil(n_it / stride) of them.  Numbering, and
+ * the (tau_t, gamma_t, eta_t) that belongs to t, are those of dsm_ctx_trace_fit_stats.
+ * Cells.  For a used iteration t, a replicate r = 0 .. R - 1 and a cell (v, s) with counts x_b, N = sum_b x_b (an empty cell adds nothing
+ * anywhere) and p_b as dsm_ctx_trace_fit_stats forms it (one shared device function):
+ *     x_rep ~ Multinomial(N, p / sum_b p_b), by conditional binomials over the bases with p_b > 0 in ascending b, the last such base
+ *             taking the remainder (a base with p_b = 0 is never drawn; a cell without any such base has X_rep = 0)
+ *     X_obs = sum_{b: p_b > 0} (x_b - N p_b)^2 / (N p_b), +inf where some p_b = 0 < x_b;  X_rep the same formula on x_rep (finite)
+ * Discrepancies.  T_s(t) = sum_v X and T_v(t) = sum_s X, of the observed table and of every replicate, plain fp64 sums in ONE order that
+ * depends on S alone (not on parts, chunks or the grid), the same for T_obs and T_rep: with L = min(64, the power of two >= S) lanes per
+ * position, lane l adds its samples l, l + L, l + 2 L, ... in ascending order from 0, then the L lane sums meet by a butterfly
+ * (a_l += a_{l xor o} for o = L/2, L/4, ... 1); over positions, the 256 / L positions of a tile in ascending order from 0, then the tiles
+ * in ascending order from 0.  Sums over (t, r) are nested: over r ascending from 0 inside an iteration, then over t ascending from 0.
+ * Outputs (host pointers, any may be NULL):
+ *     ge_sample [S], ge_position [V]        int64    the number of (t, r) with T_rep >= T_obs(t); T_obs = +inf counts 0
+ *     rep_sample [S][2], rep_position [V][2] double  sum_{t,r} T_rep and sum_{t,r} T_rep^2
+ *     obs_sample [S], obs_position [V]       double  sum_t T_obs (column X of dsm_ctx_trace_fit_stats over the same iterations, up to the
+ *                                                    order of summation)
+ * The posterior predictive p-value is ge / (n_used R).
+ * Uniforms.  Counter based, from no stream the chain uses: the generator of (v, s, t, r) is xoshiro128+ seeded with the four words of
+ * Philox4x32-10(key = the chain's counter seed xor salt, as (lo32, hi32); counter = (lo32 j, hi32 j, t * DSM_PPC_MAX_R + r, 'PPCR')),
+ * j = v S + s (a block of all zeros: word 0 = 1), t the stored iteration's own number.  A cell's draw depends on (seed, salt, v, s, t, r)
+ * alone -- not on the tiling, the grid, parts, chunks, R, or which other iterations are used.  salt = 0: the chain's seed alone.
+ * Two draw paths, one law.  N <= DSM_PPC_READS: read by read, one 32-bit word w per read against integer thresholds by the rule of the
+ * mu/E pass's read loop: c_b = p_0 + .. + p_b added in ascending b from 0, th_b = sat_u32(floor(c_b * (2^32 / c_3))) for b = 0, 1, 2,
+ * n_b = #{w < th_b}, n_b = N for every b >= the last base with p_b > 0, and x_rep = (n_0, n_1 - n_0, n_2 - n_1, N - n_2).
+ * N > DSM_PPC_READS: three conditional binomials (rem, p_b : p_{b+1} + (.. + p_3)) by the sampler of the mu/E pass (inversion while the
+ * rarer outcome's mean is <= 128, BTRS above), the tails added from p_3 downwards.
+ * The chain, both RNG streams, every trace and the MAP record are only read.  n_it = 0 succeeds and writes zeros.  DSM_ERR_STATE when no
+ * update has run; DSM_ERR_ARG for a range outside the trace, stride < 1 or R < 1.  After dsm_ctx_gibbs_update_fixed_tau every iteration
+ * is the held tau.  Limits: one context, 1 <= G <= DSM_MAX_G, S <= DSM_MAX_S, R <= DSM_PPC_MAX_R, iterations below 2^32 / DSM_PPC_MAX_R
+ * (DSM_ERR_UNSUPPORTED beyond).  Scratch: at most DSM_PPC_SCRATCH_MB MiB for the per-tile sample sums of a launch (the iterations are
+ * cut into chunks, one iteration's replicates too where a single iteration exceeds it) + 40 bytes per position and chunk iteration. */
+#define DSM_PPC_MAX_R 1024
+#define DSM_PPC_READS 128
+#define DSM_PPC_SCRATCH_MB 256
+int dsm_ctx_trace_ppc(dsm_ctx *ctx, int it0, int n_it, int stride, int R, uint64_t salt,
+                      int64_t *ge_sample /*[S]*/, int64_t *ge_position /*[V]*/,
+                      double *rep_sample /*[S][2]*/, double *rep_position /*[V][2]*/,
+                      double *obs_sample /*[S]*/, double *obs_position /*[V]*/);
+/* test hooks: the parts a launch of the call above splits its iterations into across workgroups, and the iterations / replicates per
+ * launch (0 = the library's own choice, the default; fewer replicates than R per launch means one iteration per launch)             */
+int dsm_ppc_debug_set_parts(int parts);
+int dsm_ppc_debug_set_chunk(int iterations, int replicates);
+/* test hook: what the call above over n_used >= 1 used iterations and R replicates would launch on this context's table: out = {sample
+ * slots per lane (the kernel's instantiation: 1, 2, 4 or 8), lanes per position, haplotypes per staged chunk of gamma, tiles of
+ * positions, parts, iterations per launch, replicates per launch, DSM_PPC_READS}.  Nothing is launched.  Needs counts and a state.    */
+int dsm_ppc_debug_path(dsm_ctx *ctx, int n_used, int R, int out[8]);
+
 /* Rao-Blackwellised marginals of tau for the positions of the fit (desman_amd/marginals.py): one device pass over
  * the resident counts and the tau, gamma and eta traces.  Iteration numbering, and which (tau_t, gamma_t, eta_t) belongs to iteration t,
  * are those of dsm_ctx_trace_fit_stats.  For a stored iteration t, a position v and a haplotype g
