@@ -935,11 +935,33 @@ class Context:
         check(self.lib.dsm_ctx_get_tau_at(self._h, int(it), out))
         return out
 
-    # ---- reductions of the resident tau trace (include/desman_hip.h: dsm_ctx_trace_snd; desman_amd/relabel.py)
+    # ---- reductions of the resident traces (include/desman_hip.h: dsm_ctx_trace_snd and below; csrc/api_trace.hip)
+    def _trace_n_it(self, it0, n_it):
+        """n_it, or the iterations from it0 to the end of the trace"""
+        return self.n_trace - int(it0) if n_it is None else int(n_it)
+
+    def _trace_perm(self, who, perm, n_it=None):
+        """perm as uint8 [n_it, G] labels (n_it None: any number of rows)"""
+        p = np.ascontiguousarray(perm, dtype=np.uint8)
+        fits = p.ndim == 2 and p.shape[1] == self.G and (n_it is None or p.shape[0] == max(n_it, 0))
+        if not fits or not np.array_equal(p, np.asarray(perm)):
+            raise ValueError("%s: perm must be [n_it%s, G=%d] labels 0..G-1" % (who, "" if n_it is None else "=%d" % n_it, self.G))
+        return p
+
+    @staticmethod
+    def _trace_outputs(who, want, shapes, dtypes=None, strict=True):
+        """the outputs of ``shapes`` (name -> shape, in the order of the C arguments) that ``want`` names as zeroed arrays, and one
+        pointer per name of ``shapes`` (null: not fetched); strict: a name that ``shapes`` does not have is a ValueError"""
+        bad = [k for k in want if k not in shapes]
+        if bad and strict:
+            raise ValueError("%s: unknown output %r (%s)" % (who, bad[0], ", ".join(shapes)))
+        out = {k: np.zeros(shapes[k], dtype=(dtypes or {}).get(k, np.float64)) for k in shapes if k in want}
+        return out, [_ptr(out.get(k)) for k in shapes]
+
     def trace_snd(self, mode=SND_STAR, ref=None, it0=0, n_it=None):
         """snd [n_it, G, Gr] int32: in how many positions haplotype g of stored iteration t differs from haplotype h of the reference --
         SND_STAR: the MAP record's tau; SND_SELF: the iteration itself; SND_GIVEN: ``ref`` ([V,Gr] digits or [V,Gr,4] one-hot)"""
-        n_it = self.n_trace - int(it0) if n_it is None else int(n_it)
+        n_it = self._trace_n_it(it0, n_it)
         r, Gr = None, self.G
         if mode == SND_GIVEN:
             r = _fit_tau(ref, self.V)
@@ -950,9 +972,7 @@ class Context:
 
     def get_tau_sum_perm(self, perm, it0=0):
         """get_tau_sum() over the iterations it0 .. it0 + len(perm) - 1 with iteration t's haplotype g counted as label perm[t, g]"""
-        p = np.ascontiguousarray(perm, dtype=np.uint8)
-        if p.ndim != 2 or p.shape[1] != self.G or not np.array_equal(p, np.asarray(perm)):
-            raise ValueError("get_tau_sum_perm: perm must be [n_it, G=%d] labels 0..G-1" % self.G)
+        p = self._trace_perm("get_tau_sum_perm", perm)
         out = np.zeros((self.V, self.G, 4), dtype=np.int64)
         check(self.lib.dsm_ctx_get_tau_sum_perm(self._h, _ptr(p), int(it0), p.shape[0], _ptr(out)))
         return out
@@ -962,18 +982,13 @@ class Context:
         desman_amd/diagnose.py): with L = batch_len, B = 2 (n_it // (2 L)) and N = B L, over the LAST N of the iterations
         it0 .. it0 + n_it - 1 under the labels of ``perm`` ([n_it, G], rows counted from it0; None = identity) a dict of
         sum, first, bsq [V, G, 4] int64 and flips [V, G] int32 (those named in ``want``; the others are not fetched), B, N and L"""
-        n_it = self.n_trace - int(it0) if n_it is None else int(n_it)
+        n_it = self._trace_n_it(it0, n_it)
         L = int(batch_len)
-        p = None
-        if perm is not None:
-            p = np.ascontiguousarray(perm, dtype=np.uint8)
-            if p.ndim != 2 or p.shape != (max(n_it, 0), self.G) or not np.array_equal(p, np.asarray(perm)):
-                raise ValueError("trace_batch_stats: perm must be [n_it=%d, G=%d] labels 0..G-1" % (n_it, self.G))
-        out = {k: np.zeros((self.V, self.G, 4), dtype=np.int64) for k in ("sum", "first", "bsq") if k in want}
-        if "flips" in want:
-            out["flips"] = np.zeros((self.V, self.G), dtype=np.int32)
-        check(self.lib.dsm_ctx_trace_batch_stats(self._h, _ptr(p), int(it0), n_it, L, _ptr(out.get("sum")), _ptr(out.get("first")),
-                                                 _ptr(out.get("bsq")), _ptr(out.get("flips"))))
+        p = perm if perm is None else self._trace_perm("trace_batch_stats", perm, n_it)
+        vg4 = (self.V, self.G, 4)
+        out, ptrs = self._trace_outputs("trace_batch_stats", want, dict(sum=vg4, first=vg4, bsq=vg4, flips=(self.V, self.G)),
+                                        dict(sum=np.int64, first=np.int64, bsq=np.int64, flips=np.int32), strict=False)
+        check(self.lib.dsm_ctx_trace_batch_stats(self._h, _ptr(p), int(it0), n_it, L, *ptrs))
         B = 2 * (n_it // (2 * L))
         out.update(B=B, N=B * L, L=L)
         return out
@@ -983,14 +998,9 @@ class Context:
         dsm_ctx_trace_fit_stats; desman_amd/check.py): a dict of sample [S, 4] and position [V, 4] -- the sums of (X, D, E, W) over the
         iterations and the other index -- and cell [V, S], the sum of X over the iterations; only those named in ``want`` are
         allocated and fetched.  n_it is in the dict."""
-        n_it = self.n_trace - int(it0) if n_it is None else int(n_it)
-        shapes = dict(sample=(self.S, 4), position=(self.V, 4), cell=(self.V, self.S))
-        bad = [k for k in want if k not in shapes]
-        if bad:
-            raise ValueError("trace_fit_stats: unknown output %r (sample, position, cell)" % bad[0])
-        out = {k: np.zeros(shapes[k]) for k in shapes if k in want}
-        check(self.lib.dsm_ctx_trace_fit_stats(self._h, int(it0), n_it, _ptr(out.get("sample")), _ptr(out.get("position")),
-                                               _ptr(out.get("cell"))))
+        n_it = self._trace_n_it(it0, n_it)
+        out, ptrs = self._trace_outputs("trace_fit_stats", want, dict(sample=(self.S, 4), position=(self.V, 4), cell=(self.V, self.S)))
+        check(self.lib.dsm_ctx_trace_fit_stats(self._h, int(it0), n_it, *ptrs))
         out["n_it"] = n_it
         return out
 
@@ -999,20 +1009,13 @@ class Context:
         desman_amd/marginals.py): the full conditional q of every tau[v][g] under (tau_t, gamma_t, eta_t), over the LAST N = B L of the
         iterations it0 .. it0 + n_it - 1 (L = batch_len, B = 2 (n_it // (2 L))) under the labels of ``perm`` ([n_it, G], rows counted from
         it0; None = identity): a dict of sum and bsq [V, G, 4] float64 (those named in ``want``), dead, B, N and L"""
-        n_it = self.n_trace - int(it0) if n_it is None else int(n_it)
+        n_it = self._trace_n_it(it0, n_it)
         L = int(batch_len)
-        p = None
-        if perm is not None:
-            p = np.ascontiguousarray(perm, dtype=np.uint8)
-            if p.ndim != 2 or p.shape != (max(n_it, 0), self.G) or not np.array_equal(p, np.asarray(perm)):
-                raise ValueError("trace_rb_marginals: perm must be [n_it=%d, G=%d] labels 0..G-1" % (n_it, self.G))
-        bad = [k for k in want if k not in ("sum", "bsq")]
-        if bad:
-            raise ValueError("trace_rb_marginals: unknown output %r (sum, bsq)" % bad[0])
-        out = {k: np.zeros((self.V, self.G, 4), dtype=np.float64) for k in ("sum", "bsq") if k in want}
+        p = perm if perm is None else self._trace_perm("trace_rb_marginals", perm, n_it)
+        vg4 = (self.V, self.G, 4)
+        out, ptrs = self._trace_outputs("trace_rb_marginals", want, dict(sum=vg4, bsq=vg4))
         dead = C.c_longlong(0)
-        check(self.lib.dsm_ctx_trace_rb_marginals(self._h, _ptr(p), int(it0), n_it, L, _ptr(out.get("sum")), _ptr(out.get("bsq")),
-                                                  C.byref(dead)))
+        check(self.lib.dsm_ctx_trace_rb_marginals(self._h, _ptr(p), int(it0), n_it, L, *ptrs, C.byref(dead)))
         B = 2 * (n_it // (2 * L)) if L >= 1 else 0
         out.update(dead=int(dead.value), B=B, N=B * L, L=L)
         return out
@@ -1023,7 +1026,7 @@ class Context:
         table -- logz[t] = ln of the sum over all 4^G haplotype states of exp L under (gamma_t, eta_t); a dict of lppd [N], mean [N],
         var [N] and, when named in ``want``, logz_it [n_used, N]; only those named are allocated and fetched.  n_used is in the dict.
         G <= ASSIGN_MAX_G."""
-        n_it = self.n_trace - int(it0) if n_it is None else int(n_it)
+        n_it = self._trace_n_it(it0, n_it)
         stride = int(stride)
         x = None
         N = self.V
@@ -1033,13 +1036,8 @@ class Context:
                 raise ValueError("trace_predictive: counts must be [N, S=%d, 4]; got %s" % (self.S, x.shape))
             N = x.shape[0]
         n_used = -(-n_it // stride) if stride >= 1 and n_it > 0 else 0
-        shapes = dict(lppd=(N,), mean=(N,), var=(N,), logz_it=(n_used, N))
-        bad = [k for k in want if k not in shapes]
-        if bad:
-            raise ValueError("trace_predictive: unknown output %r (lppd, mean, var, logz_it)" % bad[0])
-        out = {k: np.zeros(shapes[k]) for k in shapes if k in want}
-        check(self.lib.dsm_ctx_trace_predictive(self._h, _ptr(x), N, int(it0), n_it, stride, _ptr(out.get("lppd")), _ptr(out.get("mean")),
-                                                _ptr(out.get("var")), _ptr(out.get("logz_it"))))
+        out, ptrs = self._trace_outputs("trace_predictive", want, dict(lppd=(N,), mean=(N,), var=(N,), logz_it=(n_used, N)))
+        check(self.lib.dsm_ctx_trace_predictive(self._h, _ptr(x), N, int(it0), n_it, stride, *ptrs))
         out["n_used"] = n_used
         return out
 
@@ -1050,16 +1048,12 @@ class Context:
         T_rep >= T_obs), rep_sample [S, 2] and rep_position [V, 2] (the sums of T_rep and T_rep^2 over (t, r)), obs_sample [S] and
         obs_position [V] (the sum of T_obs over t); only those named in ``want`` are allocated and fetched.  n_used and R are in the
         dict; p = ge / (n_used R)."""
-        n_it = self.n_trace - int(it0) if n_it is None else int(n_it)
+        n_it = self._trace_n_it(it0, n_it)
         stride, R = int(stride), int(R)
-        shapes = dict(ge_sample=(self.S,), ge_position=(self.V,), rep_sample=(self.S, 2), rep_position=(self.V, 2),
-                      obs_sample=(self.S,), obs_position=(self.V,))
-        bad = [k for k in want if k not in shapes]
-        if bad:
-            raise ValueError("trace_ppc: unknown output %r (%s)" % (bad[0], ", ".join(shapes)))
-        out = {k: np.zeros(shapes[k], dtype=np.int64 if k.startswith("ge_") else np.float64) for k in shapes if k in want}
-        check(self.lib.dsm_ctx_trace_ppc(self._h, int(it0), n_it, stride, R, C.c_uint64(int(salt) & 0xFFFFFFFFFFFFFFFF),
-                                         *(_ptr(out.get(k)) for k in shapes)))
+        out, ptrs = self._trace_outputs("trace_ppc", want, dict(ge_sample=(self.S,), ge_position=(self.V,), rep_sample=(self.S, 2),
+                                                                rep_position=(self.V, 2), obs_sample=(self.S,), obs_position=(self.V,)),
+                                        dict(ge_sample=np.int64, ge_position=np.int64))
+        check(self.lib.dsm_ctx_trace_ppc(self._h, int(it0), n_it, stride, R, C.c_uint64(int(salt) & 0xFFFFFFFFFFFFFFFF), *ptrs))
         out["n_used"] = -(-n_it // stride) if stride >= 1 and n_it > 0 else 0
         out["R"] = R
         return out

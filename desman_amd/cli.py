@@ -170,7 +170,7 @@ def _load(opts, report):
     return table, flt, subsample
 
 
-def _fit(opts, flt):
+def _fit(opts, flt, pair_every=0):
     """NMF-tensor initialisation, burn-in, degenerate-haplotype merge, sampling (bin/desman:129-153)."""
     logging.info('sampler seed %d', opts.random_seed)
     rng = RandomState(opts.random_seed)
@@ -181,7 +181,7 @@ def _fit(opts, flt):
     nmft.factorize()
     chain = HaploSNP_Sampler(flt.snps_filter, opts.genomes, rng, max_iter=opts.no_iter, device=opts.device,
                              ctx=nmft._ctx,                        # same resident count tensor
-                             pair_every=_pair_moves_options(opts))
+                             pair_every=pair_every)
     chain.tau = np.copy(nmft.get_tau(), order='C')
     chain.updateTauIndices()
     chain.gamma = np.copy(nmft.get_gamma(), order='C')
@@ -239,19 +239,28 @@ def _report_relabel(report, chain, ref):
     report.output_Haplotype_stability(chain.haplotypeStability())
 
 
-def _diagnose_batch_len(opts):
-    """--diagnose: the batch length L, checked against the iterations a chain will store; the run stops here, before any chain, if
-    there are fewer than 2 L of them.  None without the option."""
-    if opts.diagnose is None:
-        return None
+def _batch_len(opts, flag):
+    """the batch length of `flag` (--diagnose, --marginals) -- the L of --diagnose [L] where one is given, else floor(sqrt(iterations))
+    -- checked against the iterations a chain will store; the run stops here, before any chain, if there are fewer than 2 L of them"""
     from . import diagnose
     n = 250 if opts.no_iter is None else opts.no_iter            # the sampler's own default
-    L = diagnose.default_batch_len(n) if opts.diagnose is True else opts.diagnose
+    given = opts.diagnose is not None and opts.diagnose is not True          # a bare --diagnose parses as True, --diagnose L as the int
+    L = opts.diagnose if given else diagnose.default_batch_len(n)
     if L < 1:
-        sys.exit("desman: --diagnose: the batch length must be at least 1; got %d" % L)
+        sys.exit("desman: %s: the batch length must be at least 1; got %d" % (flag, L))
     if n < 2 * L:
-        sys.exit("desman: --diagnose: %d stored iterations (-i) are fewer than two batches of %d" % (n, L))
+        sys.exit("desman: %s: %d stored iterations (-i) are fewer than two batches of %d" % (flag, n, L))
     return L
+
+
+def _diagnose_batch_len(opts):
+    """--diagnose: the batch length L of its files.  None without the option."""
+    return None if opts.diagnose is None else _batch_len(opts, "--diagnose")
+
+
+def _marginals_batch_len(opts):
+    """--marginals: the batch length of Tau_rb_MCSE.csv.  None without the option."""
+    return _batch_len(opts, "--marginals") if opts.marginals else None
 
 
 def _report_diagnose(report, chain, L):
@@ -260,22 +269,6 @@ def _report_diagnose(report, chain, L):
     report.output_Tau_MCSE(chain.tauMCSE(L))
     report.output_Tau_diag(chain.tauDiagnostics(L))
     report.output_Diag_scalars(chain.scalarDiagnostics(L))
-
-
-def _marginals_batch_len(opts):
-    """--marginals: the batch length of Tau_rb_MCSE.csv -- the L of --diagnose [L] where one is given, else floor(sqrt(iterations)) --
-    checked against the iterations a chain will store; refused here, before any chain, where it cannot be served.  None without the
-    option."""
-    if not opts.marginals:
-        return None
-    from . import diagnose
-    n = 250 if opts.no_iter is None else opts.no_iter            # the sampler's own default
-    L = opts.diagnose if isinstance(opts.diagnose, int) and opts.diagnose is not True else diagnose.default_batch_len(n)
-    if L < 1:
-        sys.exit("desman: --marginals: the batch length must be at least 1; got %d" % L)
-    if n < 2 * L:
-        sys.exit("desman: --marginals: %d stored iterations (-i) are fewer than two batches of %d" % (n, L))
-    return L
 
 
 def _report_marginals(report, chain, L):
@@ -349,14 +342,44 @@ def _report_predictive(report, flt, chain, n_use, subsample):
     report.output_Predictive(fit, rest, summary)
 
 
-def _assign_rest(opts, report, table, flt, chain):
-    """-r: haplotypes of the positions left out of the fit, with tau-only sweeps driven by the fitted
-    chain's gamma / eta traces (bin/desman:181-206)."""
+def _extension_options(opts, replicates=False):
+    """every extension option of a run, refused here, before any chain, where it cannot be served (replicates: for replicate chains
+    that share their launches); returns what the fit and the reports need of them"""
+    pair_every = _pair_moves_options(opts, replicates)
+    diag_len = _diagnose_batch_len(opts)
+    marg_len = _marginals_batch_len(opts)
+    _check_options(opts, replicates)
+    _predictive_options(opts, replicates)
+    return dict(pair_every=pair_every, diag_len=diag_len, marg_len=marg_len)
+
+
+def _report_extensions(opts, ext, report, flt, chain, ref, subsample):
+    """the reports of every extension option of the run, for a fitted chain (ext: of _extension_options; ref: of _relabel_reference)"""
+    if opts.relabel or ref is not None:
+        _report_relabel(report, chain, ref)
+    if ext["diag_len"] is not None:
+        _report_diagnose(report, chain, ext["diag_len"])
+    if ext["marg_len"] is not None:
+        _report_marginals(report, chain, ext["marg_len"])
+    if opts.check:
+        _report_check(report, chain, opts.check_cells)
+    if opts.check_reps is not None:
+        _report_check_reps(report, chain, opts.check_reps, opts.check_stride)
+    if opts.predictive is not None:
+        _report_predictive(report, flt, chain, opts.predictive, subsample)
+
+
+def _rest_nmft(opts, flt, chain):
+    """-r: the positions left out of the fit and their NMFT with the fitted chain's gamma held (not yet factorized)"""
     rest = flt.snps_filter_original[~np.asarray(flt.selected, dtype=bool), :]
     nmft = Init_NMFT(rest, chain.G, chain.randomState, device=opts.device)
     nmft.gamma = np.transpose(chain.gamma)
     logging.info('NMF-tensor initialisation of the %d remaining positions (gamma fixed)' % rest.shape[0])
-    nmft.factorize_tau()
+    return rest, nmft
+
+
+def _rest_sampler(opts, chain, rest, nmft):
+    """-r: the tau-only sampler of `rest` on the context of its factorized NMFT, with the fitted chain's means and stores"""
     other = HaploSNP_Sampler(rest, chain.G, chain.randomState, max_iter=opts.no_iter, device=opts.device, ctx=nmft._ctx)
     other.tau = nmft.get_tau()
     other.updateTauIndices()
@@ -364,6 +387,15 @@ def _assign_rest(opts, report, table, flt, chain):
     other.eta_star = np.copy(chain.etaMean(), order='C')
     other.gamma_store = np.copy(chain.gamma_store, order='C')
     other.eta_store = np.copy(chain.eta_store, order='C')
+    return other
+
+
+def _assign_rest(opts, report, table, flt, chain):
+    """-r: haplotypes of the positions left out of the fit, with tau-only sweeps driven by the fitted
+    chain's gamma / eta traces (bin/desman:181-206)."""
+    rest, nmft = _rest_nmft(opts, flt, chain)
+    nmft.factorize_tau()
+    other = _rest_sampler(opts, chain, rest, nmft)
     for phase in ('burn-in', 'sampling'):
         logging.info('tau-only %s' % phase)
         other.updateTau()
@@ -373,30 +405,16 @@ def _assign_rest(opts, report, table, flt, chain):
 
 def _assign_rest_batch(runs, tell):
     """_assign_rest of several replicate chains with their NMF fits and tau-only sweeps batched (equal shapes assumed)"""
-    from . import _lib
-    others, nm = [], []
+    others, starts = [], []
     for k, r in enumerate(runs):
         tell(k)
-        opts, flt, chain = r["opts"], r["flt"], r["chain"]
-        rest = flt.snps_filter_original[~np.asarray(flt.selected, dtype=bool), :]
-        nmft = Init_NMFT(rest, chain.G, chain.randomState, device=opts.device)
-        nmft.gamma = np.transpose(chain.gamma)
-        logging.info('NMF-tensor initialisation of the %d remaining positions (gamma fixed)' % rest.shape[0])
-        nm.append(nmft)
-    Init_NMFT.factorize_tau_batch(nm)
-    for k, (r, nmft) in enumerate(zip(runs, nm)):
+        starts.append(_rest_nmft(r["opts"], r["flt"], r["chain"]))
+    Init_NMFT.factorize_tau_batch([nmft for _, nmft in starts])
+    for k, (r, (rest, nmft)) in enumerate(zip(runs, starts)):
         tell(k)
         nmft._log_trace(nmft.div_trace)
-        opts, flt, chain = r["opts"], r["flt"], r["chain"]
-        rest = flt.snps_filter_original[~np.asarray(flt.selected, dtype=bool), :]
-        other = HaploSNP_Sampler(rest, chain.G, chain.randomState, max_iter=opts.no_iter, device=opts.device, ctx=nmft._ctx)
-        other.mt_state = chain.mt_state                          # the tau-only sweeps continue the chain's GSL stream
-        other.tau = nmft.get_tau()
-        other.updateTauIndices()
-        other.gamma_star = np.copy(chain.gammaMean(), order='C')
-        other.eta_star = np.copy(chain.etaMean(), order='C')
-        other.gamma_store = np.copy(chain.gamma_store, order='C')
-        other.eta_store = np.copy(chain.eta_store, order='C')
+        other = _rest_sampler(r["opts"], r["chain"], rest, nmft)
+        other.mt_state = r["chain"].mt_state                     # the tau-only sweeps continue the chain's GSL stream
         others.append(other)
     for phase in ('burn-in', 'sampling'):
         for k in range(len(runs)):
@@ -420,28 +438,13 @@ def main(argv=None):
     if opts.genomes < 0:
         logging.error('the haplotype number must be positive, got %d' % opts.genomes)
         sys.exit(-1)
-    _pair_moves_options(opts)
-    diag_len = _diagnose_batch_len(opts)
-    marg_len = _marginals_batch_len(opts)
-    _check_options(opts)
-    _predictive_options(opts)
+    ext = _extension_options(opts)
     report = Output_Results(opts.output_dir)
     table, flt, subsample = _load(opts, report)
     ref = _relabel_reference(opts, table, flt)
-    chain = _fit(opts, flt)
+    chain = _fit(opts, flt, ext["pair_every"])
     _report(report, table, flt, chain, opts.genomes)
-    if opts.relabel or ref is not None:
-        _report_relabel(report, chain, ref)
-    if diag_len is not None:
-        _report_diagnose(report, chain, diag_len)
-    if marg_len is not None:
-        _report_marginals(report, chain, marg_len)
-    if opts.check:
-        _report_check(report, chain, opts.check_cells)
-    if opts.check_reps is not None:
-        _report_check_reps(report, chain, opts.check_reps, opts.check_stride)
-    if opts.predictive is not None:
-        _report_predictive(report, flt, chain, opts.predictive, subsample)
+    _report_extensions(opts, ext, report, flt, chain, ref, subsample)
     if subsample is not None:
         _assign_rest(opts, report, table, flt, chain)
     sampletau.freeRNG()
@@ -462,18 +465,14 @@ def main_replicates(argv_list, on_chain=None):
         opts = build_parser().parse_args(argv)
         if opts.assign_file is not None:
             sys.exit('desman: -a/--assign_file is not supported (dead in the reference: bin/desman:213-214)')
-        _pair_moves_options(opts, replicates=True)
-        diag_len = _diagnose_batch_len(opts)
-        marg_len = _marginals_batch_len(opts)
-        _check_options(opts, replicates=True)
-        _predictive_options(opts, replicates=True)
+        ext = _extension_options(opts, replicates=True)      # (--pair-moves, --check-reps and --predictive are refused)
         report = Output_Results(opts.output_dir)
         table, flt, subsample = _load(opts, report)
         logging.info('sampler seed %d', opts.random_seed)
         rng = RandomState(opts.random_seed)
         nmft = Init_NMFT(flt.snps_filter, opts.genomes, rng, device=opts.device)
         runs.append(dict(opts=opts, report=report, table=table, flt=flt, subsample=subsample, rng=rng, nmft=nmft,
-                         ref=_relabel_reference(opts, table, flt), diag_len=diag_len, marg_len=marg_len))
+                         ref=_relabel_reference(opts, table, flt), ext=ext))
     # the NMF starts: together where the batched kernels apply (one shape, S <= 128, G <= 16), else one by one
     nm = [r["nmft"] for r in runs]
     done = False
@@ -527,14 +526,7 @@ def main_replicates(argv_list, on_chain=None):
     for k, r in enumerate(runs):
         tell(k)
         _report(r["report"], r["table"], r["flt"], r["chain"], r["opts"].genomes)
-        if r["opts"].relabel or r["ref"] is not None:
-            _report_relabel(r["report"], r["chain"], r["ref"])
-        if r["diag_len"] is not None:
-            _report_diagnose(r["report"], r["chain"], r["diag_len"])
-        if r["marg_len"] is not None:
-            _report_marginals(r["report"], r["chain"], r["marg_len"])
-        if r["opts"].check:
-            _report_check(r["report"], r["chain"], r["opts"].check_cells)
+        _report_extensions(r["opts"], r["ext"], r["report"], r["flt"], r["chain"], r["ref"], r["subsample"])
     # -r: the positions left out of the fit -- batched where the replicates still agree in shape
     rest_runs = [r for r in runs if r["subsample"] is not None]
     idx = {id(r): k for k, r in enumerate(runs)}

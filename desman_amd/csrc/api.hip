@@ -10,7 +10,7 @@
 #include <thread>
 
 #include "dsm_host.h"
-#include "dsm_host_util.h"
+#include "dsm_trace_host.h"
 #include "log_table.h"
 
 static thread_local char g_err[512] = "";
@@ -97,11 +97,9 @@ extern "C" int dsm_ctx_get_timing(dsm_ctx *c, double *ms_total, int64_t *launche
     return DSM_OK;
 }
 
-// ---------------------------------------------------------------- helpers (dev_alloc, DevBuf, DSM_TRY, dsm_ctx_need: dsm_host_util.h)
+// ---------------------------------------------------------------- helpers (dev_alloc, DevBuf, DSM_TRY, BIND, dsm_ctx_need: dsm_host_util.h)
 template <typename T>
 static void dev_free(T **p) { if (*p) { (void)hipFree(*p); *p = nullptr; } }
-
-#define BIND(c) HIP_TRY(hipSetDevice((c)->device))
 
 // Esum and the DSM_ESUM_PARTS copies stage 1 adds to, all zero: what a failed pass left in the copies is not added to the next one
 static int esum_reset(dsm_ctx *c)
@@ -786,7 +784,7 @@ extern "C" int dsm_ctx_loglik(dsm_ctx *c, double *ll, double *lp)
 }
 
 // ---------------------------------------------------------------- update loops
-static int alloc_traces(dsm_ctx *c, int n)
+int alloc_traces(dsm_ctx *c, int n)
 {
     // buffers are kept across update() calls and only grown (hipMalloc/hipFree cost milliseconds)
     const size_t sg = (size_t)c->S * c->G;
@@ -1518,7 +1516,7 @@ extern "C" int dsm_ctx_get_star(dsm_ctx *c, int64_t *tau_star, double *gamma_sta
     HIP_TRY(hipMemcpyAsync(st, c->star, sizeof st, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     const int slot = (int)st[1];
-    if (tau_star) DSM_TRY(fetch_tau(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)slot * c->V), tau_star));
+    if (tau_star) DSM_TRY(fetch_tau(c, trace_tau_slot(c, slot), tau_star));
     if (gamma_star) HIP_TRY(hipMemcpyAsync(gamma_star, c->gamma_star, (size_t)c->S * c->G * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (eta_star) HIP_TRY(hipMemcpyAsync(eta_star, c->eta_star, 16 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1551,362 +1549,7 @@ extern "C" int dsm_ctx_get_tau_at(dsm_ctx *c, int it, int64_t *tau)
     DSM_TRY(dsm_ctx_need(c, true, true));
     if (!c->tau_trace || !tau || it < -1 || it >= c->n_trace) { dsm_set_error("get_tau_at: bad iteration"); return DSM_ERR_ARG; }
     BIND(c);
-    return fetch_tau(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it + 1) * c->V), tau);
-}
-
-// ---------------------------------------------------------------- reductions of the tau trace (kernels_relabel.hip)
-// digits [rows][G] -> packed words; DSM_ERR_ARG on a digit outside 0..3
-static int pack_digits(const char *who, const int64_t *digits, size_t rows, int G, std::vector<uint64_t> &out)
-{
-    out.assign(rows, 0ull);
-    for (size_t r = 0; r < rows; ++r) {
-        uint64_t t = 0;
-        for (int g = 0; g < G; ++g) {
-            const int64_t d = digits[r * G + g];
-            if (d < 0 || d > 3) { dsm_set_error("%s: digit %lld at row %zu, haplotype %d is not a base 0..3", who, (long long)d, r, g); return DSM_ERR_ARG; }
-            t |= (uint64_t)d << (2 * g);
-        }
-        out[r] = t;
-    }
-    return DSM_OK;
-}
-
-// the checks the two trace reductions share: a trace, and a range inside it
-static int trace_range(dsm_ctx *c, const char *who, int it0, int n_it)
-{
-    DSM_TRY(dsm_ctx_need(c, true, true));
-    if (!c->tau_trace) { dsm_set_error("%s: no update has run", who); return DSM_ERR_STATE; }
-    if (it0 < 0 || n_it < 0 || it0 > c->n_trace || n_it > c->n_trace - it0) {
-        dsm_set_error("%s: iterations %d .. %d + %d outside the trace of %d", who, it0, it0, n_it, c->n_trace);
-        return DSM_ERR_ARG;
-    }
-    return DSM_OK;
-}
-
-// inv[t][perm[t][g]] = g for n_it rows of perm (null: identity rows); DSM_ERR_ARG on a row that is no permutation of 0..G-1
-static int perm_inverse(const char *who, const uint8_t *perm, int n_it, int G, std::vector<uint8_t> &inv)
-{
-    inv.resize((size_t)n_it * G);
-    for (int t = 0; t < n_it; ++t) {
-        uint32_t seen = 0;
-        for (int g = 0; g < G; ++g) {
-            const int p = perm ? perm[(size_t)t * G + g] : g;
-            if (p >= G || (seen >> p & 1u)) { dsm_set_error("%s: row %d of perm is not a permutation of 0..%d", who, t, G - 1); return DSM_ERR_ARG; }
-            seen |= 1u << p;
-            inv[(size_t)t * G + p] = (uint8_t)g;
-        }
-    }
-    return DSM_OK;
-}
-
-extern "C" int dsm_ctx_trace_snd(dsm_ctx *c, int mode, const int64_t *ref_tau, int Gr, int it0, int n_it, int32_t *snd)
-{
-    DSM_TRY(trace_range(c, "trace_snd", it0, n_it));
-    if (mode != DSM_SND_STAR && mode != DSM_SND_SELF && mode != DSM_SND_GIVEN) { dsm_set_error("trace_snd: mode %d is none of DSM_SND_STAR / SELF / GIVEN", mode); return DSM_ERR_ARG; }
-    if (mode == DSM_SND_GIVEN) {
-        if (Gr < 1 || Gr > DSM_MAX_G) { dsm_set_error("trace_snd: Gr=%d outside 1..%d", Gr, DSM_MAX_G); return DSM_ERR_ARG; }
-        if (!ref_tau) { dsm_set_error("trace_snd: DSM_SND_GIVEN without a reference"); return DSM_ERR_ARG; }
-    } else {
-        if (Gr != 0 && Gr != c->G) { dsm_set_error("trace_snd: Gr=%d, but this mode's reference has the chain's %d haplotypes (pass 0 or G)", Gr, c->G); return DSM_ERR_ARG; }
-        Gr = c->G;
-    }
-    if (n_it > 0 && !snd) { dsm_set_error("trace_snd: no output buffer"); return DSM_ERR_ARG; }
-    std::vector<uint64_t> packed;
-    if (mode == DSM_SND_GIVEN) DSM_TRY(pack_digits("trace_snd", ref_tau, (size_t)c->V, Gr, packed));
-    if (n_it == 0) return DSM_OK;
-    BIND(c);
-    const size_t V = (size_t)c->V, stride = c->tau_fixed_trace ? 0 : V;
-    const uint64_t *trace = c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it0 + 1) * V);
-    const uint64_t *ref = nullptr;
-    DevBuf<uint64_t> d_ref;
-    if (mode == DSM_SND_STAR) {
-        double st[2];
-        HIP_TRY(hipMemcpyAsync(st, c->star, sizeof st, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (!(st[1] >= 0.0 && st[1] <= (double)c->n_trace)) { dsm_set_error("trace_snd: the MAP record's slot lies outside the trace of %d", c->n_trace); return DSM_ERR_STATE; }
-        ref = c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(int)st[1] * V);
-    } else if (mode == DSM_SND_GIVEN) {
-        DSM_TRY(d_ref.alloc(V));
-        HIP_TRY(hipMemcpyAsync(d_ref, packed.data(), V * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-        ref = d_ref;
-    }
-    const size_t nout = (size_t)n_it * c->G * Gr;
-    DevBuf<int> d_out;
-    DSM_TRY(d_out.alloc(nout));
-    DSM_TRY(k_trace_snd(c, trace, stride, ref, Gr, n_it, d_out));
-    HIP_TRY(hipMemcpyAsync(snd, d_out, nout * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return DSM_OK;
-}
-
-extern "C" int dsm_ctx_get_tau_sum_perm(dsm_ctx *c, const uint8_t *perm, int it0, int n_it, int64_t *tau_sum)
-{
-    DSM_TRY(trace_range(c, "get_tau_sum_perm", it0, n_it));
-    if (!tau_sum || (n_it > 0 && !perm)) { dsm_set_error("get_tau_sum_perm: null pointer"); return DSM_ERR_ARG; }
-    const int G = c->G;
-    std::vector<uint8_t> inv;
-    DSM_TRY(perm_inverse("get_tau_sum_perm", perm, n_it, G, inv));
-    BIND(c);
-    const size_t V = (size_t)c->V, nt = V * G * 4;
-    DevBuf<int64_t> d_out;
-    DevBuf<uint8_t> d_inv;
-    DSM_TRY(d_out.alloc(nt));
-    DSM_TRY(d_inv.alloc(inv.size()));
-    if (n_it > 0) HIP_TRY(hipMemcpyAsync(d_inv, inv.data(), inv.size(), hipMemcpyHostToDevice, c->stream));
-    DSM_TRY(k_tau_sum_perm(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it0 + 1) * V), c->tau_fixed_trace ? 0 : V, d_inv, n_it, d_out));
-    HIP_TRY(hipMemcpyAsync(tau_sum, d_out, nt * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return DSM_OK;
-}
-
-// batch sums of the trace for convergence diagnostics (kernels_diag.hip): the last B L of the n_it iterations
-extern "C" int dsm_ctx_trace_batch_stats(dsm_ctx *c, const uint8_t *perm, int it0, int n_it, int batch_len, int64_t *sum, int64_t *first,
-                                         int64_t *bsq, int32_t *flips)
-{
-    DSM_TRY(trace_range(c, "trace_batch_stats", it0, n_it));
-    if (batch_len < 1) { dsm_set_error("trace_batch_stats: batch_len=%d, at least 1 is needed", batch_len); return DSM_ERR_ARG; }
-    if (n_it > 0 && n_it / 2 < batch_len) {
-        dsm_set_error("trace_batch_stats: %d iterations are fewer than two batches of %d", n_it, batch_len);
-        return DSM_ERR_ARG;
-    }
-    const int G = c->G, L = batch_len, B = n_it > 0 ? 2 * (n_it / (2 * L)) : 0, skip = n_it - B * L;       // (n_it > 0: 2 L <= n_it)
-    std::vector<uint8_t> inv;
-    DSM_TRY(perm_inverse("trace_batch_stats", perm, n_it, G, inv));
-    BIND(c);
-    const size_t V = (size_t)c->V, nt = V * G * 4, used = (size_t)B * L * G;
-    DevBuf<int64_t> d_sum, d_first, d_bsq;
-    DevBuf<int32_t> d_flips;
-    DevBuf<uint8_t> d_inv;
-    DSM_TRY(d_sum.alloc(nt));
-    DSM_TRY(d_first.alloc(nt));
-    DSM_TRY(d_bsq.alloc(nt));
-    DSM_TRY(d_flips.alloc(V * G));
-    DSM_TRY(d_inv.alloc(used));
-    if (used > 0) HIP_TRY(hipMemcpyAsync(d_inv, inv.data() + (size_t)skip * G, used, hipMemcpyHostToDevice, c->stream));
-    DSM_TRY(k_trace_batch_stats(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it0 + 1 + skip) * V), c->tau_fixed_trace ? 0 : V, d_inv, B,
-                            L, d_sum, d_first, d_bsq, d_flips));
-    if (sum) HIP_TRY(hipMemcpyAsync(sum, d_sum, nt * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    if (first) HIP_TRY(hipMemcpyAsync(first, d_first, nt * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    if (bsq) HIP_TRY(hipMemcpyAsync(bsq, d_bsq, nt * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    if (flips) HIP_TRY(hipMemcpyAsync(flips, d_flips, V * G * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return DSM_OK;
-}
-
-// posterior predictive fit per sample, position and cell over stored iterations (kernels_fit.hip): everything is read
-// where it lies -- the counts, the tau, gamma and eta traces -- and nothing of the chain is written
-extern "C" int dsm_ctx_trace_fit_stats(dsm_ctx *c, int it0, int n_it, double *sample, double *position, double *cell)
-{
-    DSM_TRY(trace_range(c, "trace_fit_stats", it0, n_it));
-    const size_t V = (size_t)c->V, S = (size_t)c->S, sg = S * c->G;
-    if (n_it == 0) {
-        if (sample) std::fill(sample, sample + S * 4, 0.0);
-        if (position) std::fill(position, position + V * 4, 0.0);
-        if (cell) std::fill(cell, cell + V * S, 0.0);
-        return DSM_OK;
-    }
-    FitPlan pl;
-    DSM_TRY(fit_plan(c, n_it, &pl));
-    BIND(c);
-    DevBuf<double> d_sample, d_position, d_cell, samp_part, pos_part, cell_part;
-    DSM_TRY(d_sample.alloc(S * 4));
-    DSM_TRY(d_position.alloc(V * 4));
-    DSM_TRY(samp_part.alloc((size_t)pl.parts * pl.tiles * S * 4));
-    DSM_TRY(pos_part.alloc((size_t)pl.parts * V * 4));
-    if (cell) {
-        DSM_TRY(d_cell.alloc(V * S));
-        DSM_TRY(cell_part.alloc((size_t)pl.parts * V * S));
-    }
-    DSM_TRY(k_trace_fit_stats(c, pl, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it0 + 1) * V), c->tau_fixed_trace ? 0 : V,
-                          c->gamma_trace + (size_t)it0 * sg, c->eta_trace + (size_t)it0 * 16, n_it, samp_part, pos_part, cell_part, d_sample,
-                          d_position, cell ? d_cell.p : nullptr));
-    if (sample) HIP_TRY(hipMemcpyAsync(sample, d_sample, S * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (position) HIP_TRY(hipMemcpyAsync(position, d_position, V * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (cell) HIP_TRY(hipMemcpyAsync(cell, d_cell, V * S * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return DSM_OK;
-}
-
-// Rao-Blackwellised tau marginals over stored iterations (kernels_rbtau.hip): the range, perm and batch rules of
-// dsm_ctx_trace_batch_stats; the counts and the three traces are read where they lie and nothing of the chain is written
-extern "C" int dsm_ctx_trace_rb_marginals(dsm_ctx *c, const uint8_t *perm, int it0, int n_it, int batch_len, double *sum, double *bsq,
-                                          long long *dead)
-{
-    DSM_TRY(trace_range(c, "trace_rb_marginals", it0, n_it));
-    if (batch_len < 1) { dsm_set_error("trace_rb_marginals: batch_len=%d, at least 1 is needed", batch_len); return DSM_ERR_ARG; }
-    if (n_it > 0 && n_it / 2 < batch_len) {
-        dsm_set_error("trace_rb_marginals: %d iterations are fewer than two batches of %d", n_it, batch_len);
-        return DSM_ERR_ARG;
-    }
-    const int G = c->G, L = batch_len, B = n_it > 0 ? 2 * (n_it / (2 * L)) : 0, skip = n_it - B * L;
-    std::vector<uint8_t> inv;
-    DSM_TRY(perm_inverse("trace_rb_marginals", perm, n_it, G, inv));          // the rows of skipped iterations are validated too
-    const size_t V = (size_t)c->V, nt = V * G * 4, sg = (size_t)c->S * G, used = (size_t)B * L * G;
-    if (n_it == 0) {
-        if (sum) std::fill(sum, sum + nt, 0.0);
-        if (bsq) std::fill(bsq, bsq + nt, 0.0);
-        if (dead) *dead = 0;
-        return DSM_OK;
-    }
-    { int lpv, nsl; DSM_TRY(tau_shape(c->S, &lpv, &nsl)); }                     // S <= DSM_MAX_S, before anything is allocated
-    std::vector<uint8_t> lab(used);                                           // the used rows of perm as they are (NULL: identity)
-    for (size_t i = 0; i < used; ++i) lab[i] = perm ? perm[(size_t)skip * G + i] : (uint8_t)(i % G);
-    BIND(c);
-    DevBuf<double> d_bs, d_sum, d_bsq;
-    DevBuf<unsigned long long> d_dead;
-    DevBuf<uint8_t> d_perm;
-    DSM_TRY(d_bs.alloc(nt));
-    DSM_TRY(d_sum.alloc(nt));
-    DSM_TRY(d_bsq.alloc(nt));
-    DSM_TRY(d_dead.alloc(1));
-    DSM_TRY(d_perm.alloc(used));
-    HIP_TRY(hipMemsetAsync(d_sum, 0, nt * sizeof(double), c->stream));
-    HIP_TRY(hipMemsetAsync(d_bsq, 0, nt * sizeof(double), c->stream));
-    HIP_TRY(hipMemsetAsync(d_dead, 0, sizeof(unsigned long long), c->stream));
-    HIP_TRY(hipMemcpyAsync(d_perm, lab.data(), used, hipMemcpyHostToDevice, c->stream));
-    const int t0 = it0 + skip;
-    DSM_TRY(k_rb_tau(c, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(t0 + 1) * V), c->tau_fixed_trace ? 0 : V,
-                     c->gamma_trace + (size_t)t0 * sg, c->eta_trace + (size_t)t0 * 16, d_perm, B * L, L, d_bs, d_sum, d_bsq, d_dead));
-    unsigned long long nd = 0;
-    if (sum) HIP_TRY(hipMemcpyAsync(sum, d_sum, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (bsq) HIP_TRY(hipMemcpyAsync(bsq, d_bsq, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&nd, d_dead, sizeof nd, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (dead) *dead = (long long)nd;
-    return DSM_OK;
-}
-
-// test hook: which instantiation of the fit kernel, and which grid, a call over n_it iterations would launch (nothing is launched)
-extern "C" int dsm_fit_debug_path(dsm_ctx *c, int n_it, int out[5])
-{
-    DSM_TRY(dsm_ctx_need(c, true, true));
-    if (!out || n_it < 1) { dsm_set_error("fit_debug_path: bad arguments"); return DSM_ERR_ARG; }
-    FitPlan pl;
-    DSM_TRY(fit_plan(c, n_it, &pl));
-    out[0] = pl.nsl; out[1] = pl.lpv; out[2] = pl.gc; out[3] = pl.tiles; out[4] = pl.parts;
-    return DSM_OK;
-}
-
-// posterior predictive p-values per sample and position from replicate tables drawn at the stored iterations (kernels_ppc.hip; DESIGN.md
-// sec. 8k): the counts and the three traces are read where they lie, the uniforms are the call's own, nothing of the chain is written
-static int ppc_args(dsm_ctx *c, const char *who, int it0, int n_it, int stride, int R)
-{
-    DSM_TRY(trace_range(c, who, it0, n_it));
-    if (stride < 1 || R < 1) { dsm_set_error("%s: stride=%d, R=%d: at least 1 is needed", who, stride, R); return DSM_ERR_ARG; }
-    if (R > DSM_PPC_MAX_R) { dsm_set_error("%s: R=%d above DSM_PPC_MAX_R=%d", who, R, DSM_PPC_MAX_R); return DSM_ERR_UNSUPPORTED; }
-    if ((long long)it0 + n_it > (1LL << 32) / DSM_PPC_MAX_R) {
-        dsm_set_error("%s: iteration %lld does not fit the counter word", who, (long long)it0 + n_it);
-        return DSM_ERR_UNSUPPORTED;
-    }
-    return DSM_OK;
-}
-
-extern "C" int dsm_ctx_trace_ppc(dsm_ctx *c, int it0, int n_it, int stride, int R, uint64_t salt, int64_t *ge_sample, int64_t *ge_position,
-                                 double *rep_sample, double *rep_position, double *obs_sample, double *obs_position)
-{
-    DSM_TRY(ppc_args(c, "trace_ppc", it0, n_it, stride, R));
-    const size_t V = (size_t)c->V, S = (size_t)c->S, sg = S * c->G;
-    const int n_used = (int)(((long long)n_it + stride - 1) / stride);
-    if (n_used == 0) {
-        if (ge_sample) std::fill(ge_sample, ge_sample + S, (int64_t)0);
-        if (ge_position) std::fill(ge_position, ge_position + V, (int64_t)0);
-        if (rep_sample) std::fill(rep_sample, rep_sample + S * 2, 0.0);
-        if (rep_position) std::fill(rep_position, rep_position + V * 2, 0.0);
-        if (obs_sample) std::fill(obs_sample, obs_sample + S, 0.0);
-        if (obs_position) std::fill(obs_position, obs_position + V, 0.0);
-        return DSM_OK;
-    }
-    PpcPlan pl;
-    DSM_TRY(ppc_plan(c, n_used, R, &pl));
-    BIND(c);
-    DevBuf<unsigned long long> d_ge_s, d_ge_v;
-    DevBuf<double> d_rep_s, d_rep_v, d_obs_s, d_obs_v;
-    DSM_TRY(d_ge_s.alloc(S)); DSM_TRY(d_ge_v.alloc(V));
-    DSM_TRY(d_rep_s.alloc(S * 2)); DSM_TRY(d_rep_v.alloc(V * 2));
-    DSM_TRY(d_obs_s.alloc(S)); DSM_TRY(d_obs_v.alloc(V));
-    HIP_TRY(hipMemsetAsync(d_ge_s, 0, S * sizeof(unsigned long long), c->stream));
-    HIP_TRY(hipMemsetAsync(d_ge_v, 0, V * sizeof(unsigned long long), c->stream));
-    HIP_TRY(hipMemsetAsync(d_rep_s, 0, S * 2 * sizeof(double), c->stream));
-    HIP_TRY(hipMemsetAsync(d_rep_v, 0, V * 2 * sizeof(double), c->stream));
-    HIP_TRY(hipMemsetAsync(d_obs_s, 0, S * sizeof(double), c->stream));
-    HIP_TRY(hipMemsetAsync(d_obs_v, 0, V * sizeof(double), c->stream));
-    const uint64_t key = c->ctr_seed ^ salt;
-    DSM_TRY(k_trace_ppc(c, pl, c->tau_trace + (c->tau_fixed_trace ? 0 : (size_t)(it0 + 1) * V), c->tau_fixed_trace ? 0 : V,
-                        c->gamma_trace + (size_t)it0 * sg, c->eta_trace + (size_t)it0 * 16, it0, stride, n_used, R, (uint32_t)key,
-                        (uint32_t)(key >> 32), d_ge_s, d_ge_v, d_rep_s, d_rep_v, d_obs_s, d_obs_v));
-    if (ge_sample) HIP_TRY(hipMemcpyAsync(ge_sample, d_ge_s, S * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    if (ge_position) HIP_TRY(hipMemcpyAsync(ge_position, d_ge_v, V * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    if (rep_sample) HIP_TRY(hipMemcpyAsync(rep_sample, d_rep_s, S * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (rep_position) HIP_TRY(hipMemcpyAsync(rep_position, d_rep_v, V * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (obs_sample) HIP_TRY(hipMemcpyAsync(obs_sample, d_obs_s, S * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (obs_position) HIP_TRY(hipMemcpyAsync(obs_position, d_obs_v, V * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return DSM_OK;
-}
-
-// test hook: which instantiation, chunks and grid a dsm_ctx_trace_ppc call would launch (nothing is launched)
-extern "C" int dsm_ppc_debug_path(dsm_ctx *c, int n_used, int R, int out[8])
-{
-    DSM_TRY(dsm_ctx_need(c, true, true));
-    if (!out || n_used < 1 || R < 1 || R > DSM_PPC_MAX_R) { dsm_set_error("ppc_debug_path: bad arguments"); return DSM_ERR_ARG; }
-    PpcPlan pl;
-    DSM_TRY(ppc_plan(c, n_used, R, &pl));
-    out[0] = pl.nsl; out[1] = pl.lpv; out[2] = pl.gc; out[3] = pl.tiles; out[4] = pl.parts; out[5] = pl.ct; out[6] = pl.cr;
-    out[7] = DSM_PPC_READS;
-    return DSM_OK;
-}
-
-// test hook: the first n rows of the gamma and eta traces (the companion of dsm_ctx_debug_set_trace, called after it)
-extern "C" int dsm_ctx_debug_set_param_trace(dsm_ctx *c, const double *gamma, const double *eta, int n)
-{
-    DSM_TRY(dsm_ctx_need(c, true, true));
-    const int have = c->tau_trace ? c->n_trace : 0;
-    if (n < 0 || n > have || (n > 0 && (!gamma || !eta))) {
-        dsm_set_error("debug_set_param_trace: n=%d outside the trace of %d, or a null pointer", n, have);
-        return DSM_ERR_ARG;
-    }
-    BIND(c);
-    const size_t sg = (size_t)c->S * c->G;
-    if (n > 0) {
-        HIP_TRY(hipMemcpyAsync(c->gamma_trace, gamma, (size_t)n * sg * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->eta_trace, eta, (size_t)n * 16 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return DSM_OK;
-}
-
-// test hook: a synthetic trace.  Slot 0 = the resident state, slots 1 .. n = the given digits.  A context on which no update has run has
-// no MAP record yet: it gets the resident state as one (slot 0, lp = -inf), so that DSM_SND_STAR has a reference; an existing record stays.
-extern "C" int dsm_ctx_debug_set_trace(dsm_ctx *c, const int64_t *tau_digits, int n)
-{
-    DSM_TRY(dsm_ctx_need(c, true, true));
-    if (n < 0 || (n > 0 && !tau_digits)) { dsm_set_error("debug_set_trace: bad arguments"); return DSM_ERR_ARG; }
-    std::vector<uint64_t> packed;
-    DSM_TRY(pack_digits("debug_set_trace", tau_digits, (size_t)n * c->V, c->G, packed));
-    BIND(c);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const bool fresh = !c->tau_trace || n > c->trace_cap;
-    const bool no_star = !c->tau_trace;
-    DSM_TRY(alloc_traces(c, n));
-    const size_t V = (size_t)c->V, sg = (size_t)c->S * c->G;
-    if (fresh) {                                      // the other traces of a new allocation read as zero
-        const size_t cap = (size_t)c->trace_cap;
-        HIP_TRY(hipMemsetAsync(c->ll_trace, 0, cap * sizeof(double), c->stream));
-        HIP_TRY(hipMemsetAsync(c->lp_trace, 0, cap * sizeof(double), c->stream));
-        HIP_TRY(hipMemsetAsync(c->nchange_trace, 0, cap * sizeof(int), c->stream));
-        HIP_TRY(hipMemsetAsync(c->gamma_trace, 0, cap * sg * sizeof(double), c->stream));
-        HIP_TRY(hipMemsetAsync(c->eta_trace, 0, cap * 16 * sizeof(double), c->stream));
-    }
-    if (no_star) {
-        const double st[2] = {-INFINITY, 0.0};
-        HIP_TRY(hipMemcpyAsync(c->star, st, sizeof st, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->gamma_star, c->gamma, sg * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->eta_star, c->eta, 16 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    }
-    HIP_TRY(hipMemcpyAsync(c->tau_trace, c->tau, V * sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
-    if (n > 0) HIP_TRY(hipMemcpyAsync(c->tau_trace + V, packed.data(), (size_t)n * V * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return DSM_OK;
+    return fetch_tau(c, trace_tau_slot(c, it + 1), tau);
 }
 
 // ---------------------------------------------------------------- NMFT

@@ -224,6 +224,7 @@ int k_mt_fill(dsm_ctx *c, uint32_t *out, size_t n, hipStream_t stream);
 int k_stats_v1(dsm_ctx *c, uint32_t iter);
 int k_log2f_test(dsm_ctx *c, const float *d_in, float *d_out, size_t n);
 int build_stats_items(dsm_ctx *c);          // api.hip: work list of the per-read pass from the resident tensor
+int alloc_traces(dsm_ctx *c, int n);         // api.hip: room for the traces of n iterations (kept across calls, only grown); n_trace = n
 
 // ---- launchers (kernels_stats.hip)
 // the subset table's row map: row of (subset H, sample s) = (H DSM_NTAB_HMUL + (s >> 4) DSM_NTAB_SWZ) mod 2^G (kernels_stats.hip: ensure_ntab)
@@ -293,10 +294,14 @@ int k_held_sweep(dsm_ctx *c, int n_held, const double *gamma, const double *eta,
 // every tau RNG mode; the changed digits are added to *c->nchange
 int k_pair_sweep(dsm_ctx *c, const double *gamma, const double *eta, uint32_t iter);
 
+// ---- the launchers below that read the resident traces take the rows of their first iteration as a TraceView (dsm_trace_host.h:
+// trace_view; tau_stride = words between two iterations' tau rows, 0: one row for all)
+struct TraceView;
+
 // ---- launcher (kernels_rbtau.hip): the full conditionals of tau over n_it >= 1 stored iterations in batches of L (n_it a multiple of L),
-// d_perm [n_it][G] labels, trace_stride as below; d_sum / d_bsq / *d_dead zeroed by the caller, d_bs scratch of d_sum's size
-int k_rb_tau(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const double *gamma, const double *eta, const uint8_t *d_perm, int n_it,
-             int L, double *d_bs, double *d_sum, double *d_bsq, unsigned long long *d_dead);
+// d_perm [n_it][G] labels; d_sum / d_bsq / *d_dead zeroed by the caller, d_bs scratch of d_sum's size
+int k_rb_tau(dsm_ctx *c, const TraceView &tr, const uint8_t *d_perm, int n_it, int L, double *d_bs, double *d_sum, double *d_bsq,
+             unsigned long long *d_dead);
 
 // ---- the 4^G joint states of a position as assign_kernel and pred_kernel walk them (kernels_assign.hip): the GO outer haplotypes are
 // NB = 4^GO blocks of 64 states, cut into P = min(NB, 64) partials of bpp consecutive blocks, one wavefront each.  P depends on G only.
@@ -305,28 +310,26 @@ struct JointSplit {
     explicit JointSplit(int G) : GO(G > 3 ? G - 3 : 0), NB(1 << (2 * GO)), P(NB < 64 ? NB : 64), bpp(NB / P) {}
 };
 
-// ---- launchers (kernels_relabel.hip): reductions of the tau trace; trace_stride = words between two iterations' rows (0: one row for all)
-int k_trace_snd(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const uint64_t *ref, int Gr, int n_it, int *d_out);   // ref null: each iteration against itself
-int k_tau_sum_perm(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const uint8_t *d_inv, int n, int64_t *d_out);      // inv[t][perm[t][g]] = g
+// ---- launchers (kernels_relabel.hip): reductions of the tau trace
+int k_trace_snd(dsm_ctx *c, const TraceView &tr, const uint64_t *ref, int Gr, int n_it, int *d_out);   // ref null: each iteration against itself
+int k_tau_sum_perm(dsm_ctx *c, const TraceView &tr, const uint8_t *d_inv, int n, int64_t *d_out);      // inv[t][perm[t][g]] = g
 
-// ---- launcher (kernels_diag.hip): batch sums of the tau trace; B batches of L iterations, B even, d_inv [B * L][G], trace_stride as above
-int k_trace_batch_stats(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const uint8_t *d_inv, int B, int L, int64_t *d_sum,
-                        int64_t *d_first, int64_t *d_bsq, int32_t *d_flips);
+// ---- launcher (kernels_diag.hip): batch sums of the tau trace; B batches of L iterations, B even, d_inv [B * L][G]
+int k_trace_batch_stats(dsm_ctx *c, const TraceView &tr, const uint8_t *d_inv, int B, int L, int64_t *d_sum, int64_t *d_first,
+                        int64_t *d_bsq, int32_t *d_flips);
 
-// ---- launcher (kernels_fit.hip): posterior predictive fit sums over n_it stored iterations; trace_stride as above
+// ---- launcher (kernels_fit.hip): posterior predictive fit sums over n_it stored iterations
 struct FitPlan { int nsl, lpv, gc, tiles, parts; };   // sample slots per lane, lanes per position, haplotypes per staged gamma chunk, workgroups per part, parts
 int fit_plan(const dsm_ctx *c, int n_it, FitPlan *pl);
-int k_trace_fit_stats(dsm_ctx *c, const FitPlan &pl, const uint64_t *trace, size_t trace_stride, const double *gamma, const double *eta,
-                      int n_it, double *d_samp_part, double *d_pos_part, double *d_cell_part, double *d_sample, double *d_position,
-                      double *d_cell);
+int k_trace_fit_stats(dsm_ctx *c, const FitPlan &pl, const TraceView &tr, int n_it, double *d_samp_part, double *d_pos_part,
+                      double *d_cell_part, double *d_sample, double *d_position, double *d_cell);
 
-// ---- launcher (kernels_ppc.hip): posterior predictive p-values from replicate tables over n_used stored iterations (the trace, gamma and
-// eta pointers are those of iteration it0; used iteration k is it0 + k stride); the six outputs are device buffers the launcher fills
+// ---- launcher (kernels_ppc.hip): posterior predictive p-values from replicate tables over n_used stored iterations (the view is that of
+// iteration it0; used iteration k is it0 + k stride); the six outputs are device buffers the launcher fills
 struct PpcPlan { int nsl, lpv, gc, tiles, parts, ct, cr; size_t lds; };   // as FitPlan, then the iterations and replicates per launch and its LDS bytes
 int ppc_plan(const dsm_ctx *c, int n_used, int R, PpcPlan *pl);
-int k_trace_ppc(dsm_ctx *c, const PpcPlan &pl, const uint64_t *trace, size_t trace_stride, const double *gamma, const double *eta, int it0,
-                int stride, int n_used, int R, uint32_t key0, uint32_t key1, unsigned long long *d_ge_s, unsigned long long *d_ge_v,
-                double *d_rep_s, double *d_rep_v, double *d_obs_s, double *d_obs_v);
+int k_trace_ppc(dsm_ctx *c, const PpcPlan &pl, const TraceView &tr, int it0, int stride, int n_used, int R, uint32_t key0, uint32_t key1,
+                unsigned long long *d_ge_s, unsigned long long *d_ge_v, double *d_rep_s, double *d_rep_v, double *d_obs_s, double *d_obs_v);
 
 // ---- launchers (kernels_nmft.hip)
 int k_nmft_freq(dsm_ctx *c);

@@ -10,6 +10,7 @@
 #include "log_table.h"
 
 #define DSM_TRY(x) do { int _r = (x); if (_r != DSM_OK) return _r; } while (0)
+#define BIND(c) HIP_TRY(hipSetDevice((c)->device))
 
 // *p freed, then room for n (at least one) elements; *p is null after a failure
 template <typename T>

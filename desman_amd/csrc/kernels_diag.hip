@@ -1,5 +1,5 @@
 // kernels_diag.hip -- gfx950 kernel that reduces the resident tau trace to what batch-means convergence diagnostics need, as exact
-// integers (api.hip: dsm_ctx_trace_batch_stats; desman_amd/diagnose.py).
+// integers (api_trace.hip: dsm_ctx_trace_batch_stats; desman_amd/diagnose.py).
 //
 //   trace_batch_stats_kernel   with x_t[v][l][a] = [the haplotype carrying label l in iteration t has base a at v], over B batches of
 //                              L consecutive iterations:  sum = sum_t x_t,  first = the same over batches 0 .. B/2 - 1,
@@ -9,8 +9,7 @@
 // bits for any grid and any split of the iterations.
 #include <algorithm>
 
-#include "dsm_host.h"
-#include "dsm_host_util.h"
+#include "dsm_trace_host.h"
 
 #define DG_BLOCKS 2048          // workgroups a launch aims at (256 compute units x 8)
 
@@ -77,8 +76,8 @@ extern "C" int dsm_diag_debug_set_parts(int parts)
 }
 
 // d_sum, d_first, d_bsq [V][G][4] int64 and d_flips [V][G] int32, zeroed here; d_inv [B * L][G]: inv[t][perm[t][g]] = g; B even
-int k_trace_batch_stats(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const uint8_t *d_inv, int B, int L, int64_t *d_sum,
-                        int64_t *d_first, int64_t *d_bsq, int32_t *d_flips)
+int k_trace_batch_stats(dsm_ctx *c, const TraceView &tr, const uint8_t *d_inv, int B, int L, int64_t *d_sum, int64_t *d_first,
+                        int64_t *d_bsq, int32_t *d_flips)
 {
     const int V = c->V, G = c->G;
     const size_t nt = (size_t)V * G * 4;
@@ -91,8 +90,8 @@ int k_trace_batch_stats(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, 
     const long long n = (long long)B * L;
     int gz = g_diag_parts > 0 ? g_diag_parts : (int)std::min<long long>({(DG_BLOCKS + gx * G - 1) / (gx * G), (n + 31) / 32, 1024});
     gz = std::max(1, std::min({gz, B, 65535}));                  // a part holds whole batches; gridDim.z
-    hipLaunchKernelGGL(trace_batch_stats_kernel, dim3((unsigned)gx, (unsigned)G, (unsigned)gz), dim3(256), 0, c->stream, trace,
-                       trace_stride, d_inv, B, L, V, G, reinterpret_cast<unsigned long long *>(d_sum),
+    hipLaunchKernelGGL(trace_batch_stats_kernel, dim3((unsigned)gx, (unsigned)G, (unsigned)gz), dim3(256), 0, c->stream, tr.tau,
+                       tr.tau_stride, d_inv, B, L, V, G, reinterpret_cast<unsigned long long *>(d_sum),
                        reinterpret_cast<unsigned long long *>(d_first), reinterpret_cast<unsigned long long *>(d_bsq), d_flips);
     HIP_TRY(hipGetLastError());
     return DSM_OK;

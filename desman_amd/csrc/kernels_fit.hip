@@ -1,5 +1,5 @@
 // kernels_fit.hip -- gfx950 kernels for the posterior predictive fit of a chain per sample and per position, from the traces that stay
-// resident after an update call (api.hip: dsm_ctx_trace_fit_stats; desman_amd/check.py).
+// resident after an update call (api_trace.hip: dsm_ctx_trace_fit_stats; desman_amd/check.py).
 //
 //   trace_fit_kernel<NSL>   per stored iteration t and cell (v, s) with counts n_b, N = sum_b n_b > 0, and the likelihood's own
 //                           p_b = sum_g gamma_t[s][g] eta_t[tau_t[v][g]][b], k = #{b : p_b > 0}:
@@ -15,8 +15,7 @@
 #include <algorithm>
 #include <math.h>
 
-#include "dsm_host.h"
-#include "dsm_host_util.h"
+#include "dsm_trace_host.h"
 #include "dsm_fit_cell.h"
 
 #define FIT_BLOCKS 2048         // workgroups a launch aims at (256 compute units x 8)
@@ -209,12 +208,11 @@ static void fit_launch(dsm_ctx *c, const FitPlan &pl, const FitParams &p)
 
 // n_it >= 1 iterations; d_samp_part [parts][tiles][S][4], d_pos_part [parts][V][4], d_cell_part [parts][V][S] (with d_cell, else null)
 // are scratch the caller sized by fit_plan; d_sample [S][4], d_position [V][4], d_cell [V][S] or null
-int k_trace_fit_stats(dsm_ctx *c, const FitPlan &pl, const uint64_t *trace, size_t trace_stride, const double *gamma, const double *eta,
-                      int n_it, double *d_samp_part, double *d_pos_part, double *d_cell_part, double *d_sample, double *d_position,
-                      double *d_cell)
+int k_trace_fit_stats(dsm_ctx *c, const FitPlan &pl, const TraceView &tr, int n_it, double *d_samp_part, double *d_pos_part,
+                      double *d_cell_part, double *d_sample, double *d_position, double *d_cell)
 {
     FitParams p;
-    p.cnt = c->cnt_vs; p.trace = trace; p.trace_stride = trace_stride; p.gamma = gamma; p.eta = eta;
+    p.cnt = c->cnt_vs; p.trace = tr.tau; p.trace_stride = tr.tau_stride; p.gamma = tr.gamma; p.eta = tr.eta;
     p.n = n_it; p.V = c->V; p.S = c->S; p.G = c->G; p.gc = pl.gc;
     p.lpv_log2 = 0;
     while ((1 << p.lpv_log2) < pl.lpv) ++p.lpv_log2;

@@ -1,5 +1,5 @@
 // kernels_ppc.hip -- gfx950 kernels for the posterior predictive p-values of a chain per sample and per position, from replicate tables
-// drawn at the stored iterations (api.hip: dsm_ctx_trace_ppc; desman_amd/check.py; the definition stands in
+// drawn at the stored iterations (api_trace.hip: dsm_ctx_trace_ppc; desman_amd/check.py; the definition stands in
 // include/desman_hip.h above the call).
 //
 //   trace_ppc_kernel<NSL>     per used iteration t of the launch: p_b (dsm_fit_cell.h, shared with trace_fit_kernel), X_obs and the
@@ -15,8 +15,7 @@
 #include <algorithm>
 #include <math.h>
 
-#include "dsm_host.h"
-#include "dsm_host_util.h"
+#include "dsm_trace_host.h"
 #include "dsm_fit_cell.h"
 #include "dsm_binom.h"
 
@@ -308,9 +307,8 @@ static int ppc_launch(dsm_ctx *c, const PpcPlan &pl, int parts, const PpcParams 
 }
 
 // n_used >= 1; the six outputs are device buffers, zero on entry
-int k_trace_ppc(dsm_ctx *c, const PpcPlan &pl, const uint64_t *trace, size_t trace_stride, const double *gamma, const double *eta, int it0,
-                int stride, int n_used, int R, uint32_t key0, uint32_t key1, unsigned long long *d_ge_s, unsigned long long *d_ge_v,
-                double *d_rep_s, double *d_rep_v, double *d_obs_s, double *d_obs_v)
+int k_trace_ppc(dsm_ctx *c, const PpcPlan &pl, const TraceView &tr, int it0, int stride, int n_used, int R, uint32_t key0, uint32_t key1,
+                unsigned long long *d_ge_s, unsigned long long *d_ge_v, double *d_rep_s, double *d_rep_v, double *d_obs_s, double *d_obs_v)
 {
     const size_t V = (size_t)c->V, S = (size_t)c->S;
     DevBuf<double> samp_part, obs_part, pos_it, trep, tobs, carry;
@@ -321,7 +319,7 @@ int k_trace_ppc(dsm_ctx *c, const PpcPlan &pl, const uint64_t *trace, size_t tra
     DSM_TRY(tobs.alloc((size_t)pl.ct * S));
     DSM_TRY(carry.alloc(S * 2));
     PpcParams p;
-    p.cnt = c->cnt_vs; p.trace = trace; p.trace_stride = trace_stride; p.gamma = gamma; p.eta = eta; p.log_tab = c->log_tab;
+    p.cnt = c->cnt_vs; p.trace = tr.tau; p.trace_stride = tr.tau_stride; p.gamma = tr.gamma; p.eta = tr.eta; p.log_tab = c->log_tab;
     p.V = c->V; p.S = c->S; p.G = c->G; p.gc = pl.gc;
     p.lpv_log2 = 0;
     while ((1 << p.lpv_log2) < pl.lpv) ++p.lpv_log2;

@@ -29,8 +29,7 @@
 #include <vector>
 
 #include "dsm_device.h"
-#include "dsm_host.h"
-#include "dsm_host_util.h"
+#include "dsm_trace_host.h"
 #include "log_table.h"
 
 #define PRED_WAVES 4096                     // wavefronts a launch aims at (256 compute units x 16) before iterations are cut into parts
@@ -228,13 +227,8 @@ extern "C" int dsm_pred_debug_set_parts(int parts)
 extern "C" int dsm_ctx_trace_predictive(dsm_ctx *c, const int64_t *counts, int N, int it0, int n_it, int stride, double *lppd,
                                         double *mean, double *var, double *logz_it)
 {
-    DSM_TRY(dsm_ctx_enter(c, false));                  // everything below runs on c->stream
-    if (!c->have_state) { dsm_set_error("no chain state: call dsm_ctx_set_state first"); return DSM_ERR_STATE; }
-    if (!c->tau_trace) { dsm_set_error("trace_predictive: no update has run"); return DSM_ERR_STATE; }
-    if (it0 < 0 || n_it < 0 || it0 > c->n_trace || n_it > c->n_trace - it0) {
-        dsm_set_error("trace_predictive: iterations %d .. %d + %d outside the trace of %d", it0, it0, n_it, c->n_trace);
-        return DSM_ERR_ARG;
-    }
+    DSM_TRY(trace_range(c, "trace_predictive", it0, n_it));
+    BIND(c);                                           // everything below runs on c->stream
     if (stride < 1) { dsm_set_error("trace_predictive: stride %d", stride); return DSM_ERR_ARG; }
     const int S = c->S, G = c->G;
     if (G > DSM_ASSIGN_MAX_G) {
@@ -263,7 +257,6 @@ extern "C" int dsm_ctx_trace_predictive(dsm_ctx *c, const int64_t *counts, int N
     if (counts) DSM_TRY(d_x.alloc((size_t)NC * S * 4));
     DSM_TRY(d_part.alloc((size_t)TC * NC * P * 2)); DSM_TRY(d_logz.alloc((size_t)nu * NC));
     DSM_TRY(d_lppd.alloc(NC)); DSM_TRY(d_mean.alloc(NC)); DSM_TRY(d_var.alloc(NC));
-    const size_t sg = (size_t)S * G;
     std::vector<int32_t> x32;
     for (int n0 = 0; n0 < N; n0 += NC) {
         const int n = std::min(NC, N - n0);
@@ -273,8 +266,8 @@ extern "C" int dsm_ctx_trace_predictive(dsm_ctx *c, const int64_t *counts, int N
             const int nt = std::min(TC, nu - u0);
             int parts = g_pred_parts > 0 ? g_pred_parts : (int)((PRED_WAVES + (long long)n * P - 1) / ((long long)n * P));
             parts = std::max(1, std::min({parts, nt, 65535}));
-            const size_t row0 = (size_t)it0 + (size_t)u0 * stride;
-            PredParams q{cnt, c->gamma_trace + row0 * sg, c->eta_trace + row0 * 16, (size_t)stride, c->log_tab, n, S, G, P, bpp,
+            const TraceView tr = trace_view(c, it0 + u0 * stride);
+            PredParams q{cnt, tr.gamma, tr.eta, (size_t)stride, c->log_tab, n, S, G, P, bpp,
                          nt, (nt + parts - 1) / parts, d_part};
             hipLaunchKernelGGL(pred_kernel, dim3((unsigned)n * (unsigned)P, (unsigned)parts), dim3(64), lds, c->stream, q);
             HIP_TRY(hipGetLastError());

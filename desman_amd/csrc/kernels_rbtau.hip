@@ -1,4 +1,4 @@
-// kernels_rbtau.hip -- the Rao-Blackwellised tau posterior of the positions of the fit from the resident traces (api.hip:
+// kernels_rbtau.hip -- the Rao-Blackwellised tau posterior of the positions of the fit from the resident traces (api_trace.hip:
 // dsm_ctx_trace_rb_marginals; desman_amd/marginals.py).
 //
 //   rb_tau_kernel<LPV, NSL>   for every stored iteration t, position v and haplotype g the full conditional of tau_vg given the rest of
@@ -10,6 +10,7 @@
 //     q_a        = exp(L_a - max) / (((e_0 + e_1) + e_2) + e_3);  all four -inf: the one-hot of tau_t[v][g], counted in `dead`
 // No random number is drawn anywhere.
 #include "dsm_sweep_tile.h"
+#include "dsm_trace_host.h"
 
 struct RbParams : SweepTileParams {       // gamma / eta: the rows of the first used iteration; tau and nchange are not used
     const uint64_t *trace;                // the packed tau of the first used iteration
@@ -178,17 +179,17 @@ extern "C" int dsm_rbtau_debug_path(int S, int G, int out[2])
     return DSM_OK;
 }
 
-// The conditionals of n_it >= 1 stored iterations in batches of L (n_it a multiple of L), one launch: trace / gamma / eta = the rows of
+// The conditionals of n_it >= 1 stored iterations in batches of L (n_it a multiple of L), one launch: tr = the rows of
 // the first of them, d_perm [n_it][G]; d_sum, d_bsq and *d_dead zeroed by the caller, d_bs scratch of the same size as d_sum.
-int k_rb_tau(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const double *gamma, const double *eta, const uint8_t *d_perm, int n_it,
-             int L, double *d_bs, double *d_sum, double *d_bsq, unsigned long long *d_dead)
+int k_rb_tau(dsm_ctx *c, const TraceView &tr, const uint8_t *d_perm, int n_it, int L, double *d_bs, double *d_sum, double *d_bsq,
+             unsigned long long *d_dead)
 {
     RbParams p;
-    p.cnt_vs = c->cnt_vs; p.tau = nullptr; p.gamma = gamma; p.eta = eta;
+    p.cnt_vs = c->cnt_vs; p.tau = nullptr; p.gamma = tr.gamma; p.eta = tr.eta;
     p.log_tab = c->log_tab; p.nchange = nullptr;
     p.V = c->V; p.S = c->S; p.G = c->G;
     p.k0 = 0; p.k1 = 0; p.iter = 0;
-    p.trace = trace; p.trace_stride = trace_stride; p.perm = d_perm;
+    p.trace = tr.tau; p.trace_stride = tr.tau_stride; p.perm = d_perm;
     p.bs = d_bs; p.sum = d_sum; p.bsq = d_bsq; p.dead = d_dead;
     p.n_it = n_it; p.L = L;
     return sweep_tile_dispatch(p, "rb marginals: ", "rb marginals", [&](auto LL, auto N, int grid, size_t sh) {

@@ -1,5 +1,5 @@
 // kernels_relabel.hip -- gfx950 kernels that reduce the resident tau trace (dsm_ctx::tau_trace, one packed word per position and stored
-// iteration, 2 bits per haplotype) to what label-switch-aware summaries need (api.hip: dsm_ctx_trace_snd, dsm_ctx_get_tau_sum_perm;
+// iteration, 2 bits per haplotype) to what label-switch-aware summaries need (api_trace.hip: dsm_ctx_trace_snd, dsm_ctx_get_tau_sum_perm;
 // desman_amd/relabel.py).
 //
 //   trace_snd_kernel      snd[t][g][h] = #{v : tau_t[v][g] != ref_t[v][h]}, ref = one fixed word table or tau_t itself
@@ -9,7 +9,7 @@
 // for any grid and any order.
 #include <algorithm>
 
-#include "dsm_host.h"
+#include "dsm_trace_host.h"
 
 #define RL_HT 8                 // reference haplotypes per tile: their counts of one 64-position step live in scalar registers
 #define RL_BLOCKS 2048          // workgroups a launch aims at (256 compute units x 8)
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void tau_sum_perm_kernel(const uint64_t *__res
 }
 
 // d_out [n_it][G][Gr] int32, zeroed here.  ref = nullptr: every iteration against itself.
-int k_trace_snd(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const uint64_t *ref, int Gr, int n_it, int *d_out)
+int k_trace_snd(dsm_ctx *c, const TraceView &tr, const uint64_t *ref, int Gr, int n_it, int *d_out)
 {
     if (n_it < 1) return DSM_OK;
     const int V = c->V, G = c->G;
@@ -100,22 +100,22 @@ int k_trace_snd(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const ui
     for (int t0 = 0; t0 < n_it; t0 += 65535) {                     // gridDim.y
         const int nt = std::min(n_it - t0, 65535);
         const int gx = std::max(1, std::min((RL_BLOCKS + nt - 1) / nt, (nstep + 3) / 4));
-        hipLaunchKernelGGL(trace_snd_kernel, dim3((unsigned)gx, (unsigned)nt), dim3(256), 0, c->stream, trace + (size_t)t0 * trace_stride,
-                           trace_stride, ref, V, G, Gr, d_out + (size_t)t0 * npair);
+        hipLaunchKernelGGL(trace_snd_kernel, dim3((unsigned)gx, (unsigned)nt), dim3(256), 0, c->stream, tr.tau + (size_t)t0 * tr.tau_stride,
+                           tr.tau_stride, ref, V, G, Gr, d_out + (size_t)t0 * npair);
         HIP_TRY(hipGetLastError());
     }
     return DSM_OK;
 }
 
 // d_out [V][G][4] int64, zeroed here; d_inv [n][G]: inv[t][perm[t][g]] = g.
-int k_tau_sum_perm(dsm_ctx *c, const uint64_t *trace, size_t trace_stride, const uint8_t *d_inv, int n, int64_t *d_out)
+int k_tau_sum_perm(dsm_ctx *c, const TraceView &tr, const uint8_t *d_inv, int n, int64_t *d_out)
 {
     const int V = c->V, G = c->G;
     HIP_TRY(hipMemsetAsync(d_out, 0, (size_t)V * G * 4 * sizeof(int64_t), c->stream));
     if (n < 1) return DSM_OK;
     const int gx = (V + 255) / 256;
     const int gz = std::max(1, std::min({(RL_BLOCKS + gx * G - 1) / (gx * G), (n + 31) / 32, 1024}));
-    hipLaunchKernelGGL(tau_sum_perm_kernel, dim3((unsigned)gx, (unsigned)G, (unsigned)gz), dim3(256), 0, c->stream, trace, trace_stride,
+    hipLaunchKernelGGL(tau_sum_perm_kernel, dim3((unsigned)gx, (unsigned)G, (unsigned)gz), dim3(256), 0, c->stream, tr.tau, tr.tau_stride,
                        d_inv, n, V, G, reinterpret_cast<unsigned long long *>(d_out));
     HIP_TRY(hipGetLastError());
     return DSM_OK;

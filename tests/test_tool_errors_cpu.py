@@ -154,3 +154,24 @@ def test_debug_setter(name):
         assert fn(-1) == ERR_ARG and lib.dsm_last_error().decode() == SETTERS[name]
     finally:
         assert fn(0) == OK
+
+
+# ---- the entry points that read the resident traces (desman_amd/csrc/api_trace.hip, kernels_pred.hip): a null context is refused by the
+# check they share before anything else is looked at, so the other arguments may be anything
+TRACE_CALLS = {
+    "dsm_ctx_trace_snd": (1, None, 0, 0, 1, None),
+    "dsm_ctx_get_tau_sum_perm": (None, 0, 1, None),
+    "dsm_ctx_trace_batch_stats": (None, 0, 1, 0, None, None, None, None),
+    "dsm_ctx_trace_fit_stats": (0, 1, None, None, None),
+    "dsm_ctx_trace_rb_marginals": (None, 0, 1, 0, None, None, None),
+    "dsm_ctx_trace_ppc": (0, 1, 0, 0, 0, None, None, None, None, None, None),
+    "dsm_ctx_trace_predictive": (None, -1, 0, 1, 0, None, None, None, None),
+    "dsm_ctx_debug_set_trace": (None, -1),
+    "dsm_ctx_debug_set_param_trace": (None, None, -1),
+}
+
+
+@pytest.mark.parametrize("name", sorted(TRACE_CALLS))
+def test_trace_entry_point_without_a_context(name):
+    lib = _lib.load()
+    assert getattr(lib, name)(None, *TRACE_CALLS[name]) == ERR_ARG and lib.dsm_last_error().decode() == "null context"
