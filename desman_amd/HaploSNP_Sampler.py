@@ -550,6 +550,21 @@ class HaploSNP_Sampler:
             return m
         return self._diagnosed("rb", batch_len, make)
 
+    def tauPairs(self, batch_len=None, stride=None):
+        """the Rao-Blackwellised joint posterior of the bases of every two haplotypes (marginals.rb_pairs: J, p_same [V, P(, 4, 4)],
+        dist, dist_mcse, differ [P], pairs, dead) from every stride-th stored iteration (None: marginals.pairs_stride), with tables
+        (marginals.pair_tables of J), flags (marginals.pair_flags against the calls of tauMarginals) and star_dist (the count distance
+        of tau_star under the same labels); under the relabelling the diagnostics are made under; kept until the next update"""
+        def make(L, perm):
+            K = _marginals.pairs_stride(self.max_iter, L) if stride is None else int(stride)
+            m = _marginals.rb_pairs(self._trace_ctx().trace_rb_pairs(L, perm=perm, stride=K))
+            m["stride"] = K
+            m["tables"] = _marginals.pair_tables(m["J"])
+            m["flags"] = _marginals.pair_flags(self.tauMarginals(L)["calls"]["prob"], m["pairs"])
+            m["star_dist"] = _marginals.star_distance(self._star_labelled(), m["pairs"])
+            return m
+        return self._diagnosed(("rb_pairs", stride), batch_len, make)
+
     # ---- posterior predictive fit of the last update() from the resident traces (desman_amd/check.py, DESIGN.md sec. 8g)
     def fitCheck(self, cells=False):
         """(per-sample table, per-position table) -- with ``cells`` also the [V, S] posterior mean of Pearson's X per cell -- of the

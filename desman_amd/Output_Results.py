@@ -266,6 +266,34 @@ class Output_Results:
                      "%d disagree with Tau_star, %d dead cell-iterations"
                      % (mean_name, s["expected_wrong"], s["cells"], s["low"], marginals.PROB_LOW, s["disagree"], s["dead"]))
 
+    # ---- `desman --marginal-pairs`: the joint posterior of two haplotypes' bases (desman_amd/marginals.py)
+    def output_Tau_pairs(self, pr):
+        """SND_rb.csv: one row per pair -- g, h, dist (the expected number of positions at which the two differ), dist_mcse (batch
+        means), differ (the share of positions with P(same base) < 0.5), star (the count distance of Tau_star); Tau_pairs.csv: one row
+        per flagged (position, pair), position-major -- Contig, Position, g, h, pair (the most probable two bases, as letters), prob,
+        p_same, swap, mi, kind (HaploSNP_Sampler.tauPairs); and one log line"""
+        from . import marginals
+        pairs = np.asarray(pr["pairs"])
+        snd = pd.DataFrame({"g": pairs[:, 0], "h": pairs[:, 1], "dist": pr["dist"], "dist_mcse": pr["dist_mcse"], "differ": pr["differ"],
+                            "star": pr["star_dist"]})
+        snd.to_csv(self._path("SND_rb.csv"), index=False)
+        v, p = np.nonzero(pr["flags"])
+        t = pr["tables"]
+        best = t["best"][v, p]
+        letters = np.array(list("ACGT"))
+        frame = pd.DataFrame({"Position": np.asarray(self.filtered_position)[v], "g": pairs[p, 0], "h": pairs[p, 1],
+                              "pair": np.char.add(letters[best >> 2], letters[best & 3]), "prob": t["best_prob"][v, p],
+                              "p_same": t["p_same"][v, p], "swap": t["swap"][v, p], "mi": t["mi"][v, p], "kind": t["kind"][v, p]},
+                             index=np.asarray(self.filtered_contig_names)[v])
+        frame.index.name = "Contig"
+        frame.to_csv(self._path("Tau_pairs.csv"))
+        kinds = t["kind"][v, p]
+        near = int(np.argmin(pr["dist"])) if len(pairs) else -1
+        logging.info("SND_rb.csv, Tau_pairs.csv written from every %d-th stored iteration: %d flagged (position, pair) rows (a call below %g), "
+                     "%d of kind phase, %d of kind base; the closest pair is (%d, %d) at an expected distance of %.2f +- %.2f"
+                     % (pr["stride"], len(v), marginals.PAIR_FLAG_LOW, int((kinds == "phase").sum()), int((kinds == "base").sum()),
+                        pairs[near, 0], pairs[near, 1], pr["dist"][near], pr["dist_mcse"][near]))
+
     # ---- `desman --check`: posterior predictive fit per sample and per position (desman_amd/check.py)
     _FIT_COLUMNS = (("cells", "cells"), ("X2", "X2"), ("expected", "expected"), ("z", "z"), ("deviance", "deviance"))
 

@@ -130,6 +130,9 @@ SIGNATURES = {
     "dsm_ctx_debug_set_param_trace": (_i, [_vp, _vp, _vp, _i]),
     "dsm_ctx_trace_rb_marginals": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, C.POINTER(C.c_longlong)]),
     "dsm_rbtau_debug_path": (_i, [_i, _i, C.POINTER(_i)]),
+    "dsm_ctx_trace_rb_pairs": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, C.POINTER(C.c_longlong)]),
+    "dsm_rbpair_debug_path": (_i, [_i, _i, C.POINTER(_i)]),
+    "dsm_rbpair_debug_set_chunk": (_i, [_i]),
     "dsm_nmft_set": (_i, [_vp, _f64p, _f64p, _i]),
     "dsm_nmft_get": (_i, [_vp, _vp, _vp]),
     "dsm_nmft_factorize": (_i, [_vp, _i, _d, _i, C.POINTER(_i), _vp]),
@@ -379,6 +382,19 @@ def rbtau_debug_path(S, G):
     out = (C.c_int * 2)()
     check(load().dsm_rbtau_debug_path(int(S), int(G), out))
     return int(out[0]), int(out[1])
+
+
+def rbpair_debug_path(S, G):
+    """test hook: (lanes per position, sample slots per lane) of the kernel of Context.trace_rb_pairs for S samples; nothing is
+    launched"""
+    out = (C.c_int * 2)()
+    check(load().dsm_rbpair_debug_path(int(S), int(G), out))
+    return int(out[0]), int(out[1])
+
+
+def rbpair_debug_set_chunk(positions=0):
+    """test hook: positions per launch of Context.trace_rb_pairs (0 = by the scratch bound); results do not depend on it"""
+    check(load().dsm_rbpair_debug_set_chunk(int(positions)))
 
 
 def diag_debug_set_parts(parts=0):
@@ -1018,6 +1034,27 @@ class Context:
         check(self.lib.dsm_ctx_trace_rb_marginals(self._h, _ptr(p), int(it0), n_it, L, *ptrs, C.byref(dead)))
         B = 2 * (n_it // (2 * L)) if L >= 1 else 0
         out.update(dead=int(dead.value), B=B, N=B * L, L=L)
+        return out
+
+    def trace_rb_pairs(self, batch_len, perm=None, it0=0, n_it=None, stride=1, want=("joint", "same_batch")):
+        """Rao-Blackwellised joint posterior of the bases of two haplotypes (include/desman_hip.h: dsm_ctx_trace_rb_pairs;
+        desman_amd/marginals.py): the sixteen-state full conditional q of every (tau[v][g], tau[v][h]), g < h, under (tau_t, gamma_t,
+        eta_t), over the iterations it0, it0 + stride, ... below it0 + n_it -- of these n_used the LAST N = B L (L = batch_len,
+        B = 2 (n_used // (2 L))) -- under the labels of ``perm`` ([n_it, G], rows counted from it0; None = identity): a dict of joint
+        [V, P, 4, 4] (the sum of q; [a, a'] = the bases of the lower and the higher label) and same_batch [B, P] float64 (those named in
+        ``want``), pairs [P, 2] (the labels of every pair, lexicographic), dead, n_used, B, N and L"""
+        n_it = self._trace_n_it(it0, n_it)
+        L, stride = int(batch_len), int(stride)
+        p = perm if perm is None else self._trace_perm("trace_rb_pairs", perm, n_it)
+        n_used = -(-n_it // stride) if stride >= 1 and n_it > 0 else 0
+        B = 2 * (n_used // (2 * L)) if L >= 1 else 0
+        G = self.G
+        P = G * (G - 1) // 2
+        out, ptrs = self._trace_outputs("trace_rb_pairs", want, dict(joint=(self.V, P, 4, 4), same_batch=(B, P)))
+        dead = C.c_longlong(0)
+        check(self.lib.dsm_ctx_trace_rb_pairs(self._h, _ptr(p), int(it0), n_it, stride, L, *ptrs, C.byref(dead)))
+        pairs = np.array([(g, h) for g in range(G) for h in range(g + 1, G)], dtype=np.int64).reshape(P, 2)
+        out.update(pairs=pairs, dead=int(dead.value), n_used=n_used, B=B, N=B * L, L=L)
         return out
 
     def trace_predictive(self, counts=None, it0=0, n_it=None, stride=1, want=("lppd", "mean", "var")):

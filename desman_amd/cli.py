@@ -21,6 +21,7 @@ from .Output_Results import Output_Results
 from .Variant_Filter import Variant_Filter
 
 POSITION_SELECT_SEED = 238329          # fixed seed of the -r position draw (bin/desman:85-86)
+DEFAULT_ITER = 250                     # the iterations a chain stores without -i, or with a bare -i: the sampler's own default
 
 # (short, long, kwargs) -- defaults and nargs/const quirks as in bin/desman:25-59
 _FLAGS = [
@@ -33,7 +34,7 @@ _FLAGS = [
     ('-a', '--assign_file', dict(type=str, help="(dead upstream) extra positions to assign")),
     ('-o', '--output_dir', dict(type=str, default="output", help="directory for all result files")),
     ('-p', '--optimiseP', dict(default=True, type=bool, help="optimise the mixture proportion in the filter")),
-    ('-i', '--no_iter', dict(nargs='?', const=250, type=int, help="Gibbs iterations per phase")),
+    ('-i', '--no_iter', dict(nargs='?', const=DEFAULT_ITER, type=int, help="Gibbs iterations per phase")),
     ('-m', '--min_coverage', dict(type=float, default=5.0, help="drop samples whose mean depth is not above this")),
     ('-q', '--max_qvalue', dict(default=1.0e-3, type=float, help="q-value cut of the variant filter")),
     ('-s', '--random_seed', dict(default=23724839, type=int, help="seed of both sampler RNG streams")),
@@ -100,6 +101,15 @@ def build_parser():
                          "Tau_rb_MCSE.csv (its Monte Carlo standard error by batch means; batch length as --diagnose [L]) and "
                          "Tau_calls.csv (per position and haplotype: the most probable base, its probability, the base of Tau_star, "
                          "whether they agree, the entropy); with --relabel / --relabel-ref under that relabelling (extension)")
+    ap.add_argument('--marginal-pairs', dest='marginal_pairs', nargs='?', const=True, default=None, type=int, metavar='K',
+                    help="with --marginals (implied): also write the Rao-Blackwellised JOINT posterior of the bases of every two "
+                         "haplotypes, from every K-th stored iteration: SND_rb.csv (per pair: the expected number of positions at which "
+                         "they differ, its Monte Carlo standard error, the share of positions that probably differ, the distance in "
+                         "Tau_star) and Tau_pairs.csv (per position and pair with a doubtful call in Tau_calls.csv: the most probable "
+                         "two bases, P(same base), the mass that only asks which of the two carries which base, the mutual information, "
+                         "and kind = phase where the data know the two bases but not their owners, else base); without K the largest "
+                         "stride that still uses max(50, two batches) iterations: K = max(1, iterations // max(50, 2 L)), L the batch "
+                         "length of --diagnose [L]; -g at least 2 (extension)")
     ap.add_argument('--pair-moves', dest='pair_moves', nargs='?', const=PAIR_MOVES, default=None, type=int, metavar='E',
                     help="add joint moves of two haplotypes to the Gibbs chain, burn-in and sampling alike: the sweep of every E-th "
                          "iteration (default %d: a convention, not tuned) is followed by a pass that redraws the bases of every pair of "
@@ -239,11 +249,16 @@ def _report_relabel(report, chain, ref):
     report.output_Haplotype_stability(chain.haplotypeStability())
 
 
+def _stored_iterations(opts):
+    """the iterations the chain of this run will store"""
+    return DEFAULT_ITER if opts.no_iter is None else opts.no_iter
+
+
 def _batch_len(opts, flag):
     """the batch length of `flag` (--diagnose, --marginals) -- the L of --diagnose [L] where one is given, else floor(sqrt(iterations))
     -- checked against the iterations a chain will store; the run stops here, before any chain, if there are fewer than 2 L of them"""
     from . import diagnose
-    n = 250 if opts.no_iter is None else opts.no_iter            # the sampler's own default
+    n = _stored_iterations(opts)
     given = opts.diagnose is not None and opts.diagnose is not True          # a bare --diagnose parses as True, --diagnose L as the int
     L = opts.diagnose if given else diagnose.default_batch_len(n)
     if L < 1:
@@ -259,8 +274,36 @@ def _diagnose_batch_len(opts):
 
 
 def _marginals_batch_len(opts):
-    """--marginals: the batch length of Tau_rb_MCSE.csv.  None without the option."""
-    return _batch_len(opts, "--marginals") if opts.marginals else None
+    """--marginals (--marginal-pairs implies it): the batch length of Tau_rb_MCSE.csv.  None without the option."""
+    return _batch_len(opts, "--marginals") if opts.marginals or opts.marginal_pairs is not None else None
+
+
+def _marginal_pairs_stride(opts):
+    """--marginal-pairs [K]: the stride K of a run whose options _marginal_pairs_options has accepted -- the K given or, for a bare
+    flag, marginals.pairs_stride of the stored iterations and the batch length.  None without the option."""
+    if opts.marginal_pairs is None:
+        return None
+    if opts.marginal_pairs is not True:                          # a bare flag parses as True, --marginal-pairs K as the int
+        return opts.marginal_pairs
+    from . import marginals
+    return marginals.pairs_stride(_stored_iterations(opts), _batch_len(opts, "--marginals"))
+
+
+def _marginal_pairs_options(opts):
+    """--marginal-pairs [K]: refused here, before any chain, where --marginals is, for fewer than two haplotypes and for a K that leaves
+    fewer than two batches.  (The stride is not handed on with the batch lengths: what _extension_options returns is three keys, and
+    _marginal_pairs_stride costs nothing.)"""
+    if opts.marginal_pairs is None:
+        return
+    L = _batch_len(opts, "--marginals")
+    n = _stored_iterations(opts)
+    if opts.genomes < 2:
+        sys.exit("desman: --marginal-pairs: a pair needs two haplotypes; got -g %d" % opts.genomes)
+    K = _marginal_pairs_stride(opts)
+    if K < 1:
+        sys.exit("desman: --marginal-pairs: every K-th stored iteration needs K >= 1; got %d" % K)
+    if -(-n // K) < 2 * L:
+        sys.exit("desman: --marginal-pairs: every %d-th of %d stored iterations (-i) are fewer than two batches of %d" % (K, n, L))
 
 
 def _report_diagnose(report, chain, L):
@@ -275,6 +318,15 @@ def _report_marginals(report, chain, L):
     """--marginals: the Rao-Blackwellised tau marginals of the fitted chain, next to the usual files (which do not change); under the
     relabelling of --relabel / --relabel-ref where one was made"""
     report.output_Tau_marginals(chain.tauMarginals(L), relabelled=chain._diag_perm() is not None)
+
+
+def _report_marginal_pairs(report, chain, L, K):
+    """--marginal-pairs: the joint posterior of every two haplotypes' bases, next to the files of --marginals (which do not change);
+    under the same relabelling.  A chain that merged its haplotypes down to one has no pair."""
+    if chain.G < 2:
+        logging.info("--marginal-pairs: the chain kept one haplotype after merging identical ones: no pair, no file")
+        return
+    report.output_Tau_pairs(chain.tauPairs(L, K))
 
 
 def _check_options(opts, replicates=False):
@@ -348,6 +400,7 @@ def _extension_options(opts, replicates=False):
     pair_every = _pair_moves_options(opts, replicates)
     diag_len = _diagnose_batch_len(opts)
     marg_len = _marginals_batch_len(opts)
+    _marginal_pairs_options(opts)
     _check_options(opts, replicates)
     _predictive_options(opts, replicates)
     return dict(pair_every=pair_every, diag_len=diag_len, marg_len=marg_len)
@@ -361,6 +414,8 @@ def _report_extensions(opts, ext, report, flt, chain, ref, subsample):
         _report_diagnose(report, chain, ext["diag_len"])
     if ext["marg_len"] is not None:
         _report_marginals(report, chain, ext["marg_len"])
+    if opts.marginal_pairs is not None:
+        _report_marginal_pairs(report, chain, ext["marg_len"], _marginal_pairs_stride(opts))
     if opts.check:
         _report_check(report, chain, opts.check_cells)
     if opts.check_reps is not None:

@@ -1,5 +1,5 @@
 // api_trace.hip -- the entry points that reduce the chain's resident traces, and the test hooks that plant a trace (host code only; the
-// kernels are in kernels_relabel / _diag / _fit / _rbtau / _ppc.hip).  dsm_ctx_trace_predictive lies next to its kernels in
+// kernels are in kernels_relabel / _diag / _fit / _rbtau / _rbpair / _ppc.hip).  dsm_ctx_trace_predictive lies next to its kernels in
 // kernels_pred.hip.  The scaffolding all of them share is dsm_trace_host.h.
 #include <math.h>
 #include <string.h>
@@ -189,6 +189,69 @@ extern "C" int dsm_ctx_trace_rb_marginals(dsm_ctx *c, const uint8_t *perm, int i
     DSM_TRY(k_rb_tau(c, trace_view(c, it0 + b.skip), d_perm, b.B * b.L, b.L, d_bs, d_sum, d_bsq, d_dead));
     if (sum) HIP_TRY(hipMemcpyAsync(sum, d_sum, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (bsq) HIP_TRY(hipMemcpyAsync(bsq, d_bsq, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (dead) HIP_TRY(hipMemcpyAsync(dead, d_dead, sizeof *dead, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DSM_OK;
+}
+
+// Rao-Blackwellised joint posterior of two haplotypes' bases over stored iterations (kernels_rbpair.hip): the range and
+// perm rules of dsm_ctx_trace_batch_stats, the stride of dsm_ctx_trace_predictive, the batch rule on the iterations the stride takes; the
+// positions go through the device in chunks (rb_pairs_chunk), in ascending order; nothing of the chain is written
+extern "C" int dsm_ctx_trace_rb_pairs(dsm_ctx *c, const uint8_t *perm, int it0, int n_it, int stride, int batch_len, double *joint,
+                                      double *same_batch, long long *dead)
+{
+    DSM_TRY(trace_range(c, "trace_rb_pairs", it0, n_it));
+    if (stride < 1) { dsm_set_error("trace_rb_pairs: stride %d", stride); return DSM_ERR_ARG; }
+    const int nu = (int)(((long long)n_it + stride - 1) / stride);
+    TraceBatches b;
+    DSM_TRY(trace_batches("trace_rb_pairs", nu, batch_len, &b));
+    const int G = c->G, V = c->V;
+    std::vector<uint8_t> lab;                                                 // all n_it rows of perm as they are
+    DSM_TRY(trace_perm_rows("trace_rb_pairs", perm, n_it, G, 0, false, lab));
+    if (G > DSM_MAX_G) { dsm_set_error("trace_rb_pairs: G=%d exceeds DSM_MAX_G=%d", G, DSM_MAX_G); return DSM_ERR_UNSUPPORTED; }
+    const size_t P = (size_t)G * (G - 1) / 2;
+    if (P == 0) return DSM_OK;                                                // one haplotype has no pair: nothing to write
+    if (nu == 0) {
+        if (joint) std::fill(joint, joint + (size_t)V * P * 16, 0.0);        // (same_batch has no batch)
+        if (dead) *dead = 0;
+        return DSM_OK;
+    }
+    { int lpv, nsl; DSM_TRY(tau_shape(c->S, &lpv, &nsl)); }                     // S <= DSM_MAX_S, before anything is allocated
+    // per used iteration and pair (g, h) in lexicographic order: the index of the pair of their labels, and whether they descend
+    const int n_used = b.B * b.L;
+    std::vector<uint16_t> slot((size_t)n_used * P);
+    for (int u = 0; u < n_used; ++u) {
+        const uint8_t *row = lab.data() + (size_t)(b.skip + u) * stride * G;
+        size_t pi = 0;
+        for (int g = 0; g < G; ++g)
+            for (int h = g + 1; h < G; ++h, ++pi) {
+                const int lo = std::min(row[g], row[h]), hi = std::max(row[g], row[h]);
+                slot[(size_t)u * P + pi] = (uint16_t)(((lo * (2 * G - lo - 1) / 2 + (hi - lo - 1)) << 1) | (row[g] > row[h] ? 1 : 0));
+            }
+    }
+    BIND(c);
+    const int chunk = rb_pairs_chunk(V, G, b.B, joint != nullptr, same_batch != nullptr);
+    const size_t bp = (size_t)b.B * P;
+    DevBuf<double> d_joint, d_same, d_sb;
+    DevBuf<unsigned long long> d_dead;
+    DevBuf<uint16_t> d_slot;
+    if (joint) DSM_TRY(d_joint.alloc((size_t)chunk * P * 16));
+    if (same_batch) {
+        DSM_TRY(d_same.alloc(bp * chunk));
+        DSM_TRY(d_sb.alloc(bp));
+        HIP_TRY(hipMemsetAsync(d_sb, 0, bp * sizeof(double), c->stream));
+    }
+    DSM_TRY(d_dead.alloc(1));
+    DSM_TRY(d_slot.alloc(slot.size()));
+    HIP_TRY(hipMemsetAsync(d_dead, 0, sizeof(unsigned long long), c->stream));
+    HIP_TRY(hipMemcpyAsync(d_slot, slot.data(), slot.size() * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    const TraceView tr = trace_view(c, it0 + b.skip * stride);
+    for (int v0 = 0; v0 < V; v0 += chunk) {
+        const int nv = std::min(chunk, V - v0);
+        DSM_TRY(k_rb_pairs(c, tr, stride, d_slot, n_used, b.L, v0, nv, d_joint, d_same, d_sb, d_dead));
+        if (joint) HIP_TRY(hipMemcpyAsync(joint + (size_t)v0 * P * 16, d_joint, (size_t)nv * P * 16 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (same_batch) HIP_TRY(hipMemcpyAsync(same_batch, d_sb, bp * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (dead) HIP_TRY(hipMemcpyAsync(dead, d_dead, sizeof *dead, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DSM_OK;

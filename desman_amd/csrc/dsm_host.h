@@ -303,6 +303,15 @@ struct TraceView;
 int k_rb_tau(dsm_ctx *c, const TraceView &tr, const uint8_t *d_perm, int n_it, int L, double *d_bs, double *d_sum, double *d_bsq,
              unsigned long long *d_dead);
 
+// ---- launcher (kernels_rbpair.hip): the sixteen-state conditionals of every pair over the positions v0 .. v0 + nv - 1 and n_it >= 1 used
+// iterations (a multiple of L; `stride` trace iterations apart, the view is that of the first), d_slot [n_it][P] = (relabelled pair << 1) |
+// transposed; d_joint [nv][P][16] / d_same [B][nv][P] scratch, either may be null; d_same_batch [B][P] and *d_dead zeroed by the caller
+// before the first chunk, chunks in ascending position order.  rb_pairs_chunk: positions per launch under the scratch bound
+#define DSM_RBPAIR_SCRATCH_BYTES (128u << 20)
+int rb_pairs_chunk(int V, int G, int B, bool want_joint, bool want_same);
+int k_rb_pairs(dsm_ctx *c, const TraceView &tr, int stride, const uint16_t *d_slot, int n_it, int L, int v0, int nv, double *d_joint,
+               double *d_same, double *d_same_batch, unsigned long long *d_dead);
+
 // ---- the 4^G joint states of a position as assign_kernel and pred_kernel walk them (kernels_assign.hip): the GO outer haplotypes are
 // NB = 4^GO blocks of 64 states, cut into P = min(NB, 64) partials of bpp consecutive blocks, one wavefront each.  P depends on G only.
 struct JointSplit {

@@ -424,6 +424,43 @@ int dsm_ctx_trace_rb_marginals(dsm_ctx *ctx, const uint8_t *perm /*[n_it][G] or 
                                double *sum /*[V][G][4]*/, double *bsq /*[V][G][4]*/, long long *dead /*[1]*/);
 int dsm_rbtau_debug_path(int S, int G, int out[2]);
 
+/* Rao-Blackwellised JOINT posterior of the bases of two haplotypes at the positions of the fit (DESIGN.md sec. 8l;
+ * desman_amd/marginals.py): one device pass over the resident counts and the tau, gamma and eta traces.  Iteration numbering, and which
+ * (tau_t, gamma_t, eta_t) belongs to iteration t, are those of dsm_ctx_trace_fit_stats.  P = G (G - 1) / 2 pairs (g, h), g < h, pair
+ * p at the index of its place in lexicographic order.  For a used iteration t, a position v and a pair (g, h), with the other G - 2
+ * bases at their values in tau_t (the arithmetic of the pair pass, dsm_ctx_sample_tau_pairs, without its draw and without writing tau):
+ *     m_a[s]     = sum over k != g, h with tau_t[v][k] = a of gamma_t[s][k]                       (k ascending)
+ *     rest[s][b] = ((m_0 eta_t[0][b] + m_1 eta_t[1][b]) + m_2 eta_t[2][b]) + m_3 eta_t[3][b]
+ *     L_k        = sum over s, b with x[v][s][b] > 0 of x ln((rest[s][b] + eta_t[a][b] gamma_t[s][g]) + eta_t[a'][b] gamma_t[s][h]),
+ *                  k = 4 a + a'  (x exact in fp64; a zero count adds 0; p = 0 under a positive count makes L_k = -inf)
+ *     q_k        = exp(L_k - max) / (e_0 + e_1 + ... + e_15, added in this order)
+ * is the exact full conditional of (tau_vg, tau_vh); where all sixteen L_k are -inf, q is the one-hot of the current pair and the
+ * (position, pair, iteration) is counted in *dead.  Nothing is ever NaN for a finite, non-negative trace.  No random number is drawn.
+ * Range and perm validation (all n_it rows) are those of dsm_ctx_trace_batch_stats; stride >= 1 takes the iterations it0, it0 + stride,
+ * ... below it0 + n_it, n_used = ceil(n_it / stride) of them, as dsm_ctx_trace_predictive does; the batch rule applies to the taken
+ * ones: L = batch_len, B = 2 floor(n_used / (2 L)) batches, only the LAST B L of them are used.  With l = perm[t][g], l' = perm[t][h]
+ * (NULL: l = g, l' = h) the pair is accumulated as pair (min(l, l'), max(l, l')), and with l > l' the 4 x 4 matrix q is transposed first:
+ *     joint      [V][P][16] double   the sum of q_k over the used iterations, t ascending from 0
+ *     same_batch [B][P]     double   per batch the sum over the positions, ascending from 0, of the position's sum over the batch's
+ *                                    iterations, t ascending from 0, of ((q_0 + q_5) + q_10) + q_15 = P(both carry the same base)
+ *     dead       [1]                 (position, pair, iteration)s without a live state
+ * One order of summation per cell, no floating-point atomics: the same bits from call to call, for any grid and for any cut of the
+ * positions into chunks.  The positions go through the device in chunks so that the call's device scratch -- per position of a chunk
+ * P (16 [joint asked for] + B [same_batch asked for]) doubles -- stays within 128 MiB (a chunk has at least one position: at most
+ * P (16 + B) doubles where that is more), plus the B P results and the n_used P two-byte pair indices; at G = 32, P = 496, that is
+ * 2114 positions per launch with joint alone.  dsm_rbpair_debug_set_chunk(positions): test hook, positions per launch (0 = by the
+ * bound); results do not depend on it.
+ * Any output pointer may be NULL.  n_it = 0 succeeds and writes zeros (same_batch has no batch then).  G = 1 (P = 0) succeeds and
+ * writes nothing, *dead included.  DSM_ERR_STATE when no update has run; DSM_ERR_ARG for a range outside the trace, stride < 1,
+ * batch_len < 1, 0 < n_used < 2 batch_len, a perm row that is no permutation (nothing is written then).  After
+ * dsm_ctx_gibbs_update_fixed_tau every iteration is the held tau.  The chain state, both RNG streams, every trace and the MAP record
+ * are only read.  Limits: one context, G <= DSM_MAX_G, S <= DSM_MAX_S (DSM_ERR_UNSUPPORTED beyond).
+ *   dsm_rbpair_debug_path: test hook, out = {lanes per position, sample slots per lane} of the kernel instantiation for S samples.  */
+int dsm_ctx_trace_rb_pairs(dsm_ctx *ctx, const uint8_t *perm /*[n_it][G] or NULL*/, int it0, int n_it, int stride, int batch_len,
+                           double *joint /*[V][P][16]*/, double *same_batch /*[B][P]*/, long long *dead /*[1]*/);
+int dsm_rbpair_debug_path(int S, int G, int out[2]);
+int dsm_rbpair_debug_set_chunk(int positions);
+
 /* A8-A12: Init_NMFT (desman/Init_NMFT.py).  F is derived from the resident
  * counts (:49-60).  tau [4V][G] row v + a*V, gamma [G][S] as in the reference.
  * Every shape up to S = DSM_MAX_S, G = DSM_MAX_G has a kernel (tests/test_gpu_nmft_forms.py
